@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
-"""bench.py -- ONE JSON line: the headline (a UBM EM pass, TrainWorld's hot path) and every other single-GPU BASELINE config at its stated size.
+"""bench.py -- ONE JSON line: the headline (a UBM EM pass, TrainWorld's hot path); with --full, every other single-GPU BASELINE config
+at its stated size beside it.
 
 Headline (BASELINE.json configs[1]): 2048-Gaussian diagonal UBM, 60-dim float32 frames, 10 M synthetic frames resident in HBM per GPU.
 One step = one EM iteration: log-likelihood pass + full-posterior sufficient statistics over every frame (HIP, fp64 MFMA), the RCCL
 all-reduce of the 1.98 MB statistics when N > 1, the M-step, variance control and the model re-pack.  Metric: Gframe-Gaussian
 evaluations/s, whole job (all ranks).  Scaling is weak (10 M frames per GPU).
 
-Beside it, in the same line (DESIGN.md section 6 has the table):
+A plain run (no --full) sets up, warms up, times --steps EM steps and prints the headline line: nothing else runs.
+--dump-outputs DIR writes what the last timed step computed (the EM accumulator's parts and the model after the M-step) as
+DIR/<name>.npy in float64; the inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+With --full, the line also carries the headline's untimed oracle check (`parity`), its per-kernel times (`kernels`, measured with HIP
+events inside the timed steps), `roofline`, `step_roofline`, `cpu_baseline`, `screening`, `library`, `summary`, and beside them
+(DESIGN.md section 6 has the table):
   `secondary`   configs[2] AT FULL SIZE: IvExtractor end to end on 10 000 utterances x 3000 frames per GPU -> i-vectors/s, with its own
                 `roofline` (2.67 GFLOP per i-vector), `cpu_baseline` (oracle IvExtractor, 1 and 32 threads), parity, and the opt-in paths
                 (pruned posteriors, single-pass statistics) as A/B legs on a 512-utterance slice (`slice_ab`);
@@ -823,6 +830,21 @@ def tv_iteration_cpu_baseline(ops, R, U_cpu=64, threads=32):
     return parity, cpu
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array (name -> device tensor or host array), float64.  The EM step's outputs are
+    ~4 MB whatever the frame count, so they are written whole."""
+    host = {k: np.asarray(v.cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def em_parity(ctx, g, w, mean, iv, x, acc_last, frames_per_rank, world, nframes=2000):
     """The CHECKER leg of the headline (untimed): (1) the EM statistics of the first `nframes` frames of the timed block under
     the seed model, libgmmiv against the oracle (MixtureStat::computeAndAccumulateEM restated, pinned by KAT-2); (2) a
@@ -1026,7 +1048,14 @@ def main():
                          "exchange of the T-matrix workload with it -- every RCCL call of the step executes on this one GPU")
     ap.add_argument("--share-gpu", action="store_true",
                     help="correctness mode: let the ranks share the visible GPU(s) (rank r on device r %% count) over the C ABI's shm transport")
+    ap.add_argument("--full", action="store_true",
+                    help="EM workload: also run the oracle check, per-kernel times, rooflines, CPU baselines and the other BASELINE configs "
+                         "(off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="EM workload: write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "em":
+        ap.error("--dump-outputs is implemented for the EM workload only")
 
     ndev = torch.cuda.device_count()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1071,7 +1100,10 @@ def main():
     side = torch.cuda.Stream(dev)
     torch.cuda.set_stream(side)
     ctx = capi.Context(local, side.cuda_stream)
-    ctx.set_option("timing", 1)
+    # HIP events around the library's kernels: --full reads them inside every timed EM step (`kernels`, `roofline`), which waits for
+    # the kernels there, so a plain EM run leaves them off; the tv workload records them as it always has
+    if args.full or args.workload == "tv":
+        ctx.set_option("timing", 1)
     if args.wg_waves:
         ctx.set_option("wg_waves", args.wg_waves)
     g = ctx.gmm(w, mean, iv)
@@ -1105,9 +1137,11 @@ def main():
             dist.destroy_process_group()
         return
     x = synth_frames(w, mean, iv, T, dev, seed=1234 + rank)
-    screening = screen_once(ctx, x, "headline frames")      # a check of the data only: the timed calls keep the default "assume_finite" 0
-    screening["assume_finite"] = int(ctx.set_option("assume_finite", 0))
-    traffic = load_traffic()
+    screening = traffic = None
+    if args.full:
+        screening = screen_once(ctx, x, "headline frames")      # a check of the data only: the timed calls keep the default "assume_finite" 0
+        screening["assume_finite"] = int(ctx.set_option("assume_finite", 0))
+        traffic = load_traffic()
     nacc = g.em_acc_len()
     acc = torch.zeros(nacc, dtype=torch.float64, device=dev)
     mean_d = torch.from_numpy(mean).to(dev)
@@ -1124,7 +1158,7 @@ def main():
         nonlocal mean_d, cov_d, nm_d, nc_d
         acc.zero_()
         g.em_accumulate(x, acc=acc)                         # K1 (lse) + K2 (statistics) + reduce
-        if record:
+        if record and args.full:
             for name in KERNEL_FLOP:
                 if ctx.kernel_launches(name) > 0:
                     kern_ms.setdefault(name, []).append((ctx.kernel_ms(name), ctx.kernel_launches(name)))
@@ -1157,12 +1191,17 @@ def main():
     barrier()
     dt_rank = time.perf_counter() - t0
     dt = max_over_ranks(dt_rank, world, dev)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the EM step receives from the last timed step: its all-reduced statistics and the re-estimated model
+        parts = g.split_acc(acc.cpu().numpy())
+        dump_outputs(args.dump_outputs, {"em_occ": parts["occ"], "em_sum_x": parts["sx"], "em_sum_xx": parts["sxx"], "em_llk": parts["llk"],
+                                         "em_frame_count": parts["count"], "weights": w_d, "means": mean_d, "covariances": cov_d})
     multi = None
     if world > 1:      # acc still holds the LAST step's all-reduced accumulator; the M-step outputs are replicated too
         ar_ms = float(np.mean([a.elapsed_time(b) for a, b in ar_events])) if ar_events else None
         multi = multi_rank_report(world, rank, dt_rank, args.steps, {"em_accumulator_after_allreduce": tensor_digest(acc), "weights_after_m_step": tensor_digest(w_d),
                                                                      "means_after_m_step": tensor_digest(mean_d)}, {"allreduce": ar_ms})
-    parity = em_parity(ctx, g, w, mean, iv, x, acc, T, world) if rank == 0 and check else None   # untimed checker leg
+    parity = em_parity(ctx, g, w, mean, iv, x, acc, T, world) if rank == 0 and check and args.full else None   # untimed checker leg
 
     pairs_per_step = float(T) * C * world
     value = pairs_per_step * args.steps / dt / 1e9
@@ -1186,7 +1225,7 @@ def main():
     # the same E-step on a heavily overlapping mixture (means ~ N(0, 0.3^2)): hundreds of Gaussians carry
     # posterior mass per frame, none of the data-dependent skips of K1/K2 can fire -- the dense floor.
     dense = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         wd, md, ivd = make_gmm(C, D, seed=3, spread=0.3)
         Td = min(T, 2_000_000)
         xd = synth_frames(wd, md, ivd, Td, dev, seed=4321 + rank)
@@ -1227,7 +1266,7 @@ def main():
     tv_em = None
     hostl = None
     scoring = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         g.set(w, mean, iv)     # back to the seed model for the i-vector block
         # configs[2] at its stated size (10 000 utterances x 3000 frames per GPU; --iv-utterances for a smaller dry run)
         secondary = ivector_secondary(ctx, g, w, mean, iv, dev, rank, world, U=args.iv_utterances, check=check, traffic=traffic)
@@ -1252,7 +1291,7 @@ def main():
         if world == 1 and check and rank == 0:
             secondary["cpu_baseline"] = ivector_cpu_baseline(w, mean, iv)
             scoring["cpu_baseline"] = scoring_cpu_baseline()
-    if rank == 0:
+    if rank == 0 and args.full:
         if secondary:
             out["secondary"] = secondary
         if computetest:
@@ -1301,6 +1340,7 @@ def main():
         if world == 1 and check:
             out["cpu_baseline"] = cpu_baseline(w, mean, iv, seed=99)
         out["summary"] = summarize(out)     # LAST key: the five BASELINE configs in a few hundred bytes (a truncated tail of the line still shows them)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     g.close()
     ctx.close()

@@ -270,7 +270,7 @@ def test_two_rank_rccl_through_the_c_abi(tmp_path):
 
 
 @pytest.mark.parametrize("extra", [["--workload", "tv", "--tv-utterances", "300", "--steps", "2", "--warmup", "1"],
-                                   ["--frames", "300000", "--steps", "1", "--warmup", "1", "--no-secondary"]])
+                                   ["--frames", "300000", "--steps", "1", "--warmup", "1", "--no-secondary", "--full"]])
 def test_bench_cli_emits_the_contract_line(extra):
     """bench.py as the driver launches it (one rank): one JSON line with the contract's keys, roofline and cpu_baseline objects;
     the T-matrix workload stays finite over consecutive EM iterations."""
@@ -291,3 +291,34 @@ def test_bench_cli_emits_the_contract_line(extra):
     assert d["parity"]["ok"] is True and d["parity"]["max_rel_err"] < d["parity"]["tolerance"] <= 1e-6, d["parity"]   # the oracle check inside the timed number
     if "tv" in extra:
         assert d["finite"] and set(d["phases_ms"]) >= {"tett", "estep", "update_t", "min_divergence"}
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline line and none of --full's blocks; --dump-outputs writes the last timed step's statistics and
+    model as float64 .npy files, and a --full run with the same arguments (same seeded inputs) writes the same arrays."""
+    import json
+    import subprocess
+    args = ["--gpus", "1", "--frames", "300000", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-secondary", "--no-cpu-baseline"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra + ["--dump-outputs", str(tmp_path / mode)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines[mode] = json.loads(js[0])
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    assert not set(d) & {"parity", "kernels", "roofline", "cpu_baseline", "secondary", "summary"}
+    assert {"kernels", "roofline", "summary"} <= set(lines["full"])
+    names = {"em_occ": (2048,), "em_sum_x": (2048, 60), "em_sum_xx": (2048, 60), "em_llk": (), "em_frame_count": (),
+             "weights": (2048,), "means": (2048, 60), "covariances": (2048, 60)}
+    assert sorted(p.name for p in (tmp_path / "plain").iterdir()) == sorted(n + ".npy" for n in names)
+    for n, shape in names.items():
+        a, b = np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))
+        assert a.dtype == np.float64 and a.shape == shape and np.all(np.isfinite(a)), n
+        assert np.allclose(a, b, rtol=1e-9, atol=0), n
+    assert np.load(tmp_path / "plain" / "em_frame_count.npy") == 300000
+    assert abs(np.load(tmp_path / "plain" / "weights.npy").sum() - 1.0) < 1e-9

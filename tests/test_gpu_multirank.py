@@ -374,7 +374,7 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
-@pytest.mark.parametrize("extra", [["--frames", "300000", "--steps", "1", "--warmup", "1", "--no-secondary"],
+@pytest.mark.parametrize("extra", [["--frames", "300000", "--steps", "1", "--warmup", "1", "--no-secondary", "--full"],
                                    ["--workload", "tv", "--tv-utterances", "150", "--steps", "2", "--warmup", "1"]])
 def test_bench_self_launches_its_ranks(extra):
     """`python bench.py --gpus 2 --share-gpu`: bench.py starts two ranks itself (torch.distributed.run), they share GPU 0 over the
@@ -404,7 +404,7 @@ def _check_multi_rank_block(d, world):
     assert "rccl_comm_count" in d["comm"] and d["comm"]["world"] == world
 
 
-@pytest.mark.parametrize("extra", [["--frames", "200000", "--steps", "2", "--warmup", "1", "--no-secondary"],
+@pytest.mark.parametrize("extra", [["--frames", "200000", "--steps", "2", "--warmup", "1", "--no-secondary", "--full"],
                                    ["--workload", "tv", "--tv-utterances", "40", "--steps", "1", "--warmup", "1"]])
 def test_bench_eight_ranks_on_one_gpu_carry_the_multi_rank_report(extra):
     """`python bench.py --gpus 8 --share-gpu`: exactly the code path the driver's 8-GPU run takes (same launcher, same sharding, same

@@ -16,7 +16,7 @@ if [ "$1" = build ]; then
 elif [ "$1" = run ]; then
     mkdir -p $ROOT/gpurun_out
     for v in $VARIANTS; do
-        GMMIV_LIB_PATH=$CS/abl/libgmmiv_$v.so python $ROOT/bench.py --frames ${FRAMES:-4000000} --steps 3 --warmup 1 --no-secondary --no-cpu-baseline 2>/dev/null |
+        GMMIV_LIB_PATH=$CS/abl/libgmmiv_$v.so python $ROOT/bench.py --full --frames ${FRAMES:-4000000} --steps 3 --warmup 1 --no-secondary --no-cpu-baseline 2>/dev/null |
             python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); k=d['kernels']; print('K1_ABL=%-3s k_llk_mfma %.3f ms/launch (%.1f Gpair/s, frac %.3f)   k_stats_z %.3f ms' % ('$v', k['k_llk_mfma']['ms_per_launch'], k['k_llk_mfma']['gpairs_per_s'], k['k_llk_mfma']['tflops'] / 78.6, k['k_stats_z']['ms_per_launch']))"
     done | tee $ROOT/gpurun_out/k1_ablate.txt
 fi

@@ -6,7 +6,7 @@ run() { # run <tag> <cmd...>
   ( cd $ROOT && timeout 900 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -d /tmp/g_$tag -o t -- "$@" > /tmp/g_$tag.log 2>&1 )
   python $ROOT/tools/rocpd_summary.py "$(find /tmp/g_$tag -name '*.db' | head -1)" --pmc > $ROOT/gpurun_out/grbm_$tag.txt 2>&1
 }
-run em python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
+run em python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary
 run iv python tools/pmc_blocks.py iv 2560 2
 run tv python bench.py --workload tv --steps 2 --warmup 1 --no-cpu-baseline --tv-utterances 2048
 run score python tools/pmc_blocks.py score 100000 2

@@ -9,7 +9,7 @@ TAG=${1:-run}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+BENCH="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 db() { find "$1" -name '*.db' | head -1; }
 timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o bench -- $BENCH > "$OUT/kt.log" 2>&1
 python "$ROOT/tools/rocpd_summary.py" "$(db "$OUT/kt")" > "$OUT/bench_em_kernel_stats.txt" 2>&1

@@ -22,7 +22,7 @@ pmc() { # pmc <tag> <counters...> -- <cmd...>
   python "$ROOT/tools/rocpd_summary.py" "$(db "$OUT/pmc_$tag")" --pmc > "$OUT/${tag}.txt" 2>&1
   rm -rf "$OUT/pmc_$tag"
 }
-BENCH="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+BENCH="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 kt bench_em $BENCH
 grep -h '^{"metric"' "$OUT/bench_em.log" > "$OUT/bench_em_under_rocprof.json"
 pmc bench_em_pmc_fetch_size FETCH_SIZE -- $BENCH

@@ -23,9 +23,9 @@ pmc() { # pmc <tag> <counters...> -- <cmd...>
   rm -rf "$OUT/pmc_$tag"
 }
 # 1. the driver's own command (default flags), plain: the line BENCH_r03 should reproduce
-( cd $ROOT && timeout 900 python bench.py 2> "$OUT/bench_n1.err" | grep '^{"metric"' > "$OUT/bench_n1.json" )
+( cd $ROOT && timeout 900 python bench.py --full 2> "$OUT/bench_n1.err" | grep '^{"metric"' > "$OUT/bench_n1.json" )
 # 2. the same EM workload under the kernel trace and the three PMC passes
-BENCH="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+BENCH="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 kt bench_em $BENCH
 grep -h '^{"metric"' "$OUT/bench_em.log" > "$OUT/bench_em_under_rocprof.json"
 pmc bench_em_pmc_fetch_size FETCH_SIZE -- $BENCH
@@ -39,7 +39,7 @@ pmc bench_tv_pmc_fetch_size FETCH_SIZE -- $TV
 # 4. the multi-rank orchestration on this one GPU (ranks share it over the C ABI's shm transport): a correctness record, not a scaling number
 ( cd $ROOT && timeout 900 python bench.py --gpus 2 --share-gpu --workload tv --tv-utterances 1024 --steps 2 --warmup 1 2> "$OUT/bench_tv_2ranks_shared.err" | grep '^{"metric"' > "$OUT/bench_tv_2ranks_shared_gpu.json" )
 ( cd $ROOT && timeout 900 python bench.py --gpus 2 --share-gpu --workload tv --tv-utterances 1024 --steps 2 --warmup 1 --overlap 1 2>> "$OUT/bench_tv_2ranks_shared.err" | grep '^{"metric"' > "$OUT/bench_tv_2ranks_shared_gpu_overlap.json" )
-( cd $ROOT && timeout 900 python bench.py --gpus 2 --share-gpu --frames 2000000 --steps 2 --warmup 1 --no-secondary 2> "$OUT/bench_em_2ranks_shared.err" | grep '^{"metric"' > "$OUT/bench_em_2ranks_shared_gpu.json" )
+( cd $ROOT && timeout 900 python bench.py --full --gpus 2 --share-gpu --frames 2000000 --steps 2 --warmup 1 --no-secondary 2> "$OUT/bench_em_2ranks_shared.err" | grep '^{"metric"' > "$OUT/bench_em_2ranks_shared_gpu.json" )
 # 5. the Cholesky family on its own (tools/chol_probe.hip), with the in-kernel phase stamps of one uncontended workgroup
 ( cd $ROOT && for nb in 32 256 1024; do tools/bin/chol_probe 400 $nb 5; done > "$OUT/chol_probe.txt" 2>&1; tools/bin/chol_probe_prof 400 32 2 >> "$OUT/chol_probe.txt" 2>&1 )
 # 6. ComputeTest world pass

@@ -25,12 +25,12 @@ pmc() { # pmc <tag> <counters...> -- <cmd...>
   rm -rf "$OUT/pmc_$tag"
 }
 # 1. the driver's own command, plain: the line BENCH_r06 should reproduce
-( cd $ROOT && timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 2> "$OUT/bench_n1.err" | grep '^{"metric"' > "$OUT/bench_n1.json" )
+( cd $ROOT && timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 2> "$OUT/bench_n1.err" | grep '^{"metric"' > "$OUT/bench_n1.json" )
 # 2. the whole default line under the kernel trace (every block's kernels: EM, IvExtractor at 10 k x 3 k, ComputeTest, host layer, T-matrix EM, scoring)
-kt bench_all python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+kt bench_all python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 grep -h '^{"metric"' "$OUT/bench_all.log" > "$OUT/bench_all_under_rocprof.json"
 # 3. the EM headline alone: kernel trace + the PMC passes (HBM bytes; instruction mix)
-BENCH="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
+BENCH="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary"
 kt bench_em $BENCH
 grep -h '^{"metric"' "$OUT/bench_em.log" > "$OUT/bench_em_under_rocprof.json"
 pmc bench_em_pmc_fetch_size FETCH_SIZE -- $BENCH

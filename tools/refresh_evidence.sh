@@ -7,7 +7,7 @@ R=${1:-r02}
 OUT=$ROOT/gpurun_out/evidence_$R
 mkdir -p "$OUT"; cd "$ROOT"
 j() { grep -h '^{' | tail -1; }
-timeout 900 python bench.py --steps 10 --warmup 3 2> "$OUT/bench_n1.err" | j > "$OUT/bench_n1.json"
+timeout 900 python bench.py --full --steps 10 --warmup 3 2> "$OUT/bench_n1.err" | j > "$OUT/bench_n1.json"
 timeout 900 python bench.py --workload tv --steps 4 --warmup 1 2> "$OUT/bench_tv.err" | j > "$OUT/bench_workload_tv_n1.json"
 timeout 900 python tools/bench_tv.py > "$OUT/bench_tv_tool.json" 2> "$OUT/bench_tv_tool.err"
 timeout 900 python tools/host_tv_time.py > "$OUT/host_layer_tv_time.json" 2> "$OUT/host_tv.err"
