@@ -305,6 +305,11 @@ __device__ __forceinline__ int xswz(int t) { return ((t << 1) ^ ((t & 1) << 4)) 
 // "lane base + compile-time immediate" and costs no VALU address arithmetic.
 __device__ __forceinline__ int xrot(int t) { return ((t & 1) << 4) + (((t >> 1) & 7) << 1); }
 
+// Slot of frame t (counted from a 16-frame block boundary) in the running-exponent array eit of k_llk_mfma (WZ): inside each
+// 16-frame block the frames are stored transposed 4 x 4, frame 4 r + q at slot 4 q + r, so that the lane holding frames q, q + 4,
+// q + 8, q + 12 of a block (register r = frame 4 r + q of the MFMA layout) writes them as ONE 16-byte word.
+__device__ __forceinline__ int eit_slot(int t) { return (t & ~15) | ((t & 3) << 2) | ((t >> 2) & 3); }
+
 // floor(e / D) for e < 2^16 by reciprocal multiplication: magic = 2^32 / D + 1 (host side: gmmiv_div_magic).  vectSize 1 has no
 // 32-bit magic (2^32 + 1 wraps to 1 and every quotient came out 0 -- the statistics of a ONE-dimensional model were garbage until
 // round 6; tests/golden's EnergyDetector case, C = 2, D = 1, found it): magic 0 stands for "divide by one".

@@ -94,7 +94,7 @@ __global__ void k_gmm_transpose(int C, int Cp, int D, const double *__restrict__
 // WZ: also leave every SCALED LIKELIHOOD e[t][c] = exp(z[t][c]) * 2^-E in zbuf for the statistics
 // kernel that follows (stats_z.hip) -- the log-sum-exp needs these exponentials anyway, so the
 // statistics kernel gets its posteriors with one multiply: gamma = e * 2^(E - Efin) / S_t.  E is the
-// running binary exponent of the frame's row at that tile pair (eit[tile pair][frame]); Efin and
+// running binary exponent of the frame's row at that tile pair (eit[tile pair][eit_slot(frame)]); Efin and
 // 1 / S_t (the sum is S_t 2^Efin) are written per frame at the end.  zbuf keeps the register layout
 // of the MFMA result = A-operand layout of the statistics MFMA: 2 KB blocks
 // [Gaussian tile ct][16-frame block fb][lane][4 rows], so both sides move 32 contiguous bytes per lane.
@@ -437,11 +437,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict_
 #pragma unroll
                 for (int h = 0; h < 2; ++h) __builtin_nontemporal_store(acc[g][h], (d4 *)(zw + ((size_t)g * nfb + h) * 256)); // streamed: keep the model tiles in L2
             if (i16 == 0 && !(K1_ABL & 32)) {
-                int *ew = eit + (size_t)te * (nfb * 16) + tb + q;
+                // frames 4 r + q of block h: slots 4 q + r (eit_slot), one 16-byte store per block
+                typedef int i4 __attribute__((ext_vector_type(4)));
+                int *ew = eit + (size_t)te * (nfb * 16) + tb + 4 * q;
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ew[h * 16 + 4 * r] = E[h][r];
+                for (int h = 0; h < 2; ++h) *(i4 *)(ew + h * 16) = (i4){E[h][0], E[h][1], E[h][2], E[h][3]};
             }
             return;
         }

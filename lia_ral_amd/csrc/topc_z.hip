@@ -61,9 +61,9 @@ __global__ __launch_bounds__(256, 2) void k_topc_from_z(const void *__restrict__
         for (int mm = 0; mm < 16; ++mm) {
             const int ct = 4 * (16 * h + mm) + qq, cc = ct < nct ? ct : nct - 1;
             e2[mm] = *(const d2 *)(zbuf + (((size_t)cc * nfb + fb) * 64 + 16 * q0 + i16) * 4 + 2 * half);
-            const int *ep = eit + (size_t)(cc >> 1) * (nfb * 16) + fb * 16 + q0 + 8 * half;
+            const int *ep = eit + (size_t)(cc >> 1) * (nfb * 16) + fb * 16 + eit_slot(q0 + 8 * half); // frames q0 + 8 half + {0, 4}
             e0[mm] = ep[0];
-            e1[mm] = ep[4];
+            e1[mm] = ep[1];
         }
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -975,11 +975,11 @@ __global__ __launch_bounds__(256) void k_post_from_z(long n, int C, int nct, con
         const d2 *pz = (const d2 *)(zbuf + (((size_t)ct * nfb + fb) * 64 + lane) * 4);
         const d2 a = __builtin_nontemporal_load(pz), b = __builtin_nontemporal_load(pz + 1);
         const double e[4] = {a[0], a[1], b[0], b[1]};
-        const int *ep = eit + (size_t)(ct >> 1) * (nfb * 16) + fb * 16 + q;
+        const int *ep = eit + (size_t)(ct >> 1) * (nfb * 16) + fb * 16 + eit_slot(q); // frame q + 4 r at slot 4 q + r
         const int c = 16 * ct + i16;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            if (tr[r] < n && c < C) gamma[(size_t)tr[r] * C + c] = __builtin_ldexp(e[r] * fs[r], ep[4 * r] - ef[r]);
+            if (tr[r] < n && c < C) gamma[(size_t)tr[r] * C + c] = __builtin_ldexp(e[r] * fs[r], ep[r] - ef[r]);
     }
 }
 
