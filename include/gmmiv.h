@@ -457,6 +457,49 @@ int gmmiv_score_apply_trials(gmmiv_ctx *ctx, int64_t M, int64_t S, const unsigne
  * (PldaTools.cpp:4175-4183 dispatch, AccumulateTVStat.cpp:498-507). */
 void gmmiv_shard_range(int64_t n, int rank, int world, int64_t *begin, int64_t *end);
 
+/* ---- score normalisation: LIA_SpkDet/ComputeNorm (z / t / zt / tz-norm) on resident score matrices ---------------------
+ * gmmiv_score_cohort_stats: DistribNorm::computeMeanStd (ComputeNorm.cpp:121-159) over every distribution of a cohort score
+ * matrix scores[rows x cols] (row stride ld >= cols).
+ *   axis 0: one distribution per ROW (its cols scores; z-norm: a model against the impostor segments) -> mean[rows], std[rows];
+ *   axis 1: one distribution per COLUMN (its rows scores; t-norm: the cohort models against a segment) -> mean[cols], std[cols].
+ *   select:   NULL, or bytes along the cohort axis (cols of them for axis 0, rows for axis 1): a score enters its distribution
+ *             only where the byte is non-zero (selectImp, :436-445); n = the number of non-zero bytes.
+ *   pre_mean, pre_std: NULL, or vectors along the cohort axis: the statistics are those of (x - pre_mean[j]) / pre_std[j],
+ *             computed on the fly with exactly these two operations (getAllScoresFirstNormed, :466-489) -- the zt / tz chains
+ *             never materialise a normalised copy of their cohort matrix.
+ *   mean_mode 0: mean = sum / size, std = sqrt(sum2 / size - mean * mean) (biased, not clamped: a negative radicand gives NaN, a
+ *             constant cohort gives 0 and the later division Inf / NaN, as in the reference);
+ *   mean_mode 1: mean = the score at position size / 2 of the kept range, std = the mean absolute deviation from it.
+ *   percent_h, percent_l in [0, 1): discardH = (unsigned long)((double)n * percent_h) highest and discardL lowest scores are left
+ *             out (fp64 product, truncated); size = n - discardH - discardL.  The result is what the reference gets from a
+ *             descending sort, ties included; no sort runs (an exact radix select per distribution, score_norm.hip).
+ *   Quirk kept from the reference: with mean_mode 1 and BOTH percentages zero it does not sort, and its "median" is the score
+ *   at position n / 2 in INPUT order.
+ *   An empty kept range (n == 0 or discardH + discardL >= n) is GMMIV_ERR_ARG, checked before anything is enqueued.  The one
+ *   exception: a `select` that is a DEVICE pointer is counted on the device (same fp64 product and truncation), nothing is read
+ *   back, and an empty kept range then yields NaN in mean and std.
+ *   Summation order differs from the reference's sequential loop (fixed, so results are bitwise reproducible): sums agree
+ *   within (n - 1) 2^-53 sum|x|, and exactly whenever every partial sum is exact.  NaN scores are outside the contract.
+ *   Device scratch: at most GMMIV_SCORE_NORM_SCRATCH_BYTES(ndist) = 512 * ndist + 64 bytes (+ the workspace's growth slack of 1/8),
+ *   whatever the matrix: 64 bytes for the counts of a device mask, 512 per distribution for the row-slab sums of the untrimmed
+ *   column pass (axis 1, mean_mode 0, no discard); the select histograms live in LDS.  Host arrays are staged like everywhere else.
+ * gmmiv_score_normalize: scores[M x S] in place, every step the two IEEE operations (x - mean) / std (a true division):
+ *   GMMIV_NORM_Z   (x - row_mean[m]) / row_std[m]                     GMMIV_NORM_T   (x - col_mean[s]) / col_std[s]
+ *   GMMIV_NORM_ZT  t first, then z (:596-666)                          GMMIV_NORM_TZ  z first, then t (:668-751)
+ *   first_out: NULL, or [M x S] that receives the score after the FIRST of the two normalisations (the reference writes both).
+ * Kernel timers (gmmiv_ctx_kernel_ms, option "timing"): "k_norm_stats" and "k_norm_apply".
+ * With device pointers throughout both calls only enqueue.  rows == 0 / cols == 0 / M == 0 / S == 0: nothing to do, GMMIV_OK. */
+#define GMMIV_SCORE_NORM_SCRATCH_BYTES(ndist) ((size_t)512 * (size_t)(ndist) + (size_t)64)
+enum { GMMIV_NORM_Z = 0, GMMIV_NORM_T = 1, GMMIV_NORM_ZT = 2, GMMIV_NORM_TZ = 3 };
+int gmmiv_score_cohort_stats(gmmiv_ctx *ctx, int64_t rows, int64_t cols, const double *scores, int64_t ld, int axis,
+                             const unsigned char *select, const double *pre_mean, const double *pre_std, int mean_mode,
+                             double percent_h, double percent_l, double *mean, double *std);
+int gmmiv_score_normalize(gmmiv_ctx *ctx, int64_t M, int64_t S, double *scores, int order, const double *row_mean,
+                          const double *row_std, const double *col_mean, const double *col_std, double *first_out);
+/* Bytes the context holds in the scratch slot of the score-normalisation calls (slot < 0), or in workspace slot `slot`
+ * (0 when out of range): lets a caller check that a repeated call allocates nothing. */
+size_t gmmiv_ctx_workspace_bytes(gmmiv_ctx *ctx, int slot);
+
 /* ---- JFA (LIA_SpkTools/src/AccumulateJFAStat.cpp): model M_{s,h} = m + V y_s + U x_h + D z_s ---------------------------
  * The factor steps are the total-variability entry points under the JFA names:
  *   JFAAcc::estimateVEVT / estimateUEUT (:1266-1352, :1425-1508)                         -> gmmiv_tv_tett

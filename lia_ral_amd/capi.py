@@ -493,6 +493,56 @@ class Context:
                                   ns.ctypes.data_as(ct.c_void_p), _ptr(segs), _ptr(FTJF), _ptr(out)))
         return out
 
+    # ---- score normalisation (LIA_SpkDet/ComputeNorm): cohort statistics + the (x - mean) / std passes
+    def score_cohort_stats(self, scores, axis, select=None, pre_mean=None, pre_std=None, mean_mode=0, percent_h=0.0,
+                           percent_l=0.0, out_mean=None, out_std=None):
+        """mean, std of every row (axis 0) or column (axis 1) of scores[rows, cols] the way DistribNorm::computeMeanStd
+        computes them.  scores may be a row-strided view (stride(1) == 1).  select: bytes along the cohort axis."""
+        rows, cols = scores.shape
+        if _is_torch(scores):
+            assert scores.dim() == 2 and (cols <= 1 or scores.stride(1) == 1)
+            ld = scores.stride(0) if rows > 1 else cols
+        else:
+            scores = np.ascontiguousarray(scores, dtype=np.float64)
+            ld = cols
+        nd = rows if axis == 0 else cols
+        if out_mean is None:
+            out_mean = np.empty(nd)
+        if out_std is None:
+            out_std = np.empty(nd)
+        sel = select if select is None or _is_torch(select) else np.ascontiguousarray(select, np.uint8)
+        _chk(lib.gmmiv_score_cohort_stats(self._h, ct.c_int64(rows), ct.c_int64(cols), ct.c_void_p(_data_ptr(scores)),
+                                          ct.c_int64(max(ld, cols)), int(axis), _ptr(sel), _ptr(_f64(pre_mean)),
+                                          _ptr(_f64(pre_std)), int(mean_mode), ct.c_double(percent_h), ct.c_double(percent_l),
+                                          _ptr(out_mean), _ptr(out_std)))
+        return out_mean, out_std
+
+    def score_normalize(self, scores, order, row_mean=None, row_std=None, col_mean=None, col_std=None, first_out=None):
+        """scores[M, S] in place; order NORM_Z / NORM_T / NORM_ZT (t first) / NORM_TZ (z first).  first_out: None, or an
+        [M, S] array that receives the score after the first of two normalisations."""
+        M, S = scores.shape
+        _chk(lib.gmmiv_score_normalize(self._h, ct.c_int64(M), ct.c_int64(S), _ptr(scores), int(order), _ptr(_f64(row_mean)),
+                                       _ptr(_f64(row_std)), _ptr(_f64(col_mean)), _ptr(_f64(col_std)), _ptr(first_out)))
+        return scores
+
+    def workspace_bytes(self, slot=-1):
+        """Bytes held in the score-normalisation scratch slot (slot < 0) or in workspace slot `slot`."""
+        return int(lib.gmmiv_ctx_workspace_bytes(self._h, int(slot)))
+
+
+NORM_Z, NORM_T, NORM_ZT, NORM_TZ = 0, 1, 2, 3
+
+
+def norm_scratch_bytes(ndist):
+    """GMMIV_SCORE_NORM_SCRATCH_BYTES(ndist): the most device scratch the score-normalisation calls take"""
+    return 512 * int(ndist) + 64
+lib.gmmiv_ctx_workspace_bytes.restype = ct.c_size_t
+lib.gmmiv_ctx_workspace_bytes.argtypes = [ct.c_void_p, ct.c_int]
+
+
+def _data_ptr(a):
+    return a.data_ptr() if _is_torch(a) else a.ctypes.data
+
 
 COMM_ID_BYTES = 128
 _HOOK_T = ct.CFUNCTYPE(None, ct.c_void_p)

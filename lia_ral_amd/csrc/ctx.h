@@ -34,8 +34,8 @@ void gmmiv_set_error(const char *fmt, ...);
 
 enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T6, WS_T7, WS_T8,
        WS_T9, WS_TIV, WS_LP, WS_AUX, WS_SLAB, WS_SLOTS, WS_FLAGS, WS_Z, WS_EIT, WS_INV,
-       WS_GFLAG,
-       WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass
+       WS_GFLAG, WS_NORM,
+       WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask
 
 struct gmmiv_ctx {
     int device = 0;

@@ -1097,4 +1097,63 @@ int liagpu_label_segments(const char *lbl_path, const char *label, double frameL
     })
 }
 
+// ComputeNorm on resident matrices (liagpu::computeNorm).  normType: 0 znorm, 1 tnorm, 2 ztnorm, 3 tznorm.  Every array may be a
+// host or a device pointer; imp_models [Nt] / imp_segs [Nz]: host bytes or NULL.  Returns when the results are complete.
+int liagpu_compute_norm(int device, int normType, int meanMode, double percentH, double percentL, long M, long S, long Nt, long Nz,
+                        double *X, const double *Z, const double *T, const double *ZT, const unsigned char *imp_models,
+                        const unsigned char *imp_segs, double *first_out)
+{
+    GUARD({
+        static const char *names[] = {"znorm", "tnorm", "ztnorm", "tznorm"};
+        ComputeNormCfg cfg;
+        cfg.normType = normType >= 0 && normType <= 3 ? names[normType] : "?";
+        cfg.meanMode = meanMode; cfg.percentH = percentH; cfg.percentL = percentL;
+        if (imp_models) cfg.impModels.assign(imp_models, imp_models + Nt);
+        if (imp_segs) cfg.impSegs.assign(imp_segs, imp_segs + Nz);
+        GpuServer srv(device);
+        computeNorm(srv, cfg, (unsigned long)M, (unsigned long)S, (unsigned long)Nt, (unsigned long)Nz, X, Z, T, ZT, first_out);
+        srv.sync();
+    })
+}
+
+// ComputeNorm on files (liagpu::computeNormFiles).  fields: fieldGender, fieldName, fieldDecision, fieldSeg, fieldLLR.  The lists
+// are read and checked BEFORE a device is opened: a list that is not a full cross product fails without one.
+int liagpu_compute_norm_files(int device, const char *normType, int meanMode, double percentH, double percentL, const char *testNistFile,
+                              const char *znormNistFile, const char *tnormNistFile, const char *ztnormNistFile, const char *impostorIDList,
+                              const char *outputFileBaseName, const int *fields)
+{
+    GUARD({
+        ComputeNormFilesCfg cfg;
+        cfg.norm.normType = normType; cfg.norm.meanMode = meanMode; cfg.norm.percentH = percentH; cfg.norm.percentL = percentL;
+        cfg.testNistFile = testNistFile; cfg.znormNistFile = znormNistFile ? znormNistFile : "";
+        cfg.tnormNistFile = tnormNistFile ? tnormNistFile : ""; cfg.ztnormNistFile = ztnormNistFile ? ztnormNistFile : "";
+        cfg.impostorIDList = impostorIDList ? impostorIDList : ""; cfg.outputFileBaseName = outputFileBaseName;
+        if (fields) { cfg.fields.fieldGender = fields[0]; cfg.fields.fieldName = fields[1]; cfg.fields.fieldDecision = fields[2];
+                      cfg.fields.fieldSeg = fields[3]; cfg.fields.fieldLLR = fields[4]; }
+        ComputeNormTables t = loadComputeNormTables(cfg);
+        GpuServer srv(device);
+        computeNormFiles(srv, cfg, t);
+    })
+}
+
+// resultLine / parseResultLine round trip for the tests: writes the line into `line` (cap bytes) and parses `parse_in` (or the
+// line just written when NULL) with the given field positions into name / seg / gender (each cap bytes), decision and llr.
+int liagpu_result_line(double llr, const char *client, const char *test, const char *gender, double threshold, int withTimes, double start,
+                       double end, const char *parse_in, const int *fields, char *line, char *name, char *seg, char *gender_out, long cap,
+                       int *decision, double *llr_out)
+{
+    GUARD({
+        const std::string l = resultLine(llr, client, test, gender, threshold, withTimes != 0, start, end);
+        ResultFields f;
+        if (fields) { f.fieldGender = fields[0]; f.fieldName = fields[1]; f.fieldDecision = fields[2]; f.fieldSeg = fields[3]; f.fieldLLR = fields[4]; }
+        const ResultLine r = parseResultLine(parse_in ? std::string(parse_in) : l, f);
+        auto put = [&](char *dst, const std::string &v) {
+            if ((long)v.size() + 1 > cap) throw Exception("result line buffer too small");
+            memcpy(dst, v.c_str(), v.size() + 1);
+        };
+        put(line, l); put(name, r.name); put(seg, r.seg); put(gender_out, r.gender);
+        *decision = r.decision; *llr_out = r.llr;
+    })
+}
+
 } // extern "C"

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <fstream>
+#include <map>
 #include <sstream>
 
 namespace liagpu {
@@ -353,6 +354,139 @@ std::string resultLine(double llr, const std::string &clientName, const std::str
     if (withTimes) o << start << " " << end << " ";
     o << llr;
     return o.str();
+}
+
+// ---- NIST result lines in, ComputeNorm on files -----------------------------------------------------------------------------
+ResultLine parseResultLine(const std::string &line, const ResultFields &f)
+{
+    std::vector<std::string> tok;
+    std::istringstream in(line);
+    for (std::string t; in >> t;) tok.push_back(t);
+    auto at = [&](int i, const char *what) -> const std::string & {
+        if (i < 0 || (size_t)i >= tok.size()) throw Exception(std::string("result line [") + line + "] has no field " + std::to_string(i) + " (" + what + ")");
+        return tok[(size_t)i];
+    };
+    ResultLine r;
+    r.gender = at(f.fieldGender, "fieldGender");
+    r.name = at(f.fieldName, "fieldName");
+    r.seg = at(f.fieldSeg, "fieldSeg");
+    if (f.fieldDecision >= 0 && (size_t)f.fieldDecision < tok.size()) r.decision = atoi(tok[(size_t)f.fieldDecision].c_str());
+    const std::string &v = at(f.fieldLLR, "fieldLLR");
+    char *end = nullptr;
+    r.llr = strtod(v.c_str(), &end);
+    if (end == v.c_str()) throw Exception("result line [" + line + "]: field " + std::to_string(f.fieldLLR) + " is not a score");
+    return r;
+}
+
+std::vector<ResultLine> readResultFile(const std::string &path, const ResultFields &f)
+{
+    std::ifstream in(path.c_str());
+    if (!in) throw Exception("cannot read [" + path + "]");
+    std::vector<ResultLine> out;
+    for (std::string line; std::getline(in, line);) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        out.push_back(parseResultLine(line, f));
+    }
+    return out;
+}
+
+namespace {
+unsigned long indexOf(std::vector<std::string> &names, std::map<std::string, unsigned long> &idx, const std::string &n, bool grow,
+                      const std::string &path, const char *what)
+{
+    auto it = idx.find(n);
+    if (it != idx.end()) return it->second;
+    if (!grow) throw Exception("[" + path + "]: " + what + " [" + n + "] does not occur in the other lists: not a full cross product");
+    idx[n] = names.size();
+    names.push_back(n);
+    return names.size() - 1;
+}
+// rows / cols: the names seen so far (fixed == true: the list must use exactly these); -> dense [rows x cols]
+std::vector<double> denseFromLines(const std::vector<ResultLine> &lines, const std::string &path, std::vector<std::string> &rows,
+                                   bool rowsFixed, std::vector<std::string> &cols, bool colsFixed, std::vector<unsigned long> *lineRow,
+                                   std::vector<unsigned long> *lineCol)
+{
+    std::map<std::string, unsigned long> ri, ci;
+    for (size_t i = 0; i < rows.size(); ++i) ri[rows[i]] = i;
+    for (size_t i = 0; i < cols.size(); ++i) ci[cols[i]] = i;
+    std::vector<unsigned long> lr(lines.size()), lc(lines.size());
+    for (size_t l = 0; l < lines.size(); ++l) {
+        lr[l] = indexOf(rows, ri, lines[l].name, !rowsFixed, path, "model");
+        lc[l] = indexOf(cols, ci, lines[l].seg, !colsFixed, path, "segment");
+    }
+    const size_t R = rows.size(), C = cols.size();
+    if (lines.size() != R * C)
+        throw Exception("[" + path + "]: " + std::to_string(lines.size()) + " lines for " + std::to_string(R) + " models x " + std::to_string(C) +
+                        " segments: not a full cross product (ragged cohorts are not supported)");
+    std::vector<double> out(R * C);
+    std::vector<bool> seen(R * C, false);
+    for (size_t l = 0; l < lines.size(); ++l) {
+        const size_t k = lr[l] * C + lc[l];
+        if (seen[k]) throw Exception("[" + path + "]: model [" + lines[l].name + "] meets segment [" + lines[l].seg + "] twice: not a full cross product");
+        seen[k] = true;
+        out[k] = lines[l].llr;
+    }
+    if (lineRow) *lineRow = lr;
+    if (lineCol) *lineCol = lc;
+    return out;
+}
+} // namespace
+
+ComputeNormTables loadComputeNormTables(const ComputeNormFilesCfg &cfg)
+{
+    ComputeNormTables t;
+    t.norm = cfg.norm;
+    const std::string &nt = cfg.norm.normType;
+    const bool zn = nt == "znorm", tn = nt == "tnorm", two = nt == "ztnorm" || nt == "tznorm";
+    if (!zn && !tn && !two) throw Exception("unknown normalization mode:" + nt);
+    t.test = readResultFile(cfg.testNistFile, cfg.fields);
+    t.X = denseFromLines(t.test, cfg.testNistFile, t.models, false, t.segs, false, &t.lineRow, &t.lineCol);
+    if (zn || two) t.Z = denseFromLines(readResultFile(cfg.znormNistFile, cfg.fields), cfg.znormNistFile, t.models, true, t.impSegs, false, nullptr, nullptr);
+    if (tn || two) t.T = denseFromLines(readResultFile(cfg.tnormNistFile, cfg.fields), cfg.tnormNistFile, t.cohortModels, false, t.segs, true, nullptr, nullptr);
+    if (two) t.ZT = denseFromLines(readResultFile(cfg.ztnormNistFile, cfg.fields), cfg.ztnormNistFile, t.cohortModels, true, t.impSegs, true, nullptr, nullptr);
+    if (!cfg.impostorIDList.empty()) { // selectMode 1 (:511-514): a cohort-side name enters only if the list has it
+        std::ifstream in(cfg.impostorIDList.c_str());
+        if (!in) throw Exception("cannot read [" + cfg.impostorIDList + "]");
+        std::map<std::string, int> ids;
+        for (std::string w; in >> w;) ids[w] = 1;
+        t.norm.impModels.assign(t.cohortModels.size(), 0);
+        t.norm.impSegs.assign(t.impSegs.size(), 0);
+        for (size_t i = 0; i < t.cohortModels.size(); ++i) t.norm.impModels[i] = ids.count(t.cohortModels[i]) ? 1 : 0;
+        for (size_t i = 0; i < t.impSegs.size(); ++i) t.norm.impSegs[i] = ids.count(t.impSegs[i]) ? 1 : 0;
+    }
+    return t;
+}
+
+void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormTables &t)
+{
+    const std::string &nt = t.norm.normType;
+    const bool two = nt == "ztnorm" || nt == "tznorm";
+    std::vector<double> first(two ? t.X.size() : 0);
+    computeNorm(srv, t.norm, t.models.size(), t.segs.size(), t.cohortModels.size(), t.impSegs.size(), t.X.data(),
+                t.Z.empty() ? nullptr : t.Z.data(), t.T.empty() ? nullptr : t.T.data(), t.ZT.empty() ? nullptr : t.ZT.data(),
+                two ? first.data() : nullptr);
+    srv.sync();
+    auto write = [&](const std::string &ext, const std::vector<double> &v) {
+        const std::string path = cfg.outputFileBaseName + ext;
+        std::ofstream out(path.c_str(), std::ios::out | std::ios::trunc);
+        if (!out) throw Exception("cannot write [" + path + "]");
+        out.precision(17);
+        const size_t S = t.segs.size();
+        for (size_t l = 0; l < t.test.size(); ++l) { // decision 0 like the reference (:497)
+            const double sc = v[t.lineRow[l] * S + t.lineCol[l]];
+            out << t.test[l].gender << " " << t.test[l].name << " 0 " << t.test[l].seg << " " << sc << "\n";
+        }
+    };
+    if (nt == "znorm") write(cfg.znormFilesExtension, t.X);
+    else if (nt == "tnorm") write(cfg.tnormFilesExtension, t.X);
+    else if (nt == "ztnorm") { write(cfg.ztnormFilesExtension, t.X); write(cfg.tnormFilesExtension, first); }   // :656-657
+    else { write(cfg.tznormFilesExtension, t.X); write(cfg.znormFilesExtension, first); }                        // :738-739
+}
+
+void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg)
+{
+    ComputeNormTables t = loadComputeNormTables(cfg);
+    computeNormFiles(srv, cfg, t);
 }
 
 } // namespace liagpu

@@ -70,4 +70,35 @@ std::vector<double> loadVectorsById(const std::string &dir, const std::vector<st
 std::string resultLine(double llr, const std::string &clientName, const std::string &testName, const std::string &gender,
                        double threshold, bool withTimes = false, double start = 0.0, double end = 0.0);
 
+// A NIST-style result line as the tools write it (resultLine above; outputResultLine of the reference): five fields separated
+// by blanks, their POSITIONS configurable like the reference's fieldGender / fieldName / fieldDecision / fieldSeg / fieldLLR
+// (ComputeNorm.cpp:520-524; a line written with start / end times has its score at position 6).
+struct ResultFields { int fieldGender = 0, fieldName = 1, fieldDecision = 2, fieldSeg = 3, fieldLLR = 4; };
+struct ResultLine { std::string gender, name, seg; int decision = 0; double llr = 0.0; };
+ResultLine parseResultLine(const std::string &line, const ResultFields &f = ResultFields());   // throws on a missing field
+std::vector<ResultLine> readResultFile(const std::string &path, const ResultFields &f = ResultFields()); // empty lines skipped
+
+// ComputeNorm driven by files (ComputeNorm.cpp:491-760).  The lists must be FULL CROSS PRODUCTS -- every model of the test list
+// against every test segment, every entity against the same cohort: that is what makes them dense matrices.  A ragged list (an
+// entity whose cohort differs from the others') is refused with a message; the reference's per-name DistribNorm would accept it.
+struct ComputeNormFilesCfg {
+    ComputeNormCfg norm;                 // normType, meanMode, percentH, percentL (the masks are built from impostorIDList)
+    std::string testNistFile, znormNistFile, tnormNistFile, ztnormNistFile, impostorIDList; // impostorIDList "": no selection
+    std::string outputFileBaseName;
+    std::string znormFilesExtension = ".znorm", tnormFilesExtension = ".tnorm", ztnormFilesExtension = ".ztnorm",
+                tznormFilesExtension = ".tznorm";
+    ResultFields fields;
+};
+struct ComputeNormTables {               // the lists as dense matrices, in order of first appearance
+    std::vector<ResultLine> test;        // the test list, line by line (output order)
+    std::vector<std::string> models, segs, cohortModels, impSegs;
+    std::vector<double> X, Z, T, ZT;     // [models x segs], [models x impSegs], [cohortModels x segs], [cohortModels x impSegs]
+    std::vector<unsigned long> lineRow, lineCol; // cell of X of each test line
+    ComputeNormCfg norm;                 // cfg.norm with impModels / impSegs filled from impostorIDList
+};
+ComputeNormTables loadComputeNormTables(const ComputeNormFilesCfg &cfg);                 // host only
+void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormTables &tables); // normalise + write the output files
+void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg);
+
+
 } // namespace liagpu

@@ -2342,4 +2342,55 @@ void computeEigenProblem(const std::vector<double> &EP, unsigned long n, std::ve
     }
 }
 
+// ---- ComputeNorm ---------------------------------------------------------------------------------------------------------
+void computeNorm(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long M, unsigned long S, unsigned long Nt, unsigned long Nz,
+                 double *X, const double *Z, const double *T, const double *ZT, double *firstOut)
+{
+    const bool zn = cfg.normType == "znorm", tn = cfg.normType == "tnorm", zt = cfg.normType == "ztnorm", tz = cfg.normType == "tznorm";
+    if (!zn && !tn && !zt && !tz) throw Exception("unknown normalization mode:" + cfg.normType); // :752-755
+    if (M == 0 || S == 0) return;
+    if (!X) throw Exception("computeNorm: no test scores");
+    if (!tn && (!Z || Nz == 0)) throw Exception("computeNorm: " + cfg.normType + " needs the znorm scores (znormNistFile)");
+    if (!zn && (!T || Nt == 0)) throw Exception("computeNorm: " + cfg.normType + " needs the tnorm scores (tnormNistFile)");
+    if ((zt || tz) && !ZT) throw Exception("computeNorm: " + cfg.normType + " needs the ztnorm scores (ztnormNistFile)");
+    if (!cfg.impModels.empty() && cfg.impModels.size() != Nt) throw Exception("computeNorm: impModels must flag every cohort model");
+    if (!cfg.impSegs.empty() && cfg.impSegs.size() != Nz) throw Exception("computeNorm: impSegs must flag every impostor segment");
+    const unsigned char *mT = cfg.impModels.empty() ? nullptr : cfg.impModels.data();
+    const unsigned char *mZ = cfg.impSegs.empty() ? nullptr : cfg.impSegs.data();
+    gmmiv_ctx *c = srv.ctx();
+    // the parameter vectors stay on the device: [mu_z, sd_z](M) [mu_t, sd_t](S) [mu_first, sd_first](max(Nt, Nz))
+    const size_t nf = Nt > Nz ? Nt : Nz;
+    double *v = (double *)srv.workspace(7, (2 * (size_t)M + 2 * (size_t)S + 2 * nf) * sizeof(double));
+    double *muZ = v, *sdZ = v + M, *muT = sdZ + M, *sdT = muT + S, *muF = sdT + S, *sdF = muF + nf;
+    auto rowStats = [&](unsigned long r, unsigned long cc, const double *A, const unsigned char *mask, const double *pm, const double *ps,
+                        double *mu, double *sd) {
+        srv.check(gmmiv_score_cohort_stats(c, (int64_t)r, (int64_t)cc, A, (int64_t)cc, 0, mask, pm, ps, cfg.meanMode, cfg.percentH,
+                                           cfg.percentL, mu, sd));
+    };
+    auto colStats = [&](unsigned long r, unsigned long cc, const double *A, const unsigned char *mask, const double *pm, const double *ps,
+                        double *mu, double *sd) {
+        srv.check(gmmiv_score_cohort_stats(c, (int64_t)r, (int64_t)cc, A, (int64_t)cc, 1, mask, pm, ps, cfg.meanMode, cfg.percentH,
+                                           cfg.percentL, mu, sd));
+    };
+    int order;
+    if (zn) { // :573: one distribution per model name over the impostor segments
+        rowStats(M, Nz, Z, mZ, nullptr, nullptr, muZ, sdZ);
+        order = GMMIV_NORM_Z;
+    } else if (tn) { // :537: one distribution per test segment over the cohort models
+        colStats(Nt, S, T, mT, nullptr, nullptr, muT, sdT);
+        order = GMMIV_NORM_T;
+    } else if (zt) {
+        colStats(Nt, Nz, ZT, mT, nullptr, nullptr, muF, sdF);   // :618 t-norm parameters of the impostor segments
+        colStats(Nt, S, T, mT, nullptr, nullptr, muT, sdT);     // :623 t-norm parameters of the test segments
+        rowStats(M, Nz, Z, mZ, muF, sdF, muZ, sdZ);             // :629 z-norm parameters of the t-normed impostor scores
+        order = GMMIV_NORM_ZT;
+    } else {
+        rowStats(M, Nz, Z, mZ, nullptr, nullptr, muZ, sdZ);     // :690 z-norm parameters of the models
+        rowStats(Nt, Nz, ZT, mZ, nullptr, nullptr, muF, sdF);   // :697 z-norm parameters of the cohort models
+        colStats(Nt, S, T, mT, muF, sdF, muT, sdT);             // :704 t-norm parameters of the z-normed cohort scores
+        order = GMMIV_NORM_TZ;
+    }
+    srv.check(gmmiv_score_normalize(c, (int64_t)M, (int64_t)S, X, order, muZ, sdZ, muT, sdT, (zt || tz) ? firstOut : nullptr)); // :552, :587, :647-654, :730-736
+}
+
 } // namespace liagpu

@@ -673,6 +673,26 @@ std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, s
                            const std::vector<unsigned long> &enrolPerModel, std::vector<double> test, unsigned long nTest,
                            const std::vector<double> &pldaF, const std::vector<double> &pldaG, const std::vector<double> &pldaSigma);
 
+// ---- ComputeNorm (LIA_SpkDet/ComputeNorm/src/ComputeNorm.cpp:491-760) on resident score matrices ------------------------------
+// The reference reads NIST result lines and keeps one DistribNorm per name; here the same four chains run on dense matrices
+// that stay on the device (include/gmmiv.h, "score normalisation"):
+//   X  [M  x S ]  the test scores (model m against test segment s), normalised IN PLACE
+//   Z  [M  x Nz]  znormNistFile: the models against the impostor segments
+//   T  [Nt x S ]  tnormNistFile: the t-norm cohort models against the test segments
+//   ZT [Nt x Nz]  ztnormNistFile: the cohort models against the impostor segments
+// normType "znorm" (:562-595) needs Z; "tnorm" (:530-561) T; "ztnorm" (:596-667) and "tznorm" (:668-751) all three.
+// impostorIDList (selectImp, :436-445) is a list of COHORT-side names: impModels[Nt] flags the cohort models, impSegs[Nz] the
+// impostor segments that are in it (empty vector: no selection).  Every pointer may be a host or a device pointer.
+struct ComputeNormCfg {
+    std::string normType = "znorm";     // znorm | tnorm | ztnorm | tznorm
+    int meanMode = 0;                   // 0 mean / std, 1 median / mean absolute deviation
+    double percentH = 0.0, percentL = 0.0; // share of the highest / lowest scores discarded
+    std::vector<unsigned char> impModels, impSegs;
+};
+// firstOut: NULL, or [M x S] -- the t-normed scores of "ztnorm", the z-normed scores of "tznorm" (the reference writes both files)
+void computeNorm(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long M, unsigned long S, unsigned long Nt, unsigned long Nz,
+                 double *X, const double *Z, const double *T, const double *ZT, double *firstOut = nullptr);
+
 // TVAcc::computeEigenProblem (AccumulateTVStat.cpp:2997-3102) for the SYMMETRIC matrices it is used on (the weighted
 // covariance W): cyclic Jacobi on the host, eigenvalues sorted descending, eigenVect[k*rank + j] = component k of
 // the j-th eigenvector (the reference's Eigen / LAPACK solver returns its own column order and sign; any orthonormal

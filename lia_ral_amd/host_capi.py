@@ -588,3 +588,60 @@ def label_segments(lbl_path, label, frame_length=0.01):
     _chk(lib.liagpu_label_segments(lbl_path.encode(), label.encode(), ct.c_double(frame_length), b.ctypes.data_as(_lp),
                                    l.ctypes.data_as(_lp), ct.c_long(1024), ct.byref(n)))
     return b[:n.value].copy(), l[:n.value].copy()
+
+
+# ---- ComputeNorm (LIA_SpkDet/ComputeNorm): score normalisation on resident matrices and on NIST result files
+NORM_TYPES = {"znorm": 0, "tnorm": 1, "ztnorm": 2, "tznorm": 3}
+
+
+def _vp(a):
+    """void* of a numpy array or a torch tensor (used in place), None -> NULL"""
+    if a is None:
+        return ct.c_void_p(0)
+    if type(a).__module__.startswith("torch"):
+        assert a.is_contiguous()
+        return ct.c_void_p(a.data_ptr())
+    assert a.flags["C_CONTIGUOUS"] and a.dtype in (np.float64, np.uint8)
+    return ct.c_void_p(a.ctypes.data)
+
+
+def compute_norm(X, Z=None, T=None, ZT=None, norm_type="znorm", mean_mode=0, percent_h=0.0, percent_l=0.0, imp_models=None,
+                 imp_segs=None, first_out=None, device=0):
+    """liagpu::computeNorm: X [M, S] is normalised IN PLACE (numpy float64 or a torch CUDA tensor); Z [M, Nz], T [Nt, S],
+    ZT [Nt, Nz] as the normType needs them.  first_out: None, or [M, S] for the t-normed (ztnorm) / z-normed (tznorm) scores.
+    imp_models [Nt] / imp_segs [Nz]: the impostorIDList selection as bytes.  -> X"""
+    M, S = X.shape
+    Nt = T.shape[0] if T is not None else (ZT.shape[0] if ZT is not None else 0)
+    Nz = Z.shape[1] if Z is not None else (ZT.shape[1] if ZT is not None else 0)
+    im = None if imp_models is None else np.ascontiguousarray(imp_models, np.uint8)
+    iz = None if imp_segs is None else np.ascontiguousarray(imp_segs, np.uint8)
+    _chk(lib.liagpu_compute_norm(device, NORM_TYPES.get(norm_type, -1), int(mean_mode), ct.c_double(percent_h), ct.c_double(percent_l),
+                                 ct.c_long(M), ct.c_long(S), ct.c_long(Nt), ct.c_long(Nz), _vp(X), _vp(Z), _vp(T), _vp(ZT), _vp(im), _vp(iz),
+                                 _vp(first_out)))
+    return X
+
+
+def compute_norm_files(test_nist_file, output_base, norm_type="znorm", znorm_nist_file=None, tnorm_nist_file=None,
+                       ztnorm_nist_file=None, impostor_id_list=None, mean_mode=0, percent_h=0.0, percent_l=0.0, fields=None, device=0):
+    """liagpu::computeNormFiles: writes <output_base>.znorm / .tnorm / .ztnorm / .tznorm like the reference.  fields: the five
+    positions (fieldGender, fieldName, fieldDecision, fieldSeg, fieldLLR), default 0 1 2 3 4."""
+    e = lambda p: None if p is None else str(p).encode()
+    fl = None if fields is None else (ct.c_int * 5)(*[int(v) for v in fields])
+    _chk(lib.liagpu_compute_norm_files(device, norm_type.encode(), int(mean_mode), ct.c_double(percent_h), ct.c_double(percent_l),
+                                       e(test_nist_file), e(znorm_nist_file), e(tnorm_nist_file), e(ztnorm_nist_file), e(impostor_id_list),
+                                       e(output_base), fl))
+
+
+def result_line(llr, client, test, gender="M", threshold=0.0, times=None, parse=None, fields=None):
+    """-> (the line liagpu::resultLine writes, its fields as liagpu::parseResultLine reads them back: dict).  parse: another
+    line to read instead; fields: the five field positions."""
+    cap = 4096
+    bufs = [ct.create_string_buffer(cap) for _ in range(4)]
+    dec = ct.c_int(0); out = ct.c_double(0.0)
+    fl = None if fields is None else (ct.c_int * 5)(*[int(v) for v in fields])
+    st, en = times if times is not None else (0.0, 0.0)
+    _chk(lib.liagpu_result_line(ct.c_double(llr), client.encode(), test.encode(), gender.encode(), ct.c_double(threshold),
+                                int(times is not None), ct.c_double(st), ct.c_double(en), None if parse is None else parse.encode(), fl,
+                                bufs[0], bufs[1], bufs[2], bufs[3], ct.c_long(cap), ct.byref(dec), ct.byref(out)))
+    return bufs[0].value.decode(), dict(name=bufs[1].value.decode(), seg=bufs[2].value.decode(), gender=bufs[3].value.decode(),
+                                        decision=dec.value, llr=out.value)
