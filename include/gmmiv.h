@@ -172,6 +172,10 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  *                                 log-likelihoods and nothing to the frame count (the M-step weights still sum to 1)
  *   gmmiv_tv_stats(_lines), gmmiv_jfa statistics    nothing added to N / F
  *   gmmiv_frame_moments           NOT screened: sums of the raw values, a NaN goes into the sums like in the reference
+ *   gmmiv_feat_compensate         the frame is COPIED THROUGH unchanged (converted to out_dtype), either kind, and counted in
+ *                                 "zero_llk_frames" (the reference divides 0 by 0 there); kind (1) also in "screened_frames"
+ *   gmmiv_feat_map                NOT screened: best = 0 on a frame whose every term is 0 (the reference's loop leaves idx = 0), the
+ *                                 raw values go through the map of that Gaussian -- a NaN stays a NaN
  * Frames of kind (1) are handled ON THE DEVICE, inside the kernels: every kernel that reads features reads an unusable value as 1e10
  * (csrc/devutil.h, feat_sane: one compare + select where the value is loaded -- in the MFMA log-likelihood kernel once per frame and
  * workgroup, outside its loop).  The value is finite, so no 0 x NaN reaches a statistic, and it puts every logit of the frame near
@@ -215,6 +219,13 @@ int gmmiv_gather_frames(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx,
  * device table the call only enqueues on the context's stream (no synchronisation). */
 int gmmiv_gather_runs(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, int D,
                       const int64_t *runs, int64_t nrun, void *out);
+
+/* The inverse of gmmiv_gather_runs: rows [dst, dst + len) of `in` (ld = D, the matrix gmmiv_gather_runs filled and a frame-rewriting
+ * call has worked on) go back to frames [src, src + len) of x -- FeatureServer::writeFeature over a SegCluster
+ * (AccumulateJFAStat.cpp:4675, GeneralTools.cpp:800) for features that stay resident.  Same run table, same rules: x, in DEVICE
+ * arrays, runs host or device (a device table only enqueues), pieces of <= 64 frames, runs must not overlap in x.  Frames outside
+ * the runs are not touched. */
+int gmmiv_scatter_runs(gmmiv_ctx *ctx, void *x, int x_dtype, int64_t ldx, int D, const int64_t *runs, int64_t nrun, const void *in);
 
 /* ---- segment means of per-frame values (ComputeTest's score per segment, ComputeTest.cpp:181-199) ------
  * out[r * nseg + s] = mean of v[r * ld + t], t in [seg_begin[s], seg_begin[s+1])  (0 for an empty segment).
@@ -279,6 +290,35 @@ int gmmiv_llk_use_top_multi(gmmiv_ctx *ctx, int n_clients, const gmmiv_gmm *cons
  * gamma[t*C + c] = w_c lk_c(x_t) / sum_c' w_c' lk_c'(x_t)   (row-major [T x C]). */
 int gmmiv_occ(gmmiv_ctx *ctx, const gmmiv_gmm *gmm, const void *x, int x_dtype, int64_t T, int64_t ldx,
               double *gamma);
+
+/* ---- model-based feature compensation: the two reference loops that REWRITE the frames from a GMM's per-frame posteriors ----------
+ * gmmiv_feat_compensate: channel compensation in the feature domain, JFAAcc::normalizeFeatures (AccumulateJFAStat.cpp:4623-4686,
+ * substractUXfromFeatures :4689-4697) and its LFA twin FactorAnalysisStat::normalizeFeatures (FactorAnalysis.cpp:979-1024); callers
+ * NormFeat.cpp:825, TrainTarget.cpp:347, SimpleSpkDetSystem.cpp:392:
+ *   out[t][i] = x[t][i] - sum_c gamma_tc offset[c * D + i],   gamma = the full posterior of g (what gmmiv_occ returns),
+ * g = the session model m + Vy + Dz + Ux, offset [C x D] = U x_h of the session (getUX, :1788-1800).
+ * gmmiv_feat_map: featureMapping / getBestGaussian / mapDataToDistrib (GeneralTools.cpp:762-811, caller NormFeat.cpp:619):
+ *   best[t] = argmax_c w_c lk_c(x_t) of the channel-dependent model cd (lowest index on ties, 0 when every term is 0: the strict
+ *   `>` from 0 of getBestGaussian); out[t][i] = sqrt(ci_cov / cd_cov) * (x - cd_mean) + ci_mean of that Gaussian, these operations in
+ *   this order, each rounded on its own.  cd_mean, cd_cov, ci_mean, ci_cov: [C x D] (getMean / getCov of both mixtures); best
+ *   (nullable): int32 [T].
+ * Both: x_dtype and out_dtype are GMMIV_F32 or GMMIV_F64 independently; arithmetic is fp64, an f32 output is rounded once.  out may
+ * be exactly x (same pointer, dtype and stride: in place, like the reference's writeFeature); any other overlap of the two frame
+ * ranges is GMMIV_ERR_ARG, checked -- like the dtypes -- before anything is enqueued.  T = 0 is valid.  All arrays host or device;
+ * with device pointers throughout gmmiv_feat_compensate only enqueues (gmmiv_feat_map waits once for its top-1 selection, like
+ * gmmiv_llk_determine_top).  No shape is refused: vectSize <= 60 with "stats_z" 1 runs k_llk_mfma<WZ> + k_feat_comp per frame chunk
+ * of the likelihood scratch ("z_scratch_mb") -- the stored likelihoods are streamed once, turned into posteriors with one multiply
+ * and contracted against the offsets on the matrix cores; no [T x C] posterior array exists --, anything else (vectSize > 60,
+ * "stats_z" 0, a scratch budget too small for a chunk) takes posteriors in frame chunks of 512 MiB, the fp64 GEMM and a subtraction.
+ * A frame's result does not depend on its position or its neighbours: the Gaussians are summed in one fixed order (tile by tile,
+ * ascending), nothing is accumulated with atomics.  The order differs from the reference's sequential loop: parity is within
+ * 2 (C + 1) 2^-53 (|x| + sum_c gamma |offset|) plus the posterior tolerance (tests/test_gpu_feat_comp.py).
+ * Kernel timers: "k_llk_mfma" and "k_feat_comp" ("k_posteriors", "k_feat_sub" on the generic path); "k_feat_map". */
+int gmmiv_feat_compensate(gmmiv_ctx *ctx, const gmmiv_gmm *g, const void *x, int x_dtype, int64_t T, int64_t ldx,
+                          const double *offset, void *out, int out_dtype, int64_t ldo);
+int gmmiv_feat_map(gmmiv_ctx *ctx, const gmmiv_gmm *cd, const double *cd_mean, const double *cd_cov, const double *ci_mean,
+                   const double *ci_cov, const void *x, int x_dtype, int64_t T, int64_t ldx, void *out, int out_dtype,
+                   int64_t ldo, int32_t *best /* nullable */);
 
 /* ---- MixtureStat::computeAndAccumulateEM loop (accumulateStatEM, AccumulateStat.cpp:103-152) ---
  * acc is the flat EM accumulator, length gmmiv_em_acc_len(C,D) = C*(1+2D)+2 doubles:

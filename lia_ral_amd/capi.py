@@ -86,6 +86,31 @@ def _feat(x):
     return x, (F64 if x.dtype == np.float64 else F32), x.shape[0], x.shape[1]
 
 
+def _feat_view(x):
+    """-> (array, dtype code, T, ld) WITHOUT a copy: a torch tensor or a numpy array whose rows are contiguous and evenly strided (a
+    column slice of a wider matrix keeps its row stride) -- the frames gmmiv_feat_compensate / gmmiv_feat_map read and write"""
+    if _is_torch(x):
+        return _feat(x)
+    assert isinstance(x, np.ndarray) and x.ndim == 2 and x.dtype in (np.float32, np.float64)
+    assert x.shape[0] == 0 or x.shape[1] == 0 or x.strides[1] == x.itemsize
+    ld = x.strides[0] // x.itemsize if x.shape[0] > 1 else x.shape[1]
+    assert x.shape[0] <= 1 or (x.strides[0] % x.itemsize == 0 and ld >= x.shape[1])
+    return x, (F64 if x.dtype == np.float64 else F32), x.shape[0], ld
+
+
+def _feat_like(x, dtype_code):
+    """an output frame matrix of the kind of x (numpy / torch device), compact rows"""
+    if _is_torch(x):
+        import torch
+        return torch.empty((x.shape[0], x.shape[1]), dtype=torch.float64 if dtype_code == F64 else torch.float32, device=x.device)
+    return np.empty((x.shape[0], x.shape[1]), np.float64 if dtype_code == F64 else np.float32)
+
+
+def _vptr(a):
+    """void* of the first element of a frame view (no contiguity demand beyond _feat_view's)"""
+    return ct.c_void_p(a.data_ptr()) if _is_torch(a) else ct.c_void_p(a.ctypes.data)
+
+
 STREAM_DEFAULT = -1        # GMMIV_STREAM_DEFAULT: launch on the NULL (legacy default) stream, torch's default stream
 
 
@@ -215,6 +240,14 @@ class Context:
         r = runs if _is_torch(runs) else np.ascontiguousarray(runs, np.int64)
         _chk(lib.gmmiv_gather_runs(self._h, _ptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(r), ct.c_int64(r.shape[0]), _ptr(out)))
         return out
+
+    def scatter_runs(self, x, runs, inp):
+        """The inverse of gather_runs: rows [dst, dst + len) of `inp` (compact, device) go back to frames [src, src + len) of the device
+        frame matrix x; runs [nrun, 3] int64 (frame, row, length), host or device."""
+        x, dt, T, ldx = _feat(x)
+        r = runs if _is_torch(runs) else np.ascontiguousarray(runs, np.int64)
+        _chk(lib.gmmiv_scatter_runs(self._h, _ptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(r), ct.c_int64(r.shape[0]), _ptr(inp)))
+        return x
 
     def segment_means(self, v, seg_begin, out=None):
         """v: torch CUDA float64 [nrows, ld] (or 1-D); seg_begin: nseg + 1 host offsets -> out [nrows, nseg]."""
@@ -727,6 +760,41 @@ class Gmm:
         out = np.empty((T, self.C))
         _chk(lib.gmmiv_occ(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), _ptr(out)))
         return out
+
+    def feat_compensate(self, x, offset, out=None, out_dtype=None):
+        """out[t] = x[t] - sum_c gamma_tc offset[c] with this model's full posteriors (JFAAcc::normalizeFeatures).  x, out: numpy or
+        torch device frame matrices (row-strided views allowed); out=None allocates one of out_dtype (default: x's), out=x is in place."""
+        x, dt, T, ldx = _feat_view(x)
+        if out is None:
+            out = _feat_like(x, dt if out_dtype is None else out_dtype)
+        out, odt, To, ldo = _feat_view(out)
+        assert To == T and out.shape[1] == x.shape[1] == self.D
+        off = offset if _is_torch(offset) else np.ascontiguousarray(offset, np.float64)
+        _chk(lib.gmmiv_feat_compensate(self.ctx._h, self._h, _vptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), _ptr(off), _vptr(out), odt,
+                                       ct.c_int64(ldo)))
+        return out
+
+    def feat_map(self, cd_mean, cd_cov, ci_mean, ci_cov, x, out=None, out_dtype=None, best=True):
+        """Feature mapping (featureMapping, GeneralTools.cpp:762-811) with this model as the channel-dependent one: -> (out, best);
+        best: int32 [T] (numpy, or torch device when x is), or None with best=False."""
+        x, dt, T, ldx = _feat_view(x)
+        if out is None:
+            out = _feat_like(x, dt if out_dtype is None else out_dtype)
+        out, odt, To, ldo = _feat_view(out)
+        assert To == T and out.shape[1] == x.shape[1] == self.D
+        tabs = [a if _is_torch(a) else np.ascontiguousarray(a, np.float64) for a in (cd_mean, cd_cov, ci_mean, ci_cov)]
+        b = None
+        if best is True:
+            if _is_torch(x):
+                import torch
+                b = torch.empty(T, dtype=torch.int32, device=x.device)
+            else:
+                b = np.empty(T, np.int32)
+        elif best is not False and best is not None:
+            b = best
+        _chk(lib.gmmiv_feat_map(self.ctx._h, self._h, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), _vptr(x), dt, ct.c_int64(T),
+                                ct.c_int64(ldx), _vptr(out), odt, ct.c_int64(ldo), _ptr(b)))
+        return out, b
 
     def em_acc_len(self):
         return lib.gmmiv_em_acc_len(self.C, self.D)

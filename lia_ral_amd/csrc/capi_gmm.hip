@@ -1281,5 +1281,174 @@ int gmmiv_tv_stats_lines(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt
     return o_f.finish();
 }
 
+// ---- frames rewritten from the posteriors: feature-domain channel compensation, feature mapping ----------------------------
+// argument checks shared by gmmiv_feat_compensate / gmmiv_feat_map: nothing is enqueued before they pass
+static int feat_check_dtype(const char *who, int xdt, int odt)
+{
+    if ((xdt != GMMIV_F32 && xdt != GMMIV_F64) || (odt != GMMIV_F32 && odt != GMMIV_F64)) { gmmiv_set_error("%s: x_dtype / out_dtype must be GMMIV_F32 or GMMIV_F64", who); return GMMIV_ERR_ARG; }
+    return GMMIV_OK;
+}
+static int feat_check(const char *who, const void *x, int xdt, int64_t T, int64_t ldx, const void *out, int odt, int64_t ldo, int D)
+{
+    if (T < 0 || ldx < D || ldo < D) { gmmiv_set_error("%s: T < 0 or a row stride below vectSize %d", who, D); return GMMIV_ERR_ARG; }
+    if (T == 0) return GMMIV_OK;
+    if (!x || !out) { gmmiv_set_error("%s: x or out == NULL", who); return GMMIV_ERR_ARG; }
+    const uintptr_t xb = (uintptr_t)x, xe = xb + ((size_t)(T - 1) * ldx + D) * esize(xdt);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + ((size_t)(T - 1) * ldo + D) * esize(odt);
+    const bool in_place = x == out && xdt == odt && ldx == ldo;
+    if (!in_place && xb < oe && ob < xe) { gmmiv_set_error("%s: out overlaps x (only out == x with the same dtype and stride is allowed)", who); return GMMIV_ERR_ARG; }
+    return GMMIV_OK;
+}
+
+// Device view of the output frames [T x ldo]; a host output is produced compact (ld = D) in WS_FEAT_OUT and copied back by finish().
+struct FeatOut {
+    void *d = nullptr, *host = nullptr;
+    int64_t ld = 0, hld = 0, T = 0;
+    int D = 0, dt = 0;
+    gmmiv_ctx *c = nullptr;
+    int init(gmmiv_ctx *ctx, void *out, int odt, int64_t T_, int64_t ldo, int D_)
+    {
+        c = ctx; T = T_; D = D_; dt = odt;
+        if (T == 0 || gmmiv_is_device_ptr(out)) { d = out; ld = ldo; return GMMIV_OK; }
+        int rc = c->scratch(WS_FEAT_OUT, (size_t)T * D * esize(odt), &d);
+        if (rc) return rc;
+        host = out; hld = ldo; ld = D;
+        return GMMIV_OK;
+    }
+    void *at(int64_t frame) const { return (char *)d + (size_t)frame * ld * esize(dt); }
+    int finish()
+    {
+        if (host) {
+            GCHK(hipMemcpy2DAsync(host, hld * esize(dt), d, D * esize(dt), D * esize(dt), T, hipMemcpyDeviceToHost, c->stream));
+            GCHK(hipStreamSynchronize(c->stream));
+        }
+        return GMMIV_OK;
+    }
+};
+
+int gmmiv_feat_compensate(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int64_t T, int64_t ldx, const double *offset,
+                          void *out, int odt, int64_t ldo)
+{
+    int rc = feat_check_dtype("feat_compensate", dt, odt);
+    if (rc) return rc;
+    if (!c || !g) { gmmiv_set_error("feat_compensate: NULL context or model"); return GMMIV_ERR_ARG; }
+    if ((rc = check_model(c, g))) return rc;
+    if (!offset) { gmmiv_set_error("feat_compensate: offset == NULL"); return GMMIV_ERR_ARG; }
+    if ((rc = feat_check("feat_compensate", x, dt, T, ldx, out, odt, ldo, g->D))) return rc;
+    if (T == 0) return GMMIV_OK;
+    XView xv;
+    if ((rc = xv.init(c, x, dt, T, ldx, g->D))) return rc;
+    FeatOut o;
+    if ((rc = o.init(c, out, odt, T, ldo, g->D))) return rc;
+    DevIn<double> i_off;
+    if ((rc = i_off.init(c, WS_FEAT_M0, offset, (size_t)g->C * g->D))) return rc;
+    if ((rc = count_unusable(c, xv, dt, T, g->D))) return rc;
+    // Fast path: k_llk_mfma<WZ> leaves the scaled likelihoods of a frame chunk in the scratch, k_feat_comp streams them once,
+    // contracts the posteriors against the offsets on the matrix cores and writes D values per frame -- no posterior array
+    const int64_t Tcz = g->D <= 64 ? z_chunk_frames(c, g) : 0;
+    if (Tcz > 0) {
+        const int64_t first = T < Tcz ? T : Tcz;
+        const long nfb = z_tile_blocks(first);
+        void *zb, *eit, *inv, *lz, *offp;
+        if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
+        if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
+        if ((rc = c->scratch(WS_INV, (size_t)first * (sizeof(double) + sizeof(int)), &inv))) return rc;
+        if ((rc = c->scratch(WS_LSE, (size_t)first * sizeof(double), &lz))) return rc;
+        if ((rc = c->scratch(WS_FEAT_OFF, gmmk_feat_offset_doubles(g->nct, g->D) * sizeof(double), &offp))) return rc;
+        int *efin = (int *)((double *)inv + first);
+        GCHK(gmmk_feat_pack_offset(c->stream, i_off.d, g->C, g->D, g->nct, (double *)offp));
+        for (int64_t c0 = 0; c0 < T; c0 += Tcz) {
+            const int64_t n = (T - c0) < Tcz ? (T - c0) : Tcz;
+            c->t_begin("k_llk_mfma", c0 == 0);
+            GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lz,
+                            (int)c->use_glds, (double *)zb, nfb, (int *)eit, (double *)inv, efin));
+            c->t_end();
+            GCHK(count_dead(c, (const double *)lz, n));
+            c->t_begin("k_feat_comp", c0 == 0);
+            GCHK(gmmk_feat_comp(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, n, g->D, g->nct, (const double *)zb, nfb,
+                                (const int *)eit, (const double *)inv, efin, (const double *)offp, o.at(c0), o.ld));
+            c->t_end();
+        }
+        return o.finish();
+    }
+    // Generic path (vectSize > 60, "stats_z" 0, no likelihood scratch): posteriors of a bounded frame chunk (512 MiB), P = gamma offset on
+    // the fp64 GEMM, out = x - P.  The log-sums of ALL frames come first, so an in-place call never evaluates a rewritten frame.
+    double *lse;
+    if ((rc = run_lse(c, g, xv, dt, T, &lse))) return rc;
+    int64_t per = (int64_t)(((size_t)512 << 20) / ((size_t)g->C * sizeof(double))) / 2 * 2;
+    if (per < 64) per = 64;
+    const int64_t firstg = T < per ? T : per;
+    void *gam, *pm;
+    if ((rc = c->scratch(WS_Z, (size_t)firstg * g->C * sizeof(double), &gam))) return rc;
+    if ((rc = c->scratch(WS_INV, (size_t)firstg * g->D * sizeof(double), &pm))) return rc;
+    for (int64_t b = 0; b < T; b += per) {
+        const int64_t m = T - b < per ? T - b : per;
+        c->t_begin("k_posteriors", b == 0);
+        GCHK(gmmk_posteriors(c->stream, dt == GMMIV_F64, x_at(xv, dt, b), (long)m, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, lse + b,
+                             (double *)gam));
+        c->t_end();
+        GCHK(tvk_dgemm(c->stream, false, false, (int)m, g->D, g->C, 1.0, (const double *)gam, g->C, 0, i_off.d, g->D, 0, 0.0, (double *)pm, g->D, 0, 1));
+        c->t_begin("k_feat_sub", b == 0);
+        GCHK(gmmk_feat_sub(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, x_at(xv, dt, b), xv.ldx, (long)m, g->D, (const double *)pm, lse + b, o.at(b), o.ld));
+        c->t_end();
+    }
+    return o.finish();
+}
+
+int gmmiv_feat_map(gmmiv_ctx *c, const gmmiv_gmm *cd, const double *cd_mean, const double *cd_cov, const double *ci_mean,
+                   const double *ci_cov, const void *x, int dt, int64_t T, int64_t ldx, void *out, int odt, int64_t ldo, int32_t *best)
+{
+    int rc = feat_check_dtype("feat_map", dt, odt);
+    if (rc) return rc;
+    if (!c || !cd) { gmmiv_set_error("feat_map: NULL context or model"); return GMMIV_ERR_ARG; }
+    if ((rc = check_model(c, cd))) return rc;
+    if (!cd_mean || !cd_cov || !ci_mean || !ci_cov) { gmmiv_set_error("feat_map: a model table is NULL"); return GMMIV_ERR_ARG; }
+    if ((rc = feat_check("feat_map", x, dt, T, ldx, out, odt, ldo, cd->D))) return rc;
+    if (T == 0) return GMMIV_OK;
+    XView xv;
+    if ((rc = xv.init(c, x, dt, T, ldx, cd->D))) return rc;
+    FeatOut o;
+    if ((rc = o.init(c, out, odt, T, ldo, cd->D))) return rc;
+    const size_t CD = (size_t)cd->C * cd->D;
+    DevIn<double> m0, v0, m1, v1;
+    if ((rc = m0.init(c, WS_FEAT_M0, cd_mean, CD)) || (rc = v0.init(c, WS_FEAT_M1, cd_cov, CD)) || (rc = m1.init(c, WS_FEAT_M2, ci_mean, CD)) ||
+        (rc = v1.init(c, WS_FEAT_M3, ci_cov, CD))) return rc;
+    int32_t *bd = best;
+    if (!gmmiv_is_device_ptr(best)) {
+        void *p;
+        if ((rc = c->scratch(WS_FEAT_IDX, (size_t)T * sizeof(int32_t), &p))) return rc;
+        bd = (int32_t *)p;
+    }
+    // getBestGaussian = the top-1 selection (strict `>` from 0: the lowest index on ties, index 0 when every term is 0).  The index
+    // array starts at 0: the fused ranking kernel writes no index for a frame whose candidates are all PADDED Gaussians (a frame with an
+    // unusable value under a model whose Gaussian count is no multiple of 16) -- 0 is what the rule gives such a frame.
+    GCHK(hipMemsetAsync(bd, 0, (size_t)T * sizeof(int32_t), c->stream));
+    if ((rc = gmmiv_llk_determine_top(c, cd, xv.d, dt, T, xv.ldx, 1, GMMIV_TOP_COMPLETE, -INFINITY, INFINITY, bd, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr))) return rc;
+    c->t_begin("k_feat_map");
+    GCHK(gmmk_feat_map(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, xv.d, xv.ldx, T, cd->D, cd->C, bd, m0.d, v0.d, m1.d, v1.d, o.d, o.ld));
+    c->t_end();
+    if (best && bd != best) GCHK(hipMemcpyAsync(best, bd, (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = o.finish())) return rc;
+    if (best && bd != best) GCHK(hipStreamSynchronize(c->stream));
+    return GMMIV_OK;
+}
+
+int gmmiv_scatter_runs(gmmiv_ctx *c, void *x, int dt, int64_t ldx, int D, const int64_t *runs, int64_t nrun, const void *in)
+{
+    if (!c || !x || !in || (!runs && nrun > 0) || nrun < 0 || D <= 0 || ldx < D) { gmmiv_set_error("scatter_runs: bad argument"); return GMMIV_ERR_ARG; }
+    if (dt != GMMIV_F32 && dt != GMMIV_F64) { gmmiv_set_error("scatter_runs: feature dtype must be GMMIV_F32 or GMMIV_F64"); return GMMIV_ERR_ARG; }
+    if (!gmmiv_is_device_ptr(x) || !gmmiv_is_device_ptr(in)) { gmmiv_set_error("scatter_runs: x and in must be device arrays"); return GMMIV_ERR_ARG; }
+    if (nrun == 0) return GMMIV_OK;
+    GBIND(c);
+    DevIn<int64_t> i_runs;
+    int rc = i_runs.init(c, WS_T0, runs, (size_t)nrun * 3);
+    if (rc) return rc;
+    c->t_begin("k_scatter_runs");
+    GCHK(gmmk_scatter_runs(c->stream, dt == GMMIV_F64, x, ldx, D, (const long *)i_runs.d, nrun, in));
+    c->t_end();
+    if (!gmmiv_is_device_ptr(runs)) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
+    return GMMIV_OK;
+}
 
 } // extern "C"

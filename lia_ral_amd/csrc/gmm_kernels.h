@@ -93,3 +93,14 @@ int gmmk_topc_use4_multi(hipStream_t st, int x_f64, const void *x, long T, long 
                          const int *idx, const double *nllk, int complete, double lo, double hi, double *llk); // clients: device array of {mean, iv, lwc, (long) C}
 int gmmk_post_from_z(hipStream_t st, long n, int C, int nct, const double *zbuf, long nfb, const int *eit, const double *inv,
                      const int *efin, double *gamma);
+
+// feat_comp.hip: frames rewritten from the posteriors (gmmiv_feat_compensate / gmmiv_feat_map / gmmiv_scatter_runs)
+size_t gmmk_feat_offset_doubles(int nct, int D);
+int gmmk_feat_pack_offset(hipStream_t st, const double *off, int C, int D, int nct, double *offP); // MFMA B-operand order, zero padded
+int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const double *zbuf, long nfb,
+                   const int *eit, const double *inv, const int *efin, const double *offP, void *out, long ldo); // -1: D > 64
+int gmmk_feat_sub(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, const double *P, const double *lse, void *out,
+                  long ldo);
+int gmmk_feat_map(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long T, int D, int C, const int *best, const double *cd_mean,
+                  const double *cd_cov, const double *ci_mean, const double *ci_cov, void *out, long ldo);
+int gmmk_scatter_runs(hipStream_t st, int x_f64, void *x, long ldx, int D, const long *runs, long nrun, const void *in);

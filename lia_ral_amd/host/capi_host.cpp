@@ -916,6 +916,71 @@ int liagpu_jfa_stats(int device, const float *x, long T, int D, const long *sess
     })
 }
 
+// Host arithmetic of JFAAcc::getUX / getSpeakerModel for ONE session (no device is opened): ux [SV], sp [SV] = m + V y + D z + U x
+int liagpu_jfa_session_model_host(long SV, int rankEV, int rankEC, const double *means, const double *V, const double *y, const double *Dm,
+                                  const double *z, const double *U, const double *x, double *ux, double *sp)
+{
+    GUARD({
+        jfaUX(U, x, (unsigned long)rankEC, (unsigned long)SV, ux);
+        jfaSessionSupervector(means, V, y, (unsigned long)rankEV, Dm, z, ux, (unsigned long)SV, sp);
+    })
+}
+
+static std::vector<SegCluster> clusters_from(const long *clu_off, long nclu, const long *seg_begin, const long *seg_len)
+{
+    std::vector<SegCluster> out((size_t)nclu);
+    for (long h = 0; h < nclu; ++h)
+        for (long k = clu_off[h]; k < clu_off[h + 1]; ++k) {
+            Seg s; s.begin = (unsigned long)seg_begin[k]; s.length = (unsigned long)seg_len[k]; s.source = 0;
+            out[(size_t)h].push_back(s);
+        }
+    return out;
+}
+
+// JFAAcc::normalizeFeatures on the frames x [T x D] (rewritten in place): session h owns the segments clu_off[h] .. clu_off[h + 1]
+// of (seg_begin, seg_len).  Y [nspk x rankEV], X [nsess x rankEC], Z [nspk x SV] are the factors; ux_out / model_out (nullable):
+// getUX / the means of getSpeakerModel of every session, [nsess x SV].
+int liagpu_jfa_normalize_features(int device, float *x, long T, int D, long nspk, const long *sessPerSpk, const long *clu_off,
+                                  const long *seg_begin, const long *seg_len, int C, const double *w, const double *mean, const double *cov,
+                                  int rankEV, int rankEC, const double *V, const double *U, const double *Dm, const double *Y, const double *X,
+                                  const double *Z, double *ux_out, double *model_out)
+{
+    GUARD({
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD ubm = make_mixture(C, D, w, mean, cov);
+        std::vector<unsigned long> sps(sessPerSpk, sessPerSpk + nspk);
+        JFAAcc jfa(srv, ubm, (unsigned long)rankEV, (unsigned long)rankEC, sps);
+        const size_t SV = (size_t)C * D, nsess = jfa.getNSessions();
+        jfa.loadEV(std::vector<double>(V, V + (size_t)rankEV * SV));
+        jfa.loadEC(std::vector<double>(U, U + (size_t)rankEC * SV));
+        jfa.loadD(std::vector<double>(Dm, Dm + SV));
+        jfa.getY().assign(Y, Y + (size_t)nspk * rankEV);
+        jfa.getX().assign(X, X + nsess * rankEC);
+        jfa.getZ().assign(Z, Z + (size_t)nspk * SV);
+        for (size_t h = 0; h < nsess && (ux_out || model_out); ++h) {
+            if (ux_out) { std::vector<double> ux; jfa.getUX(ux, (unsigned long)h); memcpy(ux_out + h * SV, ux.data(), SV * sizeof(double)); }
+            if (model_out) { MixtureGD m = ubm; jfa.getSpeakerModel(m, (unsigned long)h); memcpy(model_out + h * SV, m.means().data(), SV * sizeof(double)); }
+        }
+        jfa.normalizeFeatures(fs, clusters_from(clu_off, (long)nsess, seg_begin, seg_len));
+        fs.download(x);
+    })
+}
+
+// liagpu::featureMapping on the frames x [T x D] (rewritten in place) over the cluster (seg_begin, seg_len)[nseg]
+int liagpu_feature_mapping(int device, float *x, long T, int D, const long *seg_begin, const long *seg_len, long nseg, int C, const double *w_cd,
+                           const double *mean_cd, const double *cov_cd, const double *w_ci, const double *mean_ci, const double *cov_ci)
+{
+    GUARD({
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD cd = make_mixture(C, D, w_cd, mean_cd, cov_cd), ci = make_mixture(C, D, w_ci, mean_ci, cov_ci);
+        const long off[2] = {0, nseg};
+        featureMapping(ci, cd, fs, clusters_from(off, 1, seg_begin, seg_len)[0]);
+        fs.download(x);
+    })
+}
+
 // ComputeTest from FILES for one ndx line (test file + client list): RAW models, .prm features with
 // featureServerMask, .lbl selection.  Writes the NIST-style result lines (segmental mode) into out_text
 // and the LLRs into llr_out[nseg x nClients].  ComputeTest.cpp:129-215 + the format readers of io.h.

@@ -315,6 +315,38 @@ const float *FeatureBuffer::select(const SegCluster &c, unsigned long &nSelected
     return _sel;
 }
 
+void FeatureBuffer::scatter(const SegCluster &c, const float *selected)
+{
+    unsigned long first = 0, n = 0;
+    size_t nPieces = 0;
+    const unsigned long nMerged = buildRuns(c, n, first, nPieces);
+    if (n == 0) return;
+    if (selected == _dev + (size_t)first * _d && nMerged == 1) return; // handed out in place: already where it belongs
+    if (selected >= _dev && selected < _dev + (size_t)_n * _d) throw Exception("FeatureBuffer::scatter: the matrix lies inside the buffer but is not this cluster's selection");
+    hipStream_t st = (hipStream_t)_srv.stream();
+    if (_dRunsCap < nPieces) {
+        _srv.sync();
+        if (_dRuns) hipcheck(hipFree(_dRuns), "FeatureBuffer: hipFree");
+        _dRuns = nullptr; _dRunsCap = 0;
+        const size_t cap = nPieces + nPieces / 4;
+        hipcheck(hipMalloc((void **)&_dRuns, cap * 3 * sizeof(int64_t)), "FeatureBuffer: hipMalloc(runs)");
+        _dRunsCap = cap;
+    }
+    hipcheck(hipMemcpyAsync(_dRuns, _hRuns, nPieces * 3 * sizeof(int64_t), hipMemcpyHostToDevice, st), "FeatureBuffer: upload(runs)");
+    if (!_runsCopied) {
+        hipEvent_t e;
+        hipcheck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "FeatureBuffer: hipEventCreate");
+        _runsCopied = e;
+    }
+    hipcheck(hipEventRecord((hipEvent_t)_runsCopied, st), "FeatureBuffer: hipEventRecord");
+    _srv.check(gmmiv_scatter_runs(_srv.ctx(), _dev, GMMIV_F32, (int64_t)_d, (int)_d, _dRuns, (int64_t)nPieces, selected));
+}
+void FeatureBuffer::download(float *frames) const
+{
+    _srv.sync();
+    if (_n) hipcheck(hipMemcpy(frames, _dev, (size_t)_n * _d * sizeof(float), hipMemcpyDeviceToHost), "FeatureBuffer: download");
+}
+
 // ---- MixtureGD ---------------------------------------------------------------------------------
 MixtureGD::MixtureGD(unsigned long distribCount, unsigned long vectSize)
     : _c(distribCount), _d(vectSize), _w(distribCount, 1.0 / distribCount), _mean(distribCount * vectSize, 0.0),
@@ -1958,6 +1990,85 @@ void JFAAcc::getMplusVYplusDZ(std::vector<double> &Sp, unsigned long spk)
     Sp.assign(_svSize, 0.0);
     _srv.check(gmmiv_jfa_subtract(_srv.ctx(), 1, (int)_n_distrib, (int)_vectSize, n1.data(), Sp.data(), nullptr, 1, _ubm_means.cdev(), (int)_rankEV,
                                   _V.cdev(), _Y.cdev() + spk * _rankEV, _D.cdev(), _Z.cdev() + spk * _svSize));
+}
+
+void jfaUX(const double *U, const double *x, unsigned long rankEC, unsigned long svSize, double *ux)
+{
+    for (unsigned long i = 0; i < svSize; ++i) {
+        double v = 0.0;
+        for (unsigned long j = 0; j < rankEC; ++j) v += U[j * svSize + i] * x[j];
+        ux[i] = v;
+    }
+}
+void jfaSessionSupervector(const double *means, const double *V, const double *y, unsigned long rankEV, const double *Dm, const double *z,
+                           const double *ux, unsigned long svSize, double *sp)
+{
+    for (unsigned long i = 0; i < svSize; ++i) {
+        double vy = 0.0;                                            // getVY, then Sp = m + vy + D z (:1926-1933), then + ux (:4616)
+        for (unsigned long j = 0; j < rankEV; ++j) vy += V[j * svSize + i] * y[j];
+        sp[i] = (means[i] + vy + Dm[i] * z[i]) + ux[i];
+    }
+}
+void JFAAcc::getUX(std::vector<double> &ux, unsigned long session)
+{
+    if (session >= _n_sessions) throw Exception("getUX: session index out of range");
+    ux.assign(_svSize, 0.0);
+    jfaUX(_matU.chost().data(), _matX.chost().data() + session * _rankEC, _rankEC, _svSize, ux.data());
+}
+void JFAAcc::getSpeakerModel(MixtureGD &mixture, unsigned long session)
+{
+    if (session >= _n_sessions) throw Exception("getSpeakerModel: session index out of range");
+    if (mixture.getDistribCount() != _n_distrib || mixture.getVectSize() != _vectSize) throw Exception("getSpeakerModel: model shape differs from the UBM's");
+    const unsigned long spk = (unsigned long)_owner[session];
+    std::vector<double> ux, sp(_svSize);
+    getUX(ux, session);
+    jfaSessionSupervector(_ubm_means.chost().data(), _V.chost().data(), _Y.chost().data() + spk * _rankEV, _rankEV, _D.chost().data(),
+                          _Z.chost().data() + spk * _svSize, ux.data(), _svSize, sp.data());
+    for (unsigned long c = 0; c < _n_distrib; ++c)                 // svToModel: the means, nothing else
+        for (unsigned long i = 0; i < _vectSize; ++i) mixture.setMean(c, sp[c * _vectSize + i], i);
+}
+void JFAAcc::normalizeFeatures(FeatureBuffer &fs, const std::vector<SegCluster> &segsPerSession)
+{
+    if (segsPerSession.size() != _n_sessions) throw Exception("normalizeFeatures: one SegCluster per session expected");
+    if (fs.getVectSize() != _vectSize) throw Exception("normalizeFeatures: the features' vectSize differs from the model's");
+    if (&fs.server() != &_srv) throw Exception("normalizeFeatures: the feature buffer must live on the accumulator's server (the frames are rewritten in stream order)");
+    // U x_h and m + V y_s + D z_s + U x_h of ALL sessions: 0 - (-1)(...) through the subtraction entry point, one product per factor matrix
+    DVec ux(_srv), sp(_srv), wts(_srv);
+    std::vector<double> n1(_n_sessions * _n_distrib, -1.0);
+    ux.assign(_n_sessions * _svSize, 0.0);
+    sp.assign(_n_sessions * _svSize, 0.0);
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), ux.dev(), nullptr, (int64_t)_n_sessions,
+                                  nullptr, (int)_rankEC, _matU.cdev(), _matX.cdev(), nullptr, nullptr));
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), sp.dev(), _owner.data(), (int64_t)_n_speakers,
+                                  _ubm_means.cdev(), (int)_rankEV, _V.cdev(), _Y.cdev(), _D.cdev(), _Z.cdev()));
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), sp.dev(), nullptr, (int64_t)_n_sessions,
+                                  nullptr, (int)_rankEC, _matU.cdev(), _matX.cdev(), nullptr, nullptr));
+    wts.set(_ubm.weights());
+    DeviceMixture session(_srv, _ubm);                             // duplicateMixture(world): weights and variances stay the UBM's
+    FiniteScope fin(_srv, fs);
+    for (unsigned long h = 0; h < _n_sessions; ++h) {
+        unsigned long n = 0;
+        float *x = fs.selectForUpdate(segsPerSession[h], n);
+        if (n == 0) continue;
+        _srv.check(gmmiv_gmm_set(session.handle(), wts.cdev(), sp.cdev() + h * _svSize, _ubm_invvar.cdev()));
+        _srv.check(gmmiv_feat_compensate(_srv.ctx(), session.handle(), x, GMMIV_F32, (int64_t)n, (int64_t)_vectSize, ux.cdev() + h * _svSize, x,
+                                         GMMIV_F32, (int64_t)_vectSize));
+        fs.scatter(segsPerSession[h], x);
+    }
+}
+void featureMapping(MixtureGD &ci, MixtureGD &cd, FeatureBuffer &fs, const SegCluster &selectedSegments)
+{
+    if (ci.getDistribCount() != cd.getDistribCount() || ci.getVectSize() != cd.getVectSize() || cd.getVectSize() != fs.getVectSize())
+        throw Exception("featureMapping: the two models and the features must have one shape");
+    GpuServer &srv = fs.server();
+    DeviceMixture dcd(srv, cd);
+    unsigned long n = 0;
+    float *x = fs.selectForUpdate(selectedSegments, n);
+    if (n == 0) return;
+    const int64_t D = (int64_t)fs.getVectSize();
+    srv.check(gmmiv_feat_map(srv.ctx(), dcd.handle(), cd.means().data(), cd.covs().data(), ci.means().data(), ci.covs().data(), x, GMMIV_F32, (int64_t)n, D,
+                             x, GMMIV_F32, D, nullptr));
+    fs.scatter(selectedSegments, x);
 }
 
 std::vector<double> computeTestDotProduct(GpuServer &srv, JFAAcc &jfaAcc, const std::vector<double> &clientSV, unsigned long nClients)

@@ -94,6 +94,14 @@ class FeatureBuffer {
     // server that follows sees the frames; the host does not wait.  A cluster that is one contiguous run is returned in place.
     // The matrix is overwritten by the next select() -- also in stream order, after the kernels that still read it.
     const float *select(const SegCluster &c, unsigned long &nSelected);
+    // The same selection for a call that REWRITES the frames (normalizeFeatures, featureMapping) -- and scatter(), its inverse:
+    // the rows of `selected` (what select / selectForUpdate returned for this cluster) go back to the cluster's frames, in stream
+    // order (k_scatter_runs; nothing to do when the cluster was one contiguous run and was handed out in place).  This is the
+    // reference's writeFeature (AccumulateJFAStat.cpp:4675, GeneralTools.cpp:800).  Frames outside the cluster are not touched.
+    float *selectForUpdate(const SegCluster &c, unsigned long &nSelected) { return const_cast<float *>(select(c, nSelected)); }
+    void scatter(const SegCluster &c, const float *selected);
+    float *mutableDevice() { return _dev; }             // the resident frames as a mutable device view
+    void download(float *frames) const;                 // all frames back to the host (waits for the stream)
     GpuServer &server() { return _srv; }
 
   private:
@@ -557,6 +565,14 @@ class JFAAcc {
     void substractMplusDZByChannel();  // :3948-3976   _F_X_h -= N_h (m + D z) of the session's speaker
     void orthonormalizeV();            // :4700-4777
     void getMplusVYplusDZ(std::vector<double> &Sp, unsigned long spk); // :1926-1935
+    void getUX(std::vector<double> &ux, unsigned long session);        // :1803-1816 (ux += U(j, i) X(session, j); the index overload
+                                                                       // :1788-1800 assigns instead of adding and keeps only the last j)
+    void getSpeakerModel(MixtureGD &mixture, unsigned long session);   // :4605-4619: the means of m + V y + D z + U x_h
+    // normalizeFeatures (:4623-4686) / substractUXfromFeatures (:4689-4697): o'_t = o_t - sum_c P(c | o_t) (U x_h)_c on the frames of every
+    // session's cluster, with the full posterior of the session model.  The offsets U x_h and the session supervectors of ALL sessions
+    // come from one product each; per session: the session model is set, the cluster's frames are selected, compensated in one call
+    // of gmmiv_feat_compensate and scattered back -- one library call per session, not one per label segment.
+    void normalizeFeatures(FeatureBuffer &fs, const std::vector<SegCluster> &segsPerSession);
     std::vector<double> &getV() { return _V.host(); }
     std::vector<double> &getU() { return _matU.host(); }
     std::vector<double> &getD() { return _D.host(); }
@@ -579,6 +595,13 @@ class JFAAcc {
     DVec _ubm_means, _ubm_invvar, _matN, _N_h, _F_X, _F_X_h, _cN, _cN_h, _cF_X, _cF_X_h;
     DVec _V, _matU, _D, _Y, _matX, _Z, _vEvT, _uEuT, _Aev, _Cev, _Aec, _Cec, _mdR, _mdr, _mdmw; // _md*: minimum-divergence sums, unused by JFA
 };
+// host arithmetic of getUX / getSpeakerModel (no device): ux[i] = sum_j U[j][i] x[j] in the reference's order; sp = (m + vy + D z) + ux
+void jfaUX(const double *U, const double *x, unsigned long rankEC, unsigned long svSize, double *ux);
+void jfaSessionSupervector(const double *means, const double *V, const double *y, unsigned long rankEV, const double *Dm, const double *z,
+                           const double *ux, unsigned long svSize, double *sp);
+// featureMapping (GeneralTools.cpp:762-811, NormFeat.cpp:619): every frame of the cluster through its best Gaussian of the
+// channel-dependent model cd to the same Gaussian of the channel-independent model ci, in place in the buffer
+void featureMapping(MixtureGD &ci, MixtureGD &cd, FeatureBuffer &fs, const SegCluster &selectedSegments);
 // the three training tools around it (statistics and initial matrices already in the accumulator)
 void eigenVoice(JFAAcc &jfaAcc, unsigned long nbIt, bool orthonormalizeV);   // EigenVoice.cpp:114-147
 void eigenChannel(JFAAcc &jfaAcc, unsigned long nbIt);                        // EigenChannel.cpp:118-160

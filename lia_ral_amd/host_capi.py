@@ -521,6 +521,53 @@ def jfa_stats(x, sess_begin, sess_per_spk, ubm, device=0):
                               sps.ctypes.data_as(_lp), C, _d(w), _d(mean), _d(cov), _d(N), _d(Nh), _d(FX), _d(FXh)))
     return N, Nh, FX, FXh
 
+def jfa_session_model_host(means, V, y, Dm, z, U, x):
+    """getUX / getSpeakerModel host arithmetic of one session (no device): -> (ux [SV], m + V y + D z + U x [SV])."""
+    means, V, y, Dm, z, U, x = [np.ascontiguousarray(a, np.float64) for a in (means, V, y, Dm, z, U, x)]
+    SV = means.size
+    ux = np.empty(SV); sp = np.empty(SV)
+    _chk(lib.liagpu_jfa_session_model_host(ct.c_long(SV), V.shape[0], U.shape[0], _d(means), _d(V), _d(y), _d(Dm), _d(z), _d(U), _d(x), _d(ux), _d(sp)))
+    return ux, sp
+
+
+def _clusters(clusters):
+    """list (one per session) of lists of (begin, length) -> offsets, begins, lengths as int64 arrays"""
+    off = np.zeros(len(clusters) + 1, np.int64)
+    for h, c in enumerate(clusters):
+        off[h + 1] = off[h] + len(c)
+    b = np.ascontiguousarray([s[0] for c in clusters for s in c], np.int64)
+    l = np.ascontiguousarray([s[1] for c in clusters for s in c], np.int64)
+    return off, b, l
+
+
+def jfa_normalize_features(x, sess_per_spk, clusters, ubm, V, U, Dm, Y, X, Z, device=0):
+    """JFAAcc::normalizeFeatures on float32 frames: -> (compensated frames, ux [nsess, SV], session model means [nsess, SV])."""
+    w, mean, cov = [np.ascontiguousarray(a, np.float64) for a in ubm]
+    C, D = mean.shape
+    x = np.array(x, np.float32)
+    sps = np.ascontiguousarray(sess_per_spk, np.int64)
+    off, b, l = _clusters(clusters)
+    V, U, Dm, Y, X, Z = [np.ascontiguousarray(a, np.float64) for a in (V, U, Dm, Y, X, Z)]
+    nsess = int(sps.sum())
+    ux = np.empty((nsess, C * D)); models = np.empty((nsess, C * D))
+    _chk(lib.liagpu_jfa_normalize_features(device, x.ctypes.data_as(_fp), ct.c_long(x.shape[0]), D, ct.c_long(len(sps)), sps.ctypes.data_as(_lp),
+                                           off.ctypes.data_as(_lp), b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), C, _d(w), _d(mean), _d(cov),
+                                           V.shape[0], U.shape[0], _d(V), _d(U), _d(Dm), _d(Y), _d(X), _d(Z), _d(ux), _d(models)))
+    return x, ux, models
+
+
+def feature_mapping(x, cluster, cd, ci, device=0):
+    """liagpu::featureMapping on float32 frames over one cluster [(begin, length), ...]; cd / ci = (w, mean, cov) -> mapped frames."""
+    x = np.array(x, np.float32)
+    wd, md, vd = [np.ascontiguousarray(a, np.float64) for a in cd]
+    wi, mi, vi = [np.ascontiguousarray(a, np.float64) for a in ci]
+    C, D = md.shape
+    _, b, l = _clusters([cluster])
+    _chk(lib.liagpu_feature_mapping(device, x.ctypes.data_as(_fp), ct.c_long(x.shape[0]), D, b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), ct.c_long(len(b)),
+                                    C, _d(wd), _d(md), _d(vd), _d(wi), _d(mi), _d(vi)))
+    return x
+
+
 def compute_test_files(world_path, client_paths, client_names, prm_path, lbl_path, mask="", label="male", frame_length=0.01,
                        top_c=10, complete=True, min_llk=-200.0, max_llk=200.0, gender="M", test_name="test", threshold=0.0,
                        device=0):
