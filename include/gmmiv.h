@@ -176,6 +176,10 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  *                                 "zero_llk_frames" (the reference divides 0 by 0 there); kind (1) also in "screened_frames"
  *   gmmiv_feat_map                NOT screened: best = 0 on a frame whose every term is 0 (the reference's loop leaves idx = 0), the
  *                                 raw values go through the map of that Gaussian -- a NaN stays a NaN
+ *   gmmiv_frame_moments_groups    NOT screened: like gmmiv_frame_moments, a NaN goes into the sums of its group
+ *   gmmiv_feat_norm_apply         NOT screened: (x - mean) / std of the raw value; std = 0 gives Inf / NaN like computeZeroOne
+ *   gmmiv_feat_norm_online        NOT screened: a NaN / Inf frame poisons the running mean and std of its file from there on, like
+ *                                 the tool's (1 - B) * f[i]; a running std of 0 gives Inf / NaN
  * Frames of kind (1) are handled ON THE DEVICE, inside the kernels: every kernel that reads features reads an unusable value as 1e10
  * (csrc/devutil.h, feat_sane: one compare + select where the value is loaded -- in the MFMA log-likelihood kernel once per frame and
  * workgroup, outside its loop).  The value is finite, so no 0 x NaN reaches a statistic, and it puts every logit of the frame near
@@ -226,6 +230,50 @@ int gmmiv_gather_runs(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, i
  * arrays, runs host or device (a device table only enqueues), pieces of <= 64 frames, runs must not overlap in x.  Frames outside
  * the runs are not touched. */
 int gmmiv_scatter_runs(gmmiv_ctx *ctx, void *x, int x_dtype, int64_t ldx, int D, const int64_t *runs, int64_t nrun, const void *in);
+
+/* ---- cepstral mean / variance normalisation on resident frames: NormFeat's default mode (normFeat(), NormFeat.cpp:231-518) and the
+ * online mode of NormFeatWindowMode (normFeatOnlineMode, NormFeatWindowMode.cpp:165-311) -------------------------------------------
+ * x and out are DEVICE arrays (like gmmiv_gather_runs); every other array is host or device, and with device pointers throughout
+ * every call only enqueues on the context's stream.  x_dtype / out_dtype: GMMIV_F32 or GMMIV_F64 independently; arithmetic is fp64,
+ * an f32 output is rounded once.  No result is accumulated with atomics: every value is bitwise reproducible and does not depend on
+ * what else shares the call.  nrun = 0, nfiles = 0 and files / runs without frames are valid.
+ *
+ * RUN TABLE: runs[3 r + 0 .. 2] = (first frame, length, group).  Group ids are non-decreasing along the table and lie in
+ * [0, ngroups); a group may have no run.  A HOST table that breaks this is GMMIV_ERR_ARG before anything is enqueued; a DEVICE
+ * table is not checked.  A run may have any length, but one run is one unit of work (one workgroup): the caller cuts long runs
+ * (the host layer cuts at 4096 frames), as with gmmiv_gather_runs.
+ *
+ * gmmiv_frame_moments_groups: acc[g * (2 D + 1) + ...] += (sum x [D], sum x^2 [D], n) over the frames of group g's runs -- the layout of
+ * gmmiv_frame_moments per group, accumulateStatFrame over a Seg (segmental mode, NormFeat.cpp:352-356) or over a cluster (file mode,
+ * :455-459).  Order: the partial sums of a run depend on its LENGTH alone (16 interleaved row sums, each left to right, added in
+ * order), a group's total is its runs' partials added in table order, and that total is added to acc once.  n is exact.
+ * gmmiv_frame_moments_stats: mean = s / n, std = sqrt(ss / n - mean mean), [ngroups x D] each: FrameAccGD::getMeanVect / getStdVect,
+ * biased, every operation rounded on its own (the form KAT-4 pins).  n = 0 gives NaN in both.
+ * gmmiv_feat_norm_apply: out[t][i] = (x[t][i] - mean[g][i]) / std[g][i] on the frames of the runs -- computeZeroOne
+ * (GeneralTools.cpp:670-682), one subtraction and one true division.  mean == NULL: nothing is subtracted (varOnly; the reference
+ * subtracts 0.0), std == NULL: nothing is divided (cmsOnly; the reference divides by 1.0).  out may be exactly x (same pointer, dtype
+ * and stride); any other overlap of the two frame ranges is GMMIV_ERR_ARG (the rule of gmmiv_feat_compensate; with a device table only
+ * out == x with another dtype or stride can be seen and is refused).  Frames outside the runs and columns >= D of a row are not
+ * touched; a column slice is a pointer offset (x + 16, D = 1, ldx = 34: the energy pass of the recipe).
+ *
+ * gmmiv_feat_norm_online: per file f = frames [file_begin[f], file_begin[f + 1]) of n frames, with W = window >= 1 and
+ * L = min(look_ahead, W) >= 0: the state (m, c) starts as the FrameAccGD mean / biased std of W - L zero vectors followed by the first L
+ * frames (:243-270; n < L: the window shrinks to W' = W - L + n -- zeros and the whole file -- and W' replaces W below, :256-262; L = 0
+ * is the tool without initWithDelay, state 0).  Then for frame k = 1 .. n:  B = 1 if k < L else (W - 1) / W;  m <- B m + (1 - B) x;
+ * c <- sqrt(c c B + (1 - B) (x x));  out = (x - m) / c with the UPDATED m, c (:114-137, :285-296).  Two quirks of the tool are kept:
+ * frame k = L is folded in a second time, and c blends raw second moments, not variances.  One is NOT: in the tool a shrunken
+ * window length stays in force for the following files of the list; here every file starts from the caller's W, so a file's result
+ * never depends on its neighbours.  The recurrences are linear in m and c c and run as a chunked scan (chunks of 1024 frames counted
+ * from the file's first frame; one chain per chunk and dimension), within W' 2^-53 (max|x| / c + |out|) of the sequential loop.
+ * With a device file_begin the scratch of the scan is sized from the allocation that holds x.  Same overlap rule as above.
+ * Kernel timers: "k_moments_groups", "k_moments_stats", "k_feat_norm_apply", "k_feat_norm_online". */
+int gmmiv_frame_moments_groups(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, int D, const int64_t *runs, int64_t nrun,
+                               int64_t ngroups, double *acc);
+int gmmiv_frame_moments_stats(gmmiv_ctx *ctx, int64_t ngroups, int D, const double *acc, double *mean, double *std);
+int gmmiv_feat_norm_apply(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, int D, const int64_t *runs, int64_t nrun, int64_t ngroups,
+                          const double *mean /* nullable */, const double *std /* nullable */, void *out, int out_dtype, int64_t ldo);
+int gmmiv_feat_norm_online(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, int D, const int64_t *file_begin, int64_t nfiles,
+                           int64_t window, int64_t look_ahead, void *out, int out_dtype, int64_t ldo);
 
 /* ---- segment means of per-frame values (ComputeTest's score per segment, ComputeTest.cpp:181-199) ------
  * out[r * nseg + s] = mean of v[r * ld + t], t in [seg_begin[s], seg_begin[s+1])  (0 for an empty segment).

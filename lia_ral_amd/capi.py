@@ -249,6 +249,67 @@ class Context:
         _chk(lib.gmmiv_scatter_runs(self._h, _ptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(r), ct.c_int64(r.shape[0]), _ptr(inp)))
         return x
 
+    # ---- NormFeat's default mode and NormFeatWindowMode's online mode (x, out: torch device frame matrices, column slices allowed)
+    @staticmethod
+    def _tab(a):
+        return a if a is None or _is_torch(a) else np.ascontiguousarray(a, np.int64)
+
+    def frame_moments_groups(self, x, runs, ngroups, acc=None):
+        """acc[g] += (sum x, sum x^2, n) over the runs of group g; runs [nrun, 3] int64 (first frame, length, group), group ids
+        non-decreasing, host or device; acc [ngroups, 2 D + 1] float64 (numpy, or torch device), accumulated into."""
+        x, dt, T, ldx = _feat_view(x)
+        D = x.shape[1]
+        r = self._tab(runs)
+        if acc is None:
+            acc = np.zeros((ngroups, 2 * D + 1))
+        _chk(lib.gmmiv_frame_moments_groups(self._h, _vptr(x), dt, ct.c_int64(ldx), D, _ptr(r), ct.c_int64(r.shape[0]), ct.c_int64(ngroups), _ptr(acc)))
+        return acc
+
+    def frame_moments_stats(self, acc, D, mean=None, std=None):
+        """FrameAccGD mean / biased std of every group of acc [ngroups, 2 D + 1] -> (mean, std) [ngroups, D] (of acc's kind)."""
+        ngroups = acc.shape[0]
+        if mean is None or std is None:
+            if _is_torch(acc):
+                import torch
+                mean, std = torch.empty((ngroups, D), dtype=torch.float64, device=acc.device), torch.empty((ngroups, D), dtype=torch.float64, device=acc.device)
+            else:
+                mean, std = np.empty((ngroups, D)), np.empty((ngroups, D))
+        a = acc if _is_torch(acc) else np.ascontiguousarray(acc, np.float64)
+        _chk(lib.gmmiv_frame_moments_stats(self._h, ct.c_int64(ngroups), D, _ptr(a), _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def feat_norm_apply(self, x, runs, mean, std, out=None, out_dtype=None, ngroups=None):
+        """out = (x - mean[g]) / std[g] on the frames of the runs (computeZeroOne); mean / std [ngroups, D] float64 or None (no subtraction
+        / no division); out=None allocates a matrix of out_dtype (default: x's; rows outside the runs are left unset), out=x is in place."""
+        x, dt, T, ldx = _feat_view(x)
+        D = x.shape[1]
+        if out is None:
+            out = _feat_like(x, dt if out_dtype is None else out_dtype)
+        out, odt, To, ldo = _feat_view(out)
+        assert out.shape[1] == D
+        r = self._tab(runs)
+        m = mean if mean is None or _is_torch(mean) else np.ascontiguousarray(mean, np.float64)
+        s = std if std is None or _is_torch(std) else np.ascontiguousarray(std, np.float64)
+        if ngroups is None:
+            assert m is not None or s is not None, "feat_norm_apply: ngroups is needed when mean and std are both None"
+            ngroups = (m if m is not None else s).shape[0]
+        _chk(lib.gmmiv_feat_norm_apply(self._h, _vptr(x), dt, ct.c_int64(ldx), D, _ptr(r), ct.c_int64(r.shape[0]), ct.c_int64(ngroups), _ptr(m), _ptr(s),
+                                       _vptr(out), odt, ct.c_int64(ldo)))
+        return out
+
+    def feat_norm_online(self, x, file_begin, window=300, look_ahead=0, out=None, out_dtype=None):
+        """normFeatOnlineMode per file [file_begin[f], file_begin[f + 1]): running mean / std with the forgetting factor (W - 1) / W,
+        initialised from W - L zeros and the first L = min(look_ahead, window) frames.  file_begin: nfiles + 1 int64, host or device."""
+        x, dt, T, ldx = _feat_view(x)
+        if out is None:
+            out = _feat_like(x, dt if out_dtype is None else out_dtype)
+        out, odt, To, ldo = _feat_view(out)
+        assert out.shape[1] == x.shape[1]
+        fb = self._tab(file_begin)
+        _chk(lib.gmmiv_feat_norm_online(self._h, _vptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(fb), ct.c_int64(fb.shape[0] - 1), ct.c_int64(window),
+                                        ct.c_int64(look_ahead), _vptr(out), odt, ct.c_int64(ldo)))
+        return out
+
     def segment_means(self, v, seg_begin, out=None):
         """v: torch CUDA float64 [nrows, ld] (or 1-D); seg_begin: nseg + 1 host offsets -> out [nrows, nseg]."""
         v2 = v if v.dim() == 2 else v.reshape(1, -1)

@@ -1451,4 +1451,148 @@ int gmmiv_scatter_runs(gmmiv_ctx *c, void *x, int dt, int64_t ldx, int D, const 
     return GMMIV_OK;
 }
 
+// ---- cepstral mean / variance normalisation: NormFeat's default mode and NormFeatWindowMode's online mode ---------------------------
+// A HOST run table is validated before anything is enqueued (a device table is not read here): lengths >= 0, group ids non-decreasing
+// and inside [0, ngroups).  lo / hi (nullable): the frame range the runs cover.
+static int norm_check_runs(const char *who, const int64_t *runs, int64_t nrun, int64_t ngroups, int64_t *lo, int64_t *hi)
+{
+    int64_t prev = 0, a = INT64_MAX, b = 0;
+    for (int64_t r = 0; r < nrun; ++r) {
+        const int64_t first = runs[3 * r], len = runs[3 * r + 1], g = runs[3 * r + 2];
+        if (first < 0 || len < 0) { gmmiv_set_error("%s: run %ld has a negative first frame or length", who, (long)r); return GMMIV_ERR_ARG; }
+        if (g < prev || g >= ngroups) { gmmiv_set_error("%s: run %ld: group %ld is below its predecessor's or outside [0, %ld) (group ids must be non-decreasing)", who, (long)r, (long)g, (long)ngroups); return GMMIV_ERR_ARG; }
+        prev = g;
+        if (len > 0) { if (first < a) a = first; if (first + len > b) b = first + len; }
+    }
+    if (lo) *lo = a == INT64_MAX ? 0 : a;
+    if (hi) *hi = b;
+    return GMMIV_OK;
+}
+// frames [lo, hi) of x and out: out may be exactly x (pointer, dtype, stride), any other overlap is refused (the rule of feat_check)
+static int norm_check_overlap(const char *who, const void *x, int xdt, int64_t ldx, const void *out, int odt, int64_t ldo, int D, int64_t lo, int64_t hi)
+{
+    const bool in_place = x == out && xdt == odt && ldx == ldo;
+    if (in_place || hi <= lo) return GMMIV_OK;
+    const uintptr_t xb = (uintptr_t)x + (size_t)lo * ldx * esize(xdt), xe = (uintptr_t)x + ((size_t)(hi - 1) * ldx + D) * esize(xdt);
+    const uintptr_t ob = (uintptr_t)out + (size_t)lo * ldo * esize(odt), oe = (uintptr_t)out + ((size_t)(hi - 1) * ldo + D) * esize(odt);
+    if (xb < oe && ob < xe) { gmmiv_set_error("%s: out overlaps x (only out == x with the same dtype and stride is allowed)", who); return GMMIV_ERR_ARG; }
+    return GMMIV_OK;
+}
+
+int gmmiv_frame_moments_groups(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int D, const int64_t *runs, int64_t nrun, int64_t ngroups,
+                               double *acc)
+{
+    if (dt != GMMIV_F32 && dt != GMMIV_F64) { gmmiv_set_error("frame_moments_groups: x_dtype must be GMMIV_F32 or GMMIV_F64"); return GMMIV_ERR_ARG; }
+    if (nrun < 0 || ngroups < 0 || D <= 0 || ldx < D || (!runs && nrun > 0)) { gmmiv_set_error("frame_moments_groups: bad argument (nrun, ngroups < 0, D <= 0, ldx < D or runs == NULL)"); return GMMIV_ERR_ARG; }
+    const bool host_runs = nrun > 0 && !gmmiv_is_device_ptr(runs);
+    int rc;
+    if (host_runs && (rc = norm_check_runs("frame_moments_groups", runs, nrun, ngroups, nullptr, nullptr))) return rc;
+    if (!c) { gmmiv_set_error("frame_moments_groups: NULL context"); return GMMIV_ERR_ARG; }
+    if (nrun == 0 || ngroups == 0) return GMMIV_OK;
+    if (!acc || !x) { gmmiv_set_error("frame_moments_groups: x or acc == NULL"); return GMMIV_ERR_ARG; }
+    if (!gmmiv_is_device_ptr(x)) { gmmiv_set_error("frame_moments_groups: x must be a device array"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    DevIn<int64_t> i_runs;
+    if ((rc = i_runs.init(c, WS_T0, runs, (size_t)nrun * 3))) return rc;
+    DevOut<double> o;
+    if ((rc = o.init(c, WS_T1, acc, (size_t)ngroups * (2 * D + 1), true))) return rc;
+    void *part;
+    if ((rc = c->scratch(WS_PART, (size_t)nrun * 2 * D * sizeof(double), &part))) return rc;
+    c->t_begin("k_moments_groups");
+    GCHK(gmmk_moments_groups(c->stream, dt == GMMIV_F64, x, ldx, D, (const long *)i_runs.d, nrun, ngroups, (double *)part, o.d));
+    c->t_end();
+    if ((rc = o.finish())) return rc;
+    if (host_runs && !o.host) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
+    return GMMIV_OK;
+}
+
+int gmmiv_frame_moments_stats(gmmiv_ctx *c, int64_t ngroups, int D, const double *acc, double *mean, double *std)
+{
+    if (!c) { gmmiv_set_error("frame_moments_stats: NULL context"); return GMMIV_ERR_ARG; }
+    if (ngroups < 0 || D <= 0) { gmmiv_set_error("frame_moments_stats: ngroups < 0 or D <= 0"); return GMMIV_ERR_ARG; }
+    if (ngroups == 0) return GMMIV_OK;
+    if (!acc || !mean || !std) { gmmiv_set_error("frame_moments_stats: acc, mean or std == NULL"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    int rc;
+    DevIn<double> i_acc;
+    if ((rc = i_acc.init(c, WS_T1, acc, (size_t)ngroups * (2 * D + 1)))) return rc;
+    DevOut<double> om, os;
+    if ((rc = om.init(c, WS_FEAT_M0, mean, (size_t)ngroups * D, false)) || (rc = os.init(c, WS_FEAT_M1, std, (size_t)ngroups * D, false))) return rc;
+    c->t_begin("k_moments_stats");
+    GCHK(gmmk_moments_stats(c->stream, ngroups, D, i_acc.d, om.d, os.d));
+    c->t_end();
+    if ((rc = om.finish()) || (rc = os.finish())) return rc;
+    if (!gmmiv_is_device_ptr(acc) && !om.host && !os.host) GCHK(hipStreamSynchronize(c->stream)); // the host accumulator may be freed
+    return GMMIV_OK;
+}
+
+int gmmiv_feat_norm_apply(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int D, const int64_t *runs, int64_t nrun, int64_t ngroups,
+                          const double *mean, const double *std, void *out, int odt, int64_t ldo)
+{
+    int rc = feat_check_dtype("feat_norm_apply", dt, odt);
+    if (rc) return rc;
+    if (nrun < 0 || ngroups < 0 || D <= 0 || ldx < D || ldo < D || (!runs && nrun > 0)) { gmmiv_set_error("feat_norm_apply: bad argument (nrun, ngroups < 0, D <= 0, a row stride below D or runs == NULL)"); return GMMIV_ERR_ARG; }
+    const bool host_runs = nrun > 0 && !gmmiv_is_device_ptr(runs);
+    int64_t lo = 0, hi = 0;
+    if (host_runs && (rc = norm_check_runs("feat_norm_apply", runs, nrun, ngroups, &lo, &hi))) return rc;
+    if (!c) { gmmiv_set_error("feat_norm_apply: NULL context"); return GMMIV_ERR_ARG; }
+    if (nrun == 0) return GMMIV_OK;
+    if (!x || !out) { gmmiv_set_error("feat_norm_apply: x or out == NULL"); return GMMIV_ERR_ARG; }
+    if (x == out && (dt != odt || ldx != ldo)) { gmmiv_set_error("feat_norm_apply: out overlaps x (only out == x with the same dtype and stride is allowed)"); return GMMIV_ERR_ARG; }
+    if (host_runs && (rc = norm_check_overlap("feat_norm_apply", x, dt, ldx, out, odt, ldo, D, lo, hi))) return rc;
+    if (!gmmiv_is_device_ptr(x) || !gmmiv_is_device_ptr(out)) { gmmiv_set_error("feat_norm_apply: x and out must be device arrays"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    DevIn<int64_t> i_runs;
+    if ((rc = i_runs.init(c, WS_T0, runs, (size_t)nrun * 3))) return rc;
+    DevIn<double> i_mean, i_std;
+    if ((rc = i_mean.init(c, WS_FEAT_M0, mean, (size_t)ngroups * D)) || (rc = i_std.init(c, WS_FEAT_M1, std, (size_t)ngroups * D))) return rc;
+    c->t_begin("k_feat_norm_apply");
+    GCHK(gmmk_feat_norm_apply(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, x, ldx, D, (const long *)i_runs.d, nrun, ngroups, i_mean.d, i_std.d, out, ldo));
+    c->t_end();
+    if (host_runs || (mean && !gmmiv_is_device_ptr(mean)) || (std && !gmmiv_is_device_ptr(std))) GCHK(hipStreamSynchronize(c->stream)); // host arrays may be freed
+    return GMMIV_OK;
+}
+
+int gmmiv_feat_norm_online(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int D, const int64_t *file_begin, int64_t nfiles, int64_t window,
+                           int64_t look_ahead, void *out, int odt, int64_t ldo)
+{
+    int rc = feat_check_dtype("feat_norm_online", dt, odt);
+    if (rc) return rc;
+    if (nfiles < 0 || D <= 0 || ldx < D || ldo < D || window < 1 || look_ahead < 0 || (!file_begin && nfiles > 0)) { gmmiv_set_error("feat_norm_online: bad argument (nfiles < 0, D <= 0, a row stride below D, window < 1, look_ahead < 0 or file_begin == NULL)"); return GMMIV_ERR_ARG; }
+    const bool host_tab = nfiles > 0 && !gmmiv_is_device_ptr(file_begin);
+    if (host_tab)
+        for (int64_t f = 0; f < nfiles; ++f)
+            if (file_begin[f] < 0 || file_begin[f + 1] < file_begin[f]) { gmmiv_set_error("feat_norm_online: file_begin must be non-negative and non-decreasing (file %ld)", (long)f); return GMMIV_ERR_ARG; }
+    if (!c) { gmmiv_set_error("feat_norm_online: NULL context"); return GMMIV_ERR_ARG; }
+    if (nfiles == 0 || (host_tab && file_begin[nfiles] == file_begin[0])) return GMMIV_OK;
+    if (!x || !out) { gmmiv_set_error("feat_norm_online: x or out == NULL"); return GMMIV_ERR_ARG; }
+    if (x == out && (dt != odt || ldx != ldo)) { gmmiv_set_error("feat_norm_online: out overlaps x (only out == x with the same dtype and stride is allowed)"); return GMMIV_ERR_ARG; }
+    if (host_tab && (rc = norm_check_overlap("feat_norm_online", x, dt, ldx, out, odt, ldo, D, file_begin[0], file_begin[nfiles]))) return rc;
+    if (!gmmiv_is_device_ptr(x) || !gmmiv_is_device_ptr(out)) { gmmiv_set_error("feat_norm_online: x and out must be device arrays"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    // The scan's scratch is sized by the number of chunks.  A host table gives it; with a device table (never read back: the call only
+    // enqueues) the frames that fit between x and the end of its allocation bound it.
+    int64_t frames;
+    if (host_tab) frames = file_begin[nfiles] - file_begin[0];
+    else {
+        void *base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)x) != hipSuccess) { (void)hipGetLastError(); gmmiv_set_error("feat_norm_online: the allocation of x is unknown to the runtime; pass file_begin as a host array"); return GMMIV_ERR_ARG; }
+        frames = (int64_t)(((uintptr_t)base + size - (uintptr_t)x) / ((size_t)ldx * esize(dt))) + 1;
+    }
+    const long L = (long)(look_ahead < window ? look_ahead : window);
+    const size_t units = gmmk_online_units((long)nfiles, (long)frames);
+    DevIn<int64_t> i_fb;
+    if ((rc = i_fb.init(c, WS_T0, file_begin, (size_t)nfiles + 1))) return rc;
+    void *off, *state, *decay;
+    if ((rc = c->scratch(WS_NORM_OFF, ((size_t)nfiles + 1) * sizeof(int64_t), &off)) || (rc = c->scratch(WS_NORM_STATE, units * D * 2 * sizeof(double), &state)) ||
+        (rc = c->scratch(WS_NORM_DECAY, units * sizeof(double), &decay))) return rc;
+    c->t_begin("k_feat_norm_online");
+    GCHK(gmmk_feat_norm_online(c->stream, c->n_cu, dt == GMMIV_F64, odt == GMMIV_F64, x, ldx, D, (const long *)i_fb.d, (long)nfiles, (long)window, L, (long)units,
+                               (long *)off, (double *)state, (double *)decay, out, ldo));
+    c->t_end();
+    if (host_tab) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
+    return GMMIV_OK;
+}
+
 } // extern "C"

@@ -35,8 +35,10 @@ void gmmiv_set_error(const char *fmt, ...);
 enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, WS_T4, WS_T5, WS_T6, WS_T7, WS_T8,
        WS_T9, WS_TIV, WS_LP, WS_AUX, WS_SLAB, WS_SLOTS, WS_FLAGS, WS_Z, WS_EIT, WS_INV,
        WS_GFLAG, WS_NORM, WS_FEAT_OFF, WS_FEAT_OUT, WS_FEAT_IDX, WS_FEAT_M0, WS_FEAT_M1, WS_FEAT_M2, WS_FEAT_M3,
+       WS_NORM_OFF, WS_NORM_STATE, WS_NORM_DECAY,
        WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask;
-                   // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables)
+                   // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables);
+                   // WS_NORM_*: gmmiv_feat_norm_online (chunk offsets of the files, the carried states, the chunks' decay products)
 
 struct gmmiv_ctx {
     int device = 0;

@@ -104,3 +104,14 @@ int gmmk_feat_sub(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx,
 int gmmk_feat_map(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long T, int D, int C, const int *best, const double *cd_mean,
                   const double *cd_cov, const double *ci_mean, const double *ci_cov, void *out, long ldo);
 int gmmk_scatter_runs(hipStream_t st, int x_f64, void *x, long ldx, int D, const long *runs, long nrun, const void *in);
+
+// feat_norm.hip: NormFeat's default mode (moments per group, mean / std, computeZeroOne) and the online mode of NormFeatWindowMode
+int gmmk_moments_groups(hipStream_t st, int x_f64, const void *x, long ldx, int D, const long *runs, long nrun, long ngroups, double *partial,
+                        double *acc); // partial: [nrun x 2D] scratch
+int gmmk_moments_stats(hipStream_t st, long ngroups, int D, const double *acc, double *mean, double *sd);
+int gmmk_feat_norm_apply(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, int D, const long *runs, long nrun, long ngroups,
+                         const double *mean, const double *sd, void *out, long ldo); // mean / sd nullable
+size_t gmmk_online_units(long nfiles, long frames); // upper bound of the chunks of nfiles files with `frames` frames together
+long gmmk_online_chunk(void);
+int gmmk_feat_norm_online(hipStream_t st, int n_cu, int x_f64, int o_f64, const void *x, long ldx, int D, const long *file_begin, long nfiles,
+                          long W, long L, long max_units, long *chunk_off, double *state, double *decay, void *out, long ldo);

@@ -981,6 +981,58 @@ int liagpu_feature_mapping(int device, float *x, long T, int D, const long *seg_
     })
 }
 
+// liagpu::normFeat on the frames x [T x D] (rewritten in place): source s = frames [src_first[s], src_first[s + 1]) (src_first has
+// nsrc + 1 entries), its cluster the segments clu_off[s] .. clu_off[s + 1] of (seg_begin, seg_len), begins counted from the source's
+// first frame.  ext_mean / ext_std: NULL or [ncols] (ncols = 0: all columns from first_col).
+int liagpu_norm_feat(int device, float *x, long T, int D, long nsrc, const long *src_first, const long *clu_off, const long *seg_begin,
+                     const long *seg_len, int segmentalMode, int fileMode, int cmsOnly, int varOnly, const double *ext_mean, const double *ext_std,
+                     int first_col, int ncols)
+{
+    GUARD({
+        GpuServer srv(device);
+        std::vector<unsigned long> first(src_first, src_first + nsrc);
+        if (nsrc < 1 || src_first[nsrc] != T) throw Exception("norm_feat: src_first must end at the frame count");
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D, first);
+        NormFeatCfg cfg;
+        cfg.segmentalMode = segmentalMode != 0; cfg.fileMode = fileMode != 0; cfg.cmsOnly = cmsOnly != 0; cfg.varOnly = varOnly != 0;
+        const int nc = ncols ? ncols : D - first_col;
+        if (ext_mean && ext_std) { cfg.extMean.assign(ext_mean, ext_mean + nc); cfg.extStd.assign(ext_std, ext_std + nc); }
+        normFeat(fs, clusters_from(clu_off, nsrc, seg_begin, seg_len), cfg, (unsigned long)first_col, (unsigned long)ncols);
+        fs.download(x);
+    })
+}
+
+// liagpu::normFeatOnlineMode on the frames x [T x D] (rewritten in place), sources as above
+int liagpu_norm_feat_online(int device, float *x, long T, int D, long nsrc, const long *src_first, long windowDuration, long initWithDelay)
+{
+    GUARD({
+        GpuServer srv(device);
+        std::vector<unsigned long> first(src_first, src_first + nsrc);
+        if (nsrc < 1 || src_first[nsrc] != T) throw Exception("norm_feat_online: src_first must end at the frame count");
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D, first);
+        normFeatOnlineMode(fs, windowDuration, initWithDelay);
+        fs.download(x);
+    })
+}
+
+// liagpu::normFeatFiles: names [n] are joined with the paths / extensions like the reference's FeatureServer does
+int liagpu_norm_feat_files(int device, int n, const char **names, const char *feature_path, const char *load_ext, const char *save_path,
+                           const char *save_ext, const char *label_path, const char *label_ext, const char *label, double frameLength,
+                           const char *mask, int writeAllFeatures, int segmentalMode, int fileMode, int cmsOnly, int varOnly)
+{
+    GUARD({
+        GpuServer srv(device);
+        NormFeatFilesCfg cfg;
+        cfg.norm.segmentalMode = segmentalMode != 0; cfg.norm.fileMode = fileMode != 0; cfg.norm.cmsOnly = cmsOnly != 0; cfg.norm.varOnly = varOnly != 0;
+        cfg.featureFilesPath = feature_path ? feature_path : ""; cfg.loadFeatureFileExtension = load_ext ? load_ext : "";
+        cfg.saveFeatureFilePath = save_path ? save_path : ""; cfg.saveFeatureFileExtension = save_ext ? save_ext : "";
+        cfg.labelFilesPath = label_path ? label_path : ""; cfg.labelFilesExtension = label_ext ? label_ext : "";
+        cfg.labelSelectedFrames = label ? label : ""; cfg.frameLength = frameLength; cfg.featureServerMask = mask ? mask : "";
+        cfg.writeAllFeatures = writeAllFeatures != 0;
+        normFeatFiles(srv, std::vector<std::string>(names, names + n), cfg);
+    })
+}
+
 // ComputeTest from FILES for one ndx line (test file + client list): RAW models, .prm features with
 // featureServerMask, .lbl selection.  Writes the NIST-style result lines (segmental mode) into out_text
 // and the LLRs into llr_out[nseg x nClients].  ComputeTest.cpp:129-215 + the format readers of io.h.

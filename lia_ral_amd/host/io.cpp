@@ -489,4 +489,68 @@ void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg)
     computeNormFiles(srv, cfg, t);
 }
 
+// ---- NormFeat from files ------------------------------------------------------------------------------
+void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const NormFeatFilesCfg &cfg)
+{
+    if (names.empty()) return;
+    std::vector<FeatureFile> files;
+    std::vector<unsigned long> first;
+    std::vector<SegCluster> clusters;
+    unsigned long total = 0, dim = 0;
+    for (size_t k = 0; k < names.size(); ++k) {
+        files.push_back(readFeatureFile(cfg.featureFilesPath + names[k] + cfg.loadFeatureFileExtension));
+        const FeatureFile &f = files.back();
+        if (f.nFrames) {
+            if (dim && f.vectSize != dim) throw Exception("normFeatFiles: [" + names[k] + "] has another dimension than the files before it");
+            dim = f.vectSize;
+        }
+        first.push_back(total);
+        total += f.nFrames;
+        SegCluster c;
+        if (cfg.labelFilesExtension.empty()) { Seg all; all.begin = 0; all.length = f.nFrames; all.source = k; if (f.nFrames) c.push_back(all); }
+        else c = selectSegments(readLabelFile(cfg.labelFilesPath + names[k] + cfg.labelFilesExtension), cfg.labelSelectedFrames, cfg.frameLength, k);
+        for (const Seg &g : c)
+            if (g.begin + g.length > f.nFrames) throw Exception("normFeatFiles: a segment of [" + names[k] + "] ends after the last frame of the file");
+        clusters.push_back(c);
+    }
+    if (!dim) throw Exception("normFeatFiles: no frames");
+    std::vector<int> cols = parseFeatureMask(cfg.featureServerMask);
+    if (cols.empty()) for (unsigned long c = 0; c < dim; ++c) cols.push_back((int)c);
+    for (int c : cols) if ((unsigned long)c >= dim) throw Exception("featureServerMask selects a column beyond vectSize");
+    std::vector<float> all((size_t)total * dim);
+    for (size_t k = 0; k < files.size(); ++k)
+        if (files[k].nFrames) memcpy(all.data() + (size_t)first[k] * dim, files[k].data.data(), files[k].data.size() * sizeof(float));
+    {
+        FeatureBuffer fs(srv, all.data(), total, dim, first);
+        size_t done = 0;                                       // offset into the external vectors: they follow the mask's order
+        for (size_t a = 0; a < cols.size();) {                 // one call per contiguous piece of the mask
+            size_t b = a + 1;
+            while (b < cols.size() && cols[b] == cols[b - 1] + 1) ++b;
+            NormFeatCfg nc = cfg.norm;
+            if (!nc.extMean.empty()) {
+                if (nc.extMean.size() != cols.size() || nc.extStd.size() != cols.size()) throw Exception("normFeatFiles: external mean / std must have one value per masked column");
+                nc.extMean.assign(cfg.norm.extMean.begin() + done, cfg.norm.extMean.begin() + done + (b - a));
+                nc.extStd.assign(cfg.norm.extStd.begin() + done, cfg.norm.extStd.begin() + done + (b - a));
+            }
+            normFeat(fs, clusters, nc, (unsigned long)cols[a], (unsigned long)(b - a));
+            done += b - a;
+            a = b;
+        }
+        fs.download(all.data());
+    }
+    for (size_t k = 0; k < files.size(); ++k) {
+        FeatureFile out;
+        out.vectSize = cols.size(); out.baseDim = (unsigned)cols.size(); out.flags = files[k].flags;
+        auto put = [&](unsigned long t) {
+            const float *row = all.data() + (size_t)(first[k] + t) * dim;
+            for (int c : cols) out.data.push_back(row[c]);
+            ++out.nFrames;
+        };
+        if (cfg.writeAllFeatures) for (unsigned long t = 0; t < files[k].nFrames; ++t) put(t);
+        else for (const Seg &g : clusters[k]) for (unsigned long t = 0; t < g.length; ++t) put(g.begin + t);
+        if (cols.size() == dim) out.baseDim = files[k].baseDim;  // nothing masked: the header goes through unchanged
+        writeFeatureFile((cfg.saveFeatureFilePath.empty() ? cfg.featureFilesPath : cfg.saveFeatureFilePath) + names[k] + cfg.saveFeatureFileExtension, out);
+    }
+}
+
 } // namespace liagpu

@@ -101,4 +101,19 @@ void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNor
 void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg);
 
 
+// NormFeat driven by files (NormFeat.cpp:302-509): every feature file <featureFilesPath><name><loadFeatureFileExtension> of the list is
+// loaded at its full width into ONE resident buffer (the files must share their dimension), the clusters come from
+// <labelFilesPath><name><labelFilesExtension> (labelFilesExtension "": no label files, every frame is selected), liagpu::normFeat runs
+// once on the whole batch -- on the columns of featureServerMask: a contiguous mask is one column slice, a non-contiguous one a call per
+// contiguous piece -- and <saveFeatureFilePath><name><saveFeatureFileExtension> receives the masked columns of all frames
+// (writeAllFeatures, :489-495) or of the selected frames only, in cluster order (:497-498).
+struct NormFeatFilesCfg {
+    NormFeatCfg norm;
+    std::string featureFilesPath, loadFeatureFileExtension = ".prm", saveFeatureFilePath, saveFeatureFileExtension = ".norm.prm";
+    std::string labelFilesPath, labelFilesExtension = ".lbl", labelSelectedFrames = "speech", featureServerMask;
+    double frameLength = 0.01;
+    bool writeAllFeatures = true;
+};
+void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const NormFeatFilesCfg &cfg);
+
 } // namespace liagpu

@@ -964,6 +964,95 @@ double TopGauss::compute(DeviceMixture &ubm, FeatureBuffer &fs, const SegCluster
     return n ? s / (double)n : 0.0;
 }
 
+// ---- NormFeat ----------------------------------------------------------------------------------------
+namespace {
+// one pass of normFeat: groups of runs -> moments -> mean / std -> computeZeroOne, three enqueues (the table upload is a fourth copy)
+void normFeatPass(FeatureBuffer &fs, const std::vector<int64_t> &runs, int64_t ngroups, const NormFeatCfg &cfg, unsigned long firstCol, int D)
+{
+    const int64_t nrun = (int64_t)(runs.size() / 3);
+    if (nrun == 0 || ngroups == 0) return;
+    GpuServer &srv = fs.server();
+    hipStream_t st = (hipStream_t)srv.stream();
+    const int64_t ld = (int64_t)fs.getVectSize();
+    float *x = fs.mutableDevice() + firstCol;
+    const bool ext = !cfg.extMean.empty();
+    const int64_t ng = ext ? 1 : ngroups;                            // external statistics: one row for every group
+    const size_t W = 2 * (size_t)D + 1, nacc = ext ? 0 : (size_t)ng * W, nstat = (size_t)ng * D;
+    int64_t *dRuns = (int64_t *)srv.workspace(3, runs.size() * sizeof(int64_t));
+    double *buf = (double *)srv.workspace(4, (nacc + 2 * nstat) * sizeof(double));
+    double *acc = buf, *mean = buf + nacc, *sd = mean + nstat;
+    std::vector<int64_t> tab;
+    const int64_t *src = runs.data();
+    if (ext) {                                                       // every run reads row 0
+        tab = runs;
+        for (int64_t r = 0; r < nrun; ++r) tab[3 * r + 2] = 0;
+        src = tab.data();
+    }
+    hipcheck(hipMemcpyAsync(dRuns, src, runs.size() * sizeof(int64_t), hipMemcpyHostToDevice, st), "normFeat: upload(runs)");
+    if (ext) {
+        hipcheck(hipMemcpyAsync(mean, cfg.extMean.data(), nstat * sizeof(double), hipMemcpyHostToDevice, st), "normFeat: upload(extMean)");
+        hipcheck(hipMemcpyAsync(sd, cfg.extStd.data(), nstat * sizeof(double), hipMemcpyHostToDevice, st), "normFeat: upload(extStd)");
+    } else {
+        hipcheck(hipMemsetAsync(acc, 0, nacc * sizeof(double), st), "normFeat: memset");
+        srv.check(gmmiv_frame_moments_groups(srv.ctx(), x, GMMIV_F32, ld, D, dRuns, nrun, ng, acc));
+        srv.check(gmmiv_frame_moments_stats(srv.ctx(), ng, D, acc, mean, sd));
+    }
+    srv.check(gmmiv_feat_norm_apply(srv.ctx(), x, GMMIV_F32, ld, D, dRuns, nrun, ng, cfg.varOnly ? nullptr : mean, cfg.cmsOnly ? nullptr : sd, x,
+                                    GMMIV_F32, ld));
+    hipcheck(hipStreamSynchronize(st), "normFeat: the pageable run table must outlive its upload");
+}
+void pushRuns(std::vector<int64_t> &runs, unsigned long first, unsigned long len, int64_t group)
+{
+    const unsigned long kPiece = 4096;                               // one run is one workgroup: long segments are cut
+    while (len > 0) {
+        const unsigned long l = len < kPiece ? len : kPiece;
+        runs.push_back((int64_t)first); runs.push_back((int64_t)l); runs.push_back(group);
+        first += l; len -= l;
+    }
+}
+} // namespace
+
+void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSource, const NormFeatCfg &cfg, unsigned long firstCol, unsigned long nCols)
+{
+    if (cfg.cmsOnly && cfg.varOnly) throw Exception(" cmsOnly and varOnly are not compatible)");
+    if (selectedPerSource.size() != fs.getSourceCount()) throw Exception("normFeat: one SegCluster per source of the feature buffer expected");
+    if (firstCol >= fs.getVectSize() || firstCol + nCols > fs.getVectSize()) throw Exception("normFeat: the column slice lies outside vectSize");
+    const int D = (int)(nCols ? nCols : fs.getVectSize() - firstCol);
+    if (cfg.extMean.size() != cfg.extStd.size() || (!cfg.extMean.empty() && cfg.extMean.size() != (size_t)D))
+        throw Exception("normFeat: external mean / std must both have the length of the normalised columns");
+    const bool fileMode = cfg.fileMode || !cfg.segmentalMode;
+    for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
+        for (const Seg &g : selectedPerSource[s])
+            if (g.begin + g.length > fs.getFeatureCountOfASource(s)) throw Exception("segment ends after the last frame of its source");
+    std::vector<int64_t> runs;
+    if (cfg.segmentalMode) {
+        int64_t group = 0;
+        for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
+            for (const Seg &g : selectedPerSource[s]) pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, group++);
+        normFeatPass(fs, runs, group, cfg, firstCol, D);
+    }
+    if (fileMode) {
+        runs.clear();
+        for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
+            for (const Seg &g : selectedPerSource[s]) pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, (int64_t)s);
+        normFeatPass(fs, runs, (int64_t)selectedPerSource.size(), cfg, firstCol, D);
+    }
+}
+
+void normFeatOnlineMode(FeatureBuffer &fs, long windowDuration, long initWithDelay)
+{
+    if (windowDuration < 1 || initWithDelay < 0) throw Exception("normFeatOnlineMode: windowDuration >= 1 and initWithDelay >= 0 expected");
+    if (initWithDelay > windowDuration) initWithDelay = windowDuration; // "BAD INIT DELAY, SET TO WINDOW DURATION" (:182-186)
+    GpuServer &srv = fs.server();
+    const unsigned long ns = fs.getSourceCount();
+    std::vector<int64_t> fb(ns + 1);
+    for (unsigned long s = 0; s < ns; ++s) fb[s] = (int64_t)fs.getFirstFeatureIndexOfASource(s);
+    fb[ns] = (int64_t)fs.getFeatureCount();
+    const int64_t D = (int64_t)fs.getVectSize();
+    srv.check(gmmiv_feat_norm_online(srv.ctx(), fs.mutableDevice(), GMMIV_F32, D, (int)D, fb.data(), (int64_t)ns, windowDuration, initWithDelay,
+                                     fs.mutableDevice(), GMMIV_F32, D));
+}
+
 // ---- EnergyDetector ----------------------------------------------------------------------------------
 void energyMixtureInit(MixtureGD &world)
 {

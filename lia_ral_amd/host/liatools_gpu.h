@@ -87,6 +87,8 @@ class FeatureBuffer {
     unsigned long getVectSize() const { return _d; }
     unsigned long getFeatureCount() const { return _n; }
     unsigned long getFirstFeatureIndexOfASource(unsigned long s) const { return _first.at(s); }
+    unsigned long getSourceCount() const { return _first.size(); }
+    unsigned long getFeatureCountOfASource(unsigned long s) const { return (s + 1 < _first.size() ? _first[s + 1] : _n) - _first.at(s); }
     const float *device() const { return _dev; }
     unsigned long unusableFrames() const { return _unusable; } // frames with a NaN / infinite / absurd value, counted once at upload
     // device matrix [n x D] of the frames selected by the cluster, in cluster order.  The selection is ENQUEUED on the server's
@@ -439,6 +441,28 @@ unsigned long selectFrames(const std::vector<float> &energy, double threshold, c
 // and the threshold.
 SegCluster energyDetector(FeatureBuffer &fs, const SegCluster &selectedSegments, const EnergyDetectorCfg &cfg, MixtureGD *energyModel = nullptr,
                           double *threshold = nullptr);
+
+// ---- NormFeat (LIA_SpkDet/NormFeat/src/NormFeat.cpp:231-518), the default mode: mean / std of the selected frames per segment
+// (segmentalMode, :340-370) and / or per file (fileMode, :448-464; the mode when neither is set, :243), then computeZeroOne
+// (GeneralTools.cpp:670-682) on those frames, in place in the resident buffer.  Both set: segmental first, then file (:272).
+// cmsOnly: the std is replaced by 1 (:358); varOnly: the mean by 0 (:359); both: refused (:261).  extMean / extStd (both vectSize long,
+// or both empty): externalStatsFilename's vectors replace the computed ones (:347-350, :451-453).
+struct NormFeatCfg {
+    bool segmentalMode = false, fileMode = false, cmsOnly = false, varOnly = false;
+    std::vector<double> extMean, extStd;
+};
+// ALL sources of the buffer in one batch: selectedPerSource[s] is the cluster of selected segments of source s (Seg::begin counts
+// from the source's first frame; Seg::source is ignored).  A pass is three enqueues on the whole batch -- gmmiv_frame_moments_groups,
+// gmmiv_frame_moments_stats, gmmiv_feat_norm_apply, one group per segment or per source, runs cut at 4096 frames, all with device
+// pointers; the host waits once, at the end of the pass, because its run table is uploaded from pageable memory.  Between the passes the frames are float32 (the resident type; the reference's writeFeature into its
+// float buffer).  Segments of a cluster must not overlap (a label file's do not).  firstCol / nCols: the pass works on that column
+// slice only (featureServerMask; nCols = 0: all columns from firstCol); ext vectors are then nCols long.
+void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSource, const NormFeatCfg &cfg, unsigned long firstCol = 0,
+              unsigned long nCols = 0);
+// NormFeatWindowMode's normFeatOnlineMode (NormFeatWindowMode.cpp:165-311) on EVERY frame of every source (the tool uses no labels):
+// running mean / std with the forgetting factor (windowDuration - 1) / windowDuration, started from windowDuration - initWithDelay zero
+// vectors and the source's first initWithDelay frames (0: the tool without the parameter).  One enqueue (gmmiv_feat_norm_online).
+void normFeatOnlineMode(FeatureBuffer &fs, long windowDuration = 300, long initWithDelay = 0);
 
 // ---- AccumulateTVStat.h ----------------------------------------------------------------------------
 class TVAcc {

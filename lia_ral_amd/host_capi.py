@@ -568,6 +568,47 @@ def feature_mapping(x, cluster, cd, ci, device=0):
     return x
 
 
+def _sources(src_first, T):
+    sf = np.ascontiguousarray([0] if src_first is None else src_first, np.int64)
+    return np.ascontiguousarray(np.append(sf, T), np.int64)
+
+
+def norm_feat(x, clusters, src_first=None, segmental_mode=False, file_mode=False, cms_only=False, var_only=False, ext_mean=None,
+              ext_std=None, first_col=0, ncols=0, device=0):
+    """liagpu::normFeat (NormFeat's default mode) on float32 frames [T, D]: clusters = one list of (begin, length) per source (begins
+    counted from the source's first frame), src_first = first frame of every source (None: one source) -> the normalised frames."""
+    x = np.array(x, np.float32)
+    T, D = x.shape
+    sf = _sources(src_first, T)
+    off, b, l = _clusters(clusters)
+    em = None if ext_mean is None else np.ascontiguousarray(ext_mean, np.float64)
+    es = None if ext_std is None else np.ascontiguousarray(ext_std, np.float64)
+    _chk(lib.liagpu_norm_feat(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(len(sf) - 1), sf.ctypes.data_as(_lp), off.ctypes.data_as(_lp),
+                              b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), int(segmental_mode), int(file_mode), int(cms_only), int(var_only),
+                              None if em is None else _d(em), None if es is None else _d(es), int(first_col), int(ncols)))
+    return x
+
+
+def norm_feat_online(x, src_first=None, window_duration=300, init_with_delay=0, device=0):
+    """liagpu::normFeatOnlineMode (NormFeatWindowMode) on float32 frames [T, D], every source on its own -> the normalised frames."""
+    x = np.array(x, np.float32)
+    T, D = x.shape
+    sf = _sources(src_first, T)
+    _chk(lib.liagpu_norm_feat_online(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(len(sf) - 1), sf.ctypes.data_as(_lp),
+                                     ct.c_long(window_duration), ct.c_long(init_with_delay)))
+    return x
+
+
+def norm_feat_files(names, feature_path="", load_ext=".prm", save_ext=".norm.prm", label_path="", label_ext=".lbl", label="speech",
+                    frame_length=0.01, mask="", write_all_features=True, save_path="", segmental_mode=False, file_mode=False, cms_only=False,
+                    var_only=False, device=0):
+    """liagpu::normFeatFiles: <feature_path><name><load_ext> -> <save_path or feature_path><name><save_ext> for every name, one batch."""
+    arr = (ct.c_char_p * len(names))(*[n.encode() for n in names])
+    _chk(lib.liagpu_norm_feat_files(device, len(names), arr, feature_path.encode(), load_ext.encode(), save_path.encode(), save_ext.encode(),
+                                    label_path.encode(), label_ext.encode(), label.encode(), ct.c_double(frame_length), mask.encode(),
+                                    int(write_all_features), int(segmental_mode), int(file_mode), int(cms_only), int(var_only)))
+
+
 def compute_test_files(world_path, client_paths, client_names, prm_path, lbl_path, mask="", label="male", frame_length=0.01,
                        top_c=10, complete=True, min_llk=-200.0, max_llk=200.0, gender="M", test_name="test", threshold=0.0,
                        device=0):
