@@ -64,6 +64,8 @@ const char *gmmiv_version(void);
  *                      order -- depends only on this option, the model shape and the device model, not on the memory
  *                      free at call time: results are bitwise reproducible across runs and ranks.  (The order differs
  *                      from the reference's frame-by-frame accumulation: parity is to a tolerance, see DESIGN.md.)
+ *   "models_scratch_mb" 2048  gmmiv_*_models: MiB of packed models (nct (2 KS + 2) 512 bytes each, 2 MiB at 2048 x 60) built per chunk
+ *                      of segments; a chunk holds at least one model whatever the value
  *   "z_waves" 8        workgroup shape of k_stats_z (8, 16 or 4 waves)
  *   "z_depth_tv" 4     register sets of k_stats_z's likelihood stream (prefetch distance + 1; 2 or 4) in the N / F mode,
  *   "z_depth_em" 2     and in the EM mode; bit-identical results
@@ -399,6 +401,85 @@ int gmmiv_tv_stats(gmmiv_ctx *ctx, const gmmiv_gmm *g, const void *x, int x_dtyp
 int gmmiv_tv_stats_lines(gmmiv_ctx *ctx, const gmmiv_gmm *g, const void *x, int x_dtype, int64_t T, int64_t ldx,
                          const int64_t *file_begin, int64_t nfiles, int64_t nlines, const int64_t *line_off,
                          const int64_t *line_files, double *N, double *F);
+
+/* ---- MANY MODELS OF ONE SHAPE, ONE MODEL PER SEGMENT: batched enrolment ----------------------------------------------------------
+ * TrainTarget adapts thousands of clients with a few thousand frames each (adaptModel, TrainTools.cpp:850-905: per client and
+ * iteration one statistics pass under the client's CURRENT model, then computeMAP); verifyEMLK / getLLK score many short files, each
+ * under its own model.  The single-model entry points above run one small launch per client between host round trips.  A
+ * gmmiv_gmm_batch holds G models of a common (C, D); the *_models entry points evaluate every SEGMENT of one frame matrix under the
+ * model the caller names for it, in one log-likelihood pass per chunk.
+ *
+ * gmmiv_gmm_batch_load: w [G x C], mean [G x C*D], covinv [G x C*D], host or device, model g at p + g * stride (strides in doubles);
+ * stride 0 = the array is shared by all G models (the usual case: shared weights and variances, means per client).  The batch keeps
+ * device copies and the constants a_c of every model; the packed MFMA operands (what gmmiv_gmm_create keeps per model -- the same
+ * bits) are built per call, one launch for all models of a chunk, into a scratch of "models_scratch_mb" MiB (context option, default
+ * 2048 = 1024 models of 2048 x 60; never fewer than one model per chunk).
+ *
+ * Segments: s = frames [seg_begin[s], seg_begin[s+1]) under model seg_model[s]; seg_begin (nseg + 1, non-decreasing) and seg_model
+ * are HOST arrays.  A model may serve many segments or none; an empty segment gives zeros.  Frames before seg_begin[0] and from
+ * seg_begin[nseg] on belong to no segment: they are not read and their outputs are not touched.  Zero-likelihood frames follow
+ * "DEGENERATE INPUTS" exactly like gmmiv_llk / gmmiv_tv_stats, counters included.
+ *   gmmiv_llk_models       llk[t] (nullable, indexed like x) = clamp(log sum_c w_c lk_c(x_t)) under the segment's model;
+ *                          seg_sum[s] (nullable) = the sum of those over the segment (OVERWRITTEN; 0 for an empty segment)
+ *   gmmiv_tv_stats_models  N [nseg x C], F [nseg x C*D] as gmmiv_tv_stats; seg_llk (nullable) [2 s] = sum of the log-likelihoods of the
+ *                          segment's frames (unclamped, zero-likelihood frames left out), [2 s + 1] = the number of frames in that sum
+ * Work is cut into chunks of whole segments whose frames fit the likelihood scratch ("z_scratch_mb") and whose distinct models fit
+ * the model scratch.  A per-frame value does not depend on the chunking; a statistics row depends only on its own segment.
+ * Shapes without a stored-likelihood kernel (vectSize > 60) and calls with a segment longer than the scratch walk the segments one
+ * by one through the single-model kernels: same results, launch-bound (one model upload and ~5 launches per segment).
+ * Kernel timers: "k_llk_mfma", "k_stats_z", "k_gmm_pack". */
+typedef struct gmmiv_gmm_batch gmmiv_gmm_batch;
+int gmmiv_gmm_batch_create(gmmiv_ctx *ctx, int G, int C, int D, gmmiv_gmm_batch **out);
+int gmmiv_gmm_batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride,
+                         const double *covinv, int64_t covinv_stride);
+void gmmiv_gmm_batch_destroy(gmmiv_gmm_batch *b);
+int gmmiv_llk_models(gmmiv_ctx *ctx, const gmmiv_gmm_batch *b, const void *x, int x_dtype, int64_t T, int64_t ldx,
+                     const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, double min_llk, double max_llk,
+                     double *llk /* [T], nullable */, double *seg_sum /* [nseg], nullable */);
+int gmmiv_tv_stats_models(gmmiv_ctx *ctx, const gmmiv_gmm_batch *b, const void *x, int x_dtype, int64_t T, int64_t ldx,
+                          const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, double *N, double *F,
+                          double *seg_llk /* [2 nseg], nullable */);
+/* Debug / test access: the packed block of model g as a call would build it, nct * (2 KS + 2) * 64 doubles (*len, also returned when
+ * out == NULL); GMMIV_ERR_UNSUPPORTED for a shape without packed operands. */
+int gmmiv_gmm_batch_packed(const gmmiv_gmm_batch *b, int g, double *out, int64_t *len);
+
+/* The work list of the batched log-likelihood kernel, exported so that it can be checked without a GPU (pure host function).  One
+ * entry per workgroup: a tile of tile_frames frames (a multiple of 32; the kernel uses 256) that starts at `first`, a multiple of 16 --
+ * the 16-frame block holding the segment's first frame, then every tile_frames from there (the stored likelihoods are laid out in
+ * blocks of 16 frames, frame = 16 block + row, so a segment cannot be shifted inside its blocks).  The workgroup evaluates the
+ * frames [lo, hi) of its tile -- the part that belongs to segment `seg` -- under model `model`; the other rows of its tile are loaded
+ * as 0 and none of their outputs is written, so a block that straddles two segments is visited by two workgroups that write
+ * disjoint rows.  Rows of the first / last 16-frame block that lie before seg_begin[0] / from seg_begin[nseg] on belong to nobody; the
+ * first and the last tile of the list also write those rows of the LIKELIHOOD scratch (pad_lo / pad_hi rows, evaluated on zeros), so
+ * that the statistics kernel, which reads whole blocks and masks by multiplying with 0, never meets uninitialised memory.
+ * Returns the number of tiles (entries beyond `cap` are counted, not written), or -1 for a bad argument. */
+typedef struct gmmiv_model_tile {
+    int64_t first;           /* first frame of the tile (multiple of 16) */
+    int64_t lo, hi;          /* frames of the segment inside the tile: first <= lo < hi <= first + tile_frames */
+    int32_t model, seg;
+    int32_t pad_lo, pad_hi;  /* rows [lo - pad_lo, lo) and [hi, hi + pad_hi) are written to the likelihood scratch too (< 16 each) */
+} gmmiv_model_tile;
+int64_t gmmiv_plan_model_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int tile_frames,
+                               gmmiv_model_tile *tiles, int64_t cap);
+
+/* computeMAP (TrainTools.cpp:445-556) for G models at once, from the statistics rows of gmmiv_tv_stats_models: element-wise over
+ * [G x C x D], nothing leaves the device.  Per model g: count_g = count[g * count_stride] (seg_llk + 1 with stride 2 fits), the ML
+ * estimate w_c = N_c / count_g (0 when count_g = 0), mean_c = F_c / N_c, a Gaussian with N_c = 0 keeps cur_mean (model g at
+ * cur_mean + g * cur_stride, stride 0 = shared) and gets weight 0 like gmmiv_em_get; then, with n = count_g TRUNCATED to an integer
+ * (the reference passes an unsigned long) and the a-priori model (w0, mean0):
+ *   GMMIV_MAP_OCC_DEP / GMMIV_MAP_MODEL_BASED   alpha = w_c n; a = alpha / (alpha + mean_reg); mean = (1 - a) mean0 + a mean_ml;
+ *                          weights (weight_adapt): a = alpha / (alpha + weight_reg), a w_c + (1 - a) w0_c, renormalised to sum 1
+ *   GMMIV_MAP_CONST        mean = mean_alpha mean0 + (1 - mean_alpha) mean_ml
+ *   GMMIV_MAP_CONST2       mean = (mean_alpha w0 mean0 + (1 - mean_alpha) w mean_ml) / (w0 mean_alpha + w (1 - mean_alpha))
+ *   GMMIV_MAP_NONE         the ML estimate itself (an unknown mapAlgo: "No adaptation will be perform")
+ * mean_adapt = 0 gives mean0; without weight_adapt (and for the two constant methods) the weights are w0.  Variances are not touched
+ * (varAdapt needs second-order statistics per segment: not batched).  mean_out [G x C*D], w_out [G x C] (nullable): device or
+ * host; device outputs can be handed straight to gmmiv_gmm_batch_load.  Every operation is rounded on its own (no contraction). */
+enum { GMMIV_MAP_NONE = 0, GMMIV_MAP_OCC_DEP = 1, GMMIV_MAP_MODEL_BASED = 2, GMMIV_MAP_CONST = 3, GMMIV_MAP_CONST2 = 4 };
+int gmmiv_map_adapt_models(gmmiv_ctx *ctx, int G, int C, int D, const double *N, const double *F, const double *count,
+                           int64_t count_stride, const double *w0, const double *mean0, const double *cur_mean, int64_t cur_stride,
+                           int method, int mean_adapt, int weight_adapt, double mean_reg, double weight_reg, double mean_alpha,
+                           double *mean_out, double *w_out);
 
 /* ---- TVAcc i-vector maths (exact mode) -------------------------------------------------------
  * T: [R x C*D] row-major total-variability matrix; invvar: [C*D] UBM inverse variances.

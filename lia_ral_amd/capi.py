@@ -39,6 +39,7 @@ def _load():
     lib.gmmiv_comm_backend.restype = ct.c_char_p
     lib.gmmiv_comm_take_bytes.restype = ct.c_double
     lib.gmmiv_ctx_stream.restype = ct.c_void_p
+    lib.gmmiv_plan_model_tiles.restype = ct.c_int64
     return lib
 
 
@@ -219,6 +220,10 @@ class Context:
         return Gmm(self, w, mean, covinv)
 
     # ---- FrameAccGD
+    def gmm_batch(self, G, C, D):
+        """G models of one (C, D) for the per-segment entry points: .load, .llk, .tv_stats, .map_adapt (GmmBatch)."""
+        return GmmBatch(self, G, C, D)
+
     def frame_moments(self, x, acc=None):
         x, dt, T, ldx = _feat(x)
         D = x.shape[1]
@@ -904,3 +909,123 @@ class Gmm:
         _chk(lib.gmmiv_tv_stats(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx),
                                 ub.ctypes.data_as(ct.c_void_p), ct.c_int64(U), _ptr(N), _ptr(F)))
         return N, F
+
+
+class ModelTile(ct.Structure):
+    """gmmiv_model_tile: one workgroup of the batched log-likelihood kernel"""
+    _fields_ = [("first", ct.c_int64), ("lo", ct.c_int64), ("hi", ct.c_int64), ("model", ct.c_int32), ("seg", ct.c_int32),
+                ("pad_lo", ct.c_int32), ("pad_hi", ct.c_int32)]
+
+
+def plan_model_tiles(seg_begin, seg_model, tile_frames=256):
+    """gmmiv_plan_model_tiles (host only, needs no GPU) -> list of dicts first / lo / hi / model / seg / pad_lo / pad_hi"""
+    sb = np.ascontiguousarray(seg_begin, np.int64)
+    sm = np.ascontiguousarray(seg_model, np.int32)
+    nseg = len(sb) - 1
+    assert len(sm) == nseg
+    args = (sb.ctypes.data_as(ct.c_void_p), sm.ctypes.data_as(ct.c_void_p), ct.c_int64(nseg), int(tile_frames))
+    n = lib.gmmiv_plan_model_tiles(*args, ct.c_void_p(0), ct.c_int64(0))
+    if n < 0:
+        raise GmmivError("gmmiv_plan_model_tiles: bad argument")
+    buf = (ModelTile * max(int(n), 1))()
+    lib.gmmiv_plan_model_tiles(*args, ct.cast(buf, ct.c_void_p), ct.c_int64(n))
+    return [{k: getattr(buf[i], k) for k, _ in ModelTile._fields_} for i in range(int(n))]
+
+
+MAP_METHODS = {"MAPOccDep": 1, "MAPModelBased": 2, "MAPConst": 3, "MAPConst2": 4}  # anything else: 0, the ML estimate (computeMAP's "mapAlgo unknown")
+
+
+class GmmBatch:
+    """G device-resident models of one shape, a model per SEGMENT of the frame matrix (batched enrolment / getLLK for many files)."""
+
+    def __init__(self, ctx, G, C, D):
+        self.ctx, self.G, self.C, self.D = ctx, int(G), int(C), int(D)
+        self._h = ct.c_void_p()
+        _chk(lib.gmmiv_gmm_batch_create(ctx._h, self.G, self.C, self.D, ct.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.gmmiv_gmm_batch_destroy(self._h)
+            self._h = ct.c_void_p()
+
+    def __del__(self):
+        try:
+            if sys is None or sys.is_finalizing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def _stride(self, a, row):
+        """[row] or [1, row]: shared (stride 0); [G, row]: one per model"""
+        n = a.numel() if _is_torch(a) else a.size
+        assert n in (row, self.G * row), "a table is shared ([%d]) or per model ([%d x %d])" % (row, self.G, row)
+        return 0 if n == row and self.G > 1 else row
+
+    def load(self, w, mean, covinv):
+        """w [C] or [G, C]; mean, covinv [C, D] or [G, C, D] (numpy or torch device): a table with one model's size is shared by all G."""
+        w, mean, covinv = _f64(w), _f64(mean), _f64(covinv)
+        CD = self.C * self.D
+        _chk(lib.gmmiv_gmm_batch_load(self._h, _ptr(w), ct.c_int64(self._stride(w, self.C)), _ptr(mean), ct.c_int64(self._stride(mean, CD)),
+                                      _ptr(covinv), ct.c_int64(self._stride(covinv, CD))))
+        return self
+
+    def packed(self, g):
+        """the packed MFMA operands of model g as a call builds them (tests: bit for bit those of a single-model handle)"""
+        n = ct.c_int64()
+        _chk(lib.gmmiv_gmm_batch_packed(self._h, int(g), ct.c_void_p(0), ct.byref(n)))
+        out = np.empty(n.value)
+        _chk(lib.gmmiv_gmm_batch_packed(self._h, int(g), _ptr(out), ct.byref(n)))
+        return out
+
+    @staticmethod
+    def _segs(seg_begin, seg_model):
+        sb = np.ascontiguousarray(seg_begin, np.int64)
+        sm = np.ascontiguousarray(seg_model, np.int32)
+        assert len(sb) == len(sm) + 1
+        return sb, sm
+
+    def llk(self, x, seg_begin, seg_model, min_llk=-200.0, max_llk=200.0, out=None, seg_sum=None):
+        """-> (llk [T], seg_sum [nseg]); entries of llk outside the segments keep what `out` holds (a fresh array: NaN)"""
+        x, dt, T, ldx = _feat(x)
+        sb, sm = self._segs(seg_begin, seg_model)
+        if out is None:
+            out = np.full(T, np.nan)
+        if seg_sum is None:
+            seg_sum = np.empty(len(sm))
+        _chk(lib.gmmiv_llk_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
+                                  sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), ct.c_double(min_llk), ct.c_double(max_llk), _ptr(out),
+                                  _ptr(seg_sum)))
+        return out, seg_sum
+
+    def tv_stats(self, x, seg_begin, seg_model, N=None, F=None, seg_llk=None):
+        """-> (N [nseg, C], F [nseg, C*D], seg_llk [nseg, 2] = (sum of log-likelihoods, frames in it))"""
+        x, dt, T, ldx = _feat(x)
+        sb, sm = self._segs(seg_begin, seg_model)
+        if N is None:
+            N = np.empty((len(sm), self.C)); F = np.empty((len(sm), self.C * self.D))
+        if seg_llk is None:
+            seg_llk = np.empty((len(sm), 2))
+        _chk(lib.gmmiv_tv_stats_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
+                                       sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(N), _ptr(F), _ptr(seg_llk)))
+        return N, F, seg_llk
+
+    def map_adapt(self, N, F, count, w0, mean0, cur_mean, method="MAPOccDep", mean=True, weight=False, reg=(16.0, 16.0, 16.0), alpha_mean=0.75,
+                  mean_out=None, w_out=None, count_stride=1):
+        """computeMAP for the G statistics rows (gmmiv_map_adapt_models): -> (means [G, C*D], weights [G, C]).  reg = (mean, var, weight)
+        like host_capi.compute_map; cur_mean [C*D] (shared) or [G, C*D]; count [G] (count_stride 1) or e.g. seg_llk[:, 1] as stride 2."""
+        G, C, D = self.G, self.C, self.D
+        tor = _is_torch(N)
+        if mean_out is None:
+            if tor:
+                import torch
+                mean_out = torch.empty((G, C * D), dtype=torch.float64, device=N.device)
+                w_out = torch.empty((G, C), dtype=torch.float64, device=N.device)
+            else:
+                mean_out = np.empty((G, C * D)); w_out = np.empty((G, C))
+        cur = _f64(cur_mean)
+        _chk(lib.gmmiv_map_adapt_models(self.ctx._h, G, C, D, _ptr(_f64(N)), _ptr(_f64(F)), _ptr(_f64(count)), ct.c_int64(count_stride), _ptr(_f64(w0)),
+                                        _ptr(_f64(mean0)), _ptr(cur), ct.c_int64(self._stride(cur, C * D)), MAP_METHODS.get(method, 0), int(bool(mean)),
+                                        int(bool(weight)), ct.c_double(reg[0]), ct.c_double(reg[2]), ct.c_double(alpha_mean), _ptr(mean_out),
+                                        _ptr(w_out)))
+        return mean_out, w_out

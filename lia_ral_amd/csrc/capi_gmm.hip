@@ -6,6 +6,7 @@
 #include "ctx.h"
 #include "gmm_kernels.h"
 #include "tv_kernels.h"
+#include "capi_gmm_util.h"
 
 static thread_local char g_err[512] = "";
 
@@ -111,6 +112,7 @@ long gmmiv_ctx_set_option(gmmiv_ctx *c, const char *key, long value)
     else if (!strcmp(key, "prune_log2")) slot = &c->prune_log2;
     else if (!strcmp(key, "stats_z")) slot = &c->stats_z;
     else if (!strcmp(key, "z_scratch_mb")) slot = &c->z_scratch_mb;
+    else if (!strcmp(key, "models_scratch_mb")) slot = &c->models_scratch_mb;
     else if (!strcmp(key, "tv_batch")) slot = &c->tv_batch;
     else if (!strcmp(key, "tv_tett_direct")) slot = &c->tv_tett_direct;
     else if (!strcmp(key, "tv_stats_split")) slot = &c->tv_stats_split;
@@ -273,26 +275,6 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g)
 
 // ---- helpers -----------------------------------------------------------------------------
 static size_t esize(int dt) { return dt == GMMIV_F64 ? 8 : 4; }
-
-// Device view of the feature block [T x ldx]; host input is copied (compacted to ldx = D).
-struct XView {
-    const void *d = nullptr;
-    int64_t ldx = 0;
-    int init(gmmiv_ctx *c, const void *x, int dt, int64_t T, int64_t ld, int D)
-    {
-        if (dt != GMMIV_F32 && dt != GMMIV_F64) { gmmiv_set_error("feature dtype must be GMMIV_F32 or GMMIV_F64"); return GMMIV_ERR_ARG; }
-        if (ld < D) { gmmiv_set_error("ldx (%ld) < D (%d)", (long)ld, D); return GMMIV_ERR_ARG; }
-        if (T == 0) { d = x; ldx = ld; return GMMIV_OK; }
-        if (!x) { gmmiv_set_error("x == NULL"); return GMMIV_ERR_ARG; }
-        if (gmmiv_is_device_ptr(x)) { d = x; ldx = ld; return GMMIV_OK; }
-        void *buf;
-        int rc = c->scratch(WS_X, (size_t)T * D * esize(dt), &buf);
-        if (rc) return rc;
-        GCHK(hipMemcpy2DAsync(buf, D * esize(dt), x, ld * esize(dt), D * esize(dt), T, hipMemcpyHostToDevice, c->stream));
-        d = buf; ldx = D;
-        return GMMIV_OK;
-    }
-};
 
 // ---- degenerate inputs (include/gmmiv.h): frames with a non-finite / absurd feature value never reach the kernels ----------
 // Screening = one HBM pass over x per call (skipped with the option "assume_finite"); in the -- rare -- call that has unusable
@@ -1593,6 +1575,15 @@ int gmmiv_feat_norm_online(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int
     c->t_end();
     if (host_tab) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
     return GMMIV_OK;
+}
+
+// ---- helpers shared with capi_models.hip (capi_gmm_util.h) ---------------------------------------------------------------------
+int gmmiv_i_count_unusable(gmmiv_ctx *c, const XView &xv, int dt, int64_t T, int D) { return count_unusable(c, xv, dt, T, D); }
+int gmmiv_i_run_lse(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, double **lse_out) { return run_lse(c, g, xv, dt, T, lse_out); }
+int gmmiv_i_generic_gamma_gemm(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t t0, int64_t n, const double *lse, bool sq, int NC,
+                               double *S)
+{
+    return generic_gamma_gemm(c, g, xv, dt, t0, n, lse, sq, NC, S);
 }
 
 } // extern "C"

@@ -1,0 +1,490 @@
+// capi_models.hip -- C ABI (include/gmmiv.h): a batch of models of one shape, log-likelihood / Baum-Welch statistics with a model per
+// segment, computeMAP for the whole batch.  DESIGN.md section 3.14.
+#include <math.h>
+#include <stdlib.h>
+
+#include <vector>
+
+#include "capi_gmm_util.h"
+#include "gmm_kernels.h"
+
+#define MODEL_TILE_FRAMES 256 // frames per workgroup of k_llk_mfma (8 waves x 32)
+
+extern "C" {
+
+// ---- the tile table (pure host) ---------------------------------------------------------------------------------------------------
+int64_t gmmiv_plan_model_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int tile_frames, gmmiv_model_tile *tiles,
+                               int64_t cap)
+{
+    if (!seg_begin || !seg_model || nseg < 0 || tile_frames <= 0 || tile_frames % 32 || seg_begin[0] < 0) return -1;
+    int64_t first_ne = -1, last_ne = -1;
+    for (int64_t s = 0; s < nseg; ++s) {
+        if (seg_begin[s + 1] < seg_begin[s]) return -1;
+        if (seg_begin[s + 1] > seg_begin[s]) { if (first_ne < 0) first_ne = s; last_ne = s; }
+    }
+    int64_t n = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t b = seg_begin[s], e = seg_begin[s + 1];
+        if (e <= b) continue; // an empty segment has no tile
+        for (int64_t f = b & ~(int64_t)15; f < e; f += tile_frames) {
+            gmmiv_model_tile t;
+            t.first = f;
+            t.lo = b > f ? b : f;
+            t.hi = e < f + tile_frames ? e : f + tile_frames;
+            t.model = seg_model[s];
+            t.seg = (int32_t)s;
+            // rows of the first / last block that no segment owns: written (as the likelihoods of a zero frame) by the tile next to them
+            t.pad_lo = (s == first_ne && f <= b) ? (int32_t)(b - f) : 0;
+            t.pad_hi = (s == last_ne && t.hi == e) ? (int32_t)(((e + 15) & ~(int64_t)15) - e) : 0;
+            if (tiles && n < cap) tiles[n] = t;
+            ++n;
+        }
+    }
+    return n;
+}
+
+// ---- the batch ----------------------------------------------------------------------------------------------------------------------
+int gmmiv_gmm_batch_create(gmmiv_ctx *c, int G, int C, int D, gmmiv_gmm_batch **out)
+{
+    if (!c || !out || G <= 0 || C <= 0 || D <= 0) { gmmiv_set_error("gmm_batch_create: bad argument"); return GMMIV_ERR_ARG; }
+    const int KS = gmmk_ks_for_dim(D);
+    if (!KS) { gmmiv_set_error("gmm_batch_create: vectSize %d not supported (max %d)", D, GMMK_MAX_DIM); return GMMIV_ERR_UNSUPPORTED; }
+    GBIND(c);
+    gmmiv_gmm_batch *b = new gmmiv_gmm_batch();
+    b->ctx = c; b->G = G; b->C = C; b->D = D; b->KS = KS;
+    b->nct = ((C + 15) / 16 + 1) / 2 * 2; // as gmmiv_gmm_create
+    b->Cp64 = (C + 63) / 64 * 64;
+    b->Cpa = b->Cp64 > b->nct * 16 ? b->Cp64 : b->nct * 16;
+    if (hipMalloc((void **)&b->a, (size_t)G * b->Cpa * sizeof(double)) != hipSuccess || hipMalloc((void **)&b->lwc, (size_t)G * b->Cpa * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        gmmiv_gmm_batch_destroy(b);
+        gmmiv_set_error("gmm_batch_create: hipMalloc of the constants of %d models failed", G);
+        return GMMIV_ERR_HIP;
+    }
+    *out = b;
+    return GMMIV_OK;
+}
+
+void gmmiv_gmm_batch_destroy(gmmiv_gmm_batch *b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    void *ptrs[] = {b->w, b->mean, b->iv, b->a, b->lwc};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    delete b;
+}
+
+// one table: G rows of `row` doubles `stride` apart (or one shared row) into a compact device copy
+static int batch_table(gmmiv_gmm_batch *b, double **dst, size_t *cap, long *dst_stride, const double *src, int64_t stride, size_t row)
+{
+    gmmiv_ctx *c = b->ctx;
+    const size_t rows = stride == 0 ? 1 : (size_t)b->G, need = rows * row;
+    if (*cap < need) {
+        if (*dst) { GCHK(hipStreamSynchronize(c->stream)); GCHK(hipFree(*dst)); *dst = nullptr; *cap = 0; }
+        const hipError_t e = hipMalloc((void **)dst, need * sizeof(double));
+        if (e != hipSuccess) { (void)hipGetLastError(); *dst = nullptr; gmmiv_set_error("gmm_batch_load: hipMalloc of %zu bytes -> %s", need * sizeof(double), hipGetErrorString(e)); return GMMIV_ERR_HIP; }
+        *cap = need;
+    }
+    const hipMemcpyKind kind = gmmiv_is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    GCHK(hipMemcpy2DAsync(*dst, row * sizeof(double), src, (stride == 0 ? row : (size_t)stride) * sizeof(double), row * sizeof(double), rows, kind, c->stream));
+    *dst_stride = stride == 0 ? 0 : (long)row;
+    return GMMIV_OK;
+}
+
+int gmmiv_gmm_batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride, const double *covinv,
+                         int64_t covinv_stride)
+{
+    if (!b || !w || !mean || !covinv) { gmmiv_set_error("gmm_batch_load: bad argument"); return GMMIV_ERR_ARG; }
+    const size_t CD = (size_t)b->C * b->D;
+    if ((w_stride && w_stride < b->C) || (mean_stride && mean_stride < (int64_t)CD) || (covinv_stride && covinv_stride < (int64_t)CD)) {
+        gmmiv_set_error("gmm_batch_load: a stride must be 0 (shared) or at least the size of one model's table");
+        return GMMIV_ERR_ARG;
+    }
+    gmmiv_ctx *c = b->ctx;
+    GBIND(c);
+    int rc;
+    b->loaded = false;
+    if ((rc = batch_table(b, &b->w, &b->cap_w, &b->sw, w, w_stride, (size_t)b->C))) return rc;
+    if ((rc = batch_table(b, &b->mean, &b->cap_mean, &b->sm, mean, mean_stride, CD))) return rc;
+    if ((rc = batch_table(b, &b->iv, &b->cap_iv, &b->si, covinv, covinv_stride, CD))) return rc;
+    GCHK(gmmk_const_models(c->stream, b->G, b->C, b->Cpa, b->D, b->w, b->sw, b->mean, b->sm, b->iv, b->si, b->a, b->lwc));
+    if (!gmmiv_is_device_ptr(w) || !gmmiv_is_device_ptr(mean) || !gmmiv_is_device_ptr(covinv)) GCHK(hipStreamSynchronize(c->stream)); // host sources may be freed by the caller on return
+    b->loaded = true;
+    return GMMIV_OK;
+}
+
+static int check_batch(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const char *who)
+{
+    if (!c || !b) { gmmiv_set_error("%s: NULL context or batch", who); return GMMIV_ERR_ARG; }
+    if (b->ctx != c) { gmmiv_set_error("%s: the batch belongs to a different context", who); return GMMIV_ERR_ARG; }
+    if (!b->loaded) { gmmiv_set_error("%s: the batch has no models yet (gmmiv_gmm_batch_load)", who); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    return GMMIV_OK;
+}
+
+static int check_segments(const gmmiv_gmm_batch *b, const char *who, int64_t T, const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg)
+{
+    if (T < 0 || nseg < 0 || !seg_begin || (nseg && !seg_model)) { gmmiv_set_error("%s: bad argument", who); return GMMIV_ERR_ARG; }
+    if (gmmiv_is_device_ptr(seg_begin) || gmmiv_is_device_ptr(seg_model)) { gmmiv_set_error("%s: seg_begin and seg_model must be host arrays", who); return GMMIV_ERR_ARG; }
+    if (nseg > 0x7fffffff / 64) { gmmiv_set_error("%s: too many segments in one call", who); return GMMIV_ERR_UNSUPPORTED; }
+    if (seg_begin[0] < 0 || seg_begin[nseg] > T) { gmmiv_set_error("%s: seg_begin out of range", who); return GMMIV_ERR_ARG; }
+    for (int64_t s = 0; s < nseg; ++s) {
+        if (seg_begin[s + 1] < seg_begin[s]) { gmmiv_set_error("%s: seg_begin must be non-decreasing", who); return GMMIV_ERR_ARG; }
+        if (seg_model[s] < 0 || seg_model[s] >= b->G) { gmmiv_set_error("%s: seg_model[%lld] = %d outside [0, %d)", who, (long long)s, seg_model[s], b->G); return GMMIV_ERR_ARG; }
+    }
+    return GMMIV_OK;
+}
+
+int gmmiv_gmm_batch_packed(const gmmiv_gmm_batch *b, int g, double *out, int64_t *len)
+{
+    if (!b || g < 0 || g >= b->G) { gmmiv_set_error("gmm_batch_packed: bad argument"); return GMMIV_ERR_ARG; }
+    int rc = check_batch(b->ctx, b, "gmm_batch_packed");
+    if (rc) return rc;
+    if (b->KS == GMMK_KS_GENERIC) { gmmiv_set_error("gmm_batch_packed: vectSize %d has no packed operands", b->D); return GMMIV_ERR_UNSUPPORTED; }
+    if (len) *len = (int64_t)b->packed_doubles();
+    if (!out) return GMMIV_OK;
+    gmmiv_ctx *c = b->ctx;
+    void *pt, *ids;
+    if ((rc = c->scratch(WS_MB_PT, b->packed_doubles() * sizeof(double), &pt))) return rc;
+    if ((rc = c->scratch(WS_MB_IDS, sizeof(int), &ids))) return rc;
+    GCHK(hipMemcpyAsync(ids, &g, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    GCHK(gmmk_pack_models(c->stream, 1, (const int *)ids, b->C, b->Cpa, b->D, b->KS, b->nct, b->mean, b->sm, b->iv, b->si, b->a, (double *)pt));
+    GCHK(hipMemcpyAsync(out, pt, b->packed_doubles() * sizeof(double), gmmiv_is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    GCHK(hipStreamSynchronize(c->stream));
+    return GMMIV_OK;
+}
+
+// ---- chunks of whole segments: frames that fit the scratch, distinct models that fit the packed-model scratch --------------------------
+struct ModelChunk {
+    int64_t s0, s1;      // segments [s0, s1)
+    int64_t base;        // first frame of the chunk's coordinate system: the 16-frame block holding seg_begin[s0]
+    size_t tile_off, ntiles, id_off, nids, seg_off;
+};
+struct ModelPlan {
+    std::vector<ModelChunk> chunks;
+    std::vector<gmmiv_model_tile> tiles;
+    std::vector<int> ids;
+    std::vector<long> segrel;
+    int64_t max_span = 0; // frames from a chunk's base to its end
+    int max_models = 0;
+    const gmmiv_model_tile *d_tiles = nullptr;
+    const int *d_ids = nullptr;
+    const long *d_seg = nullptr;
+};
+
+// false: a segment is longer than max_frames (the caller walks the segments one by one)
+static bool plan_chunks(const gmmiv_gmm_batch *b, const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int64_t max_frames, int max_models,
+                        ModelPlan &p)
+{
+    std::vector<int> slot((size_t)b->G, -1);
+    for (int64_t s0 = 0; s0 < nseg;) {
+        ModelChunk ck;
+        ck.s0 = s0;
+        ck.base = seg_begin[s0] & ~(int64_t)15;
+        ck.id_off = p.ids.size();
+        int64_t s1 = s0;
+        while (s1 < nseg) {
+            const bool ne = seg_begin[s1 + 1] > seg_begin[s1];
+            if (ne && seg_begin[s1 + 1] - ck.base > max_frames) break;
+            if (ne && slot[seg_model[s1]] < 0) {
+                if ((int)(p.ids.size() - ck.id_off) >= max_models) break;
+                slot[seg_model[s1]] = (int)(p.ids.size() - ck.id_off);
+                p.ids.push_back(seg_model[s1]);
+            }
+            ++s1;
+        }
+        if (s1 == s0) return false;
+        ck.s1 = s1;
+        ck.nids = p.ids.size() - ck.id_off;
+        ck.seg_off = p.segrel.size();
+        for (int64_t s = s0; s <= s1; ++s) p.segrel.push_back((long)(seg_begin[s] - ck.base));
+        ck.tile_off = p.tiles.size();
+        const int64_t nt = gmmiv_plan_model_tiles(seg_begin + s0, seg_model + s0, s1 - s0, MODEL_TILE_FRAMES, nullptr, 0);
+        p.tiles.resize(ck.tile_off + (size_t)nt);
+        gmmiv_plan_model_tiles(seg_begin + s0, seg_model + s0, s1 - s0, MODEL_TILE_FRAMES, p.tiles.data() + ck.tile_off, nt);
+        for (size_t i = ck.tile_off; i < p.tiles.size(); ++i) {
+            gmmiv_model_tile &t = p.tiles[i];
+            t.first -= ck.base; t.lo -= ck.base; t.hi -= ck.base;
+            t.model = slot[t.model];
+        }
+        ck.ntiles = (size_t)nt;
+        for (size_t i = ck.id_off; i < p.ids.size(); ++i) slot[p.ids[i]] = -1;
+        const int64_t span = seg_begin[s1] - ck.base;
+        if (span > p.max_span) p.max_span = span;
+        if ((int)ck.nids > p.max_models) p.max_models = (int)ck.nids;
+        p.chunks.push_back(ck);
+        s0 = s1;
+    }
+    return true;
+}
+
+static int upload_plan(gmmiv_ctx *c, ModelPlan &p)
+{
+    void *dt, *di, *ds;
+    int rc;
+    if ((rc = c->scratch(WS_MB_TILES, p.tiles.size() * sizeof(gmmiv_model_tile), &dt))) return rc;
+    if ((rc = c->scratch(WS_MB_IDS, p.ids.size() * sizeof(int), &di))) return rc;
+    if ((rc = c->scratch(WS_MB_SEG, p.segrel.size() * sizeof(long), &ds))) return rc;
+    if (!p.tiles.empty()) GCHK(hipMemcpyAsync(dt, p.tiles.data(), p.tiles.size() * sizeof(gmmiv_model_tile), hipMemcpyHostToDevice, c->stream));
+    if (!p.ids.empty()) GCHK(hipMemcpyAsync(di, p.ids.data(), p.ids.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    GCHK(hipMemcpyAsync(ds, p.segrel.data(), p.segrel.size() * sizeof(long), hipMemcpyHostToDevice, c->stream));
+    GCHK(hipStreamSynchronize(c->stream)); // the tables live in host vectors
+    p.d_tiles = (const gmmiv_model_tile *)dt; p.d_ids = (const int *)di; p.d_seg = (const long *)ds;
+    return GMMIV_OK;
+}
+
+static int models_per_chunk(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
+{
+    const size_t budget = (size_t)(c->models_scratch_mb > 0 ? c->models_scratch_mb : 0) << 20;
+    const size_t n = budget / (b->packed_doubles() * sizeof(double));
+    return n < 1 ? 1 : (n > 0x7fff ? 0x7fff : (int)n);
+}
+
+// frames per chunk of the stored-likelihood path (multiple of 256), 0 when it does not apply.  Like z_chunk_frames of capi_gmm.hip it
+// depends on the option, the model shape and the device's TOTAL memory only; unlike it, it goes down to one tile: a call of short
+// segments is served with any scratch that holds its longest segment
+static int64_t models_chunk_frames(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
+{
+    if (!c->stats_z || b->KS > 15) return 0;
+    size_t budget = (size_t)(c->z_scratch_mb > 0 ? c->z_scratch_mb : 0) << 20;
+    if (c->total_mem && budget > c->total_mem / 4) budget = c->total_mem / 4;
+    const size_t per_frame = (size_t)b->nct * 16 * sizeof(double) + (size_t)b->nct * 2 + 24; // likelihoods + exponents + lse, 1 / S, Efin
+    const int64_t tc = (int64_t)(budget / per_frame / 1.2); // scratch() over-allocates by 1/8
+    return tc / 256 * 256;
+}
+
+static long model_tile_blocks(int64_t n) // z_tile_blocks of capi_gmm.hip: whole 256-frame tiles, tile stride an odd number of 4 KB granules
+{
+    long nfb = 16 * ((n + 255) / 256);
+    if ((nfb / 2) % 2 == 0) nfb += 2;
+    return nfb;
+}
+
+static int pack_chunk(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const ModelPlan &p, const ModelChunk &ck, double *pt, bool first)
+{
+    c->t_begin("k_gmm_pack", first);
+    GCHK(gmmk_pack_models(c->stream, (int)ck.nids, p.d_ids + ck.id_off, b->C, b->Cpa, b->D, b->KS, b->nct, b->mean, b->sm, b->iv, b->si, b->a, pt));
+    c->t_end();
+    return GMMIV_OK;
+}
+
+// ---- the walk for shapes / calls the batched kernel does not serve: one segment at a time on a single-model handle -----------------
+struct OneModel {
+    gmmiv_gmm *g = nullptr;
+    int cur = -1;
+    ~OneModel() { if (g) gmmiv_gmm_destroy(g); }
+    int set(gmmiv_ctx *c, const gmmiv_gmm_batch *b, int m)
+    {
+        if (m == cur) return GMMIV_OK;
+        const double *w = b->w + (size_t)m * b->sw, *mean = b->mean + (size_t)m * b->sm, *iv = b->iv + (size_t)m * b->si;
+        const int rc = g ? gmmiv_gmm_set(g, w, mean, iv) : gmmiv_gmm_create(c, b->C, b->D, w, mean, iv, &g);
+        if (!rc) cur = m;
+        return rc;
+    }
+};
+
+static int segment_table(gmmiv_ctx *c, int64_t n, long **sb)
+{
+    void *p;
+    int rc = c->scratch(WS_MB_SEG, 2 * sizeof(long), &p);
+    if (rc) return rc;
+    GCHK(gmmk_fill_chunks(c->stream, (long *)p, 1, (long)n, (long)n)); // {0, n}, written on the device
+    *sb = (long *)p;
+    return GMMIV_OK;
+}
+
+int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                     const int32_t *seg_model, int64_t nseg, double min_llk, double max_llk, double *llk, double *seg_sum)
+{
+    int rc = check_batch(c, b, "llk_models");
+    if (rc) return rc;
+    if ((rc = check_segments(b, "llk_models", T, seg_begin, seg_model, nseg))) return rc;
+    if (nseg == 0) return GMMIV_OK;
+    XView xv;
+    if ((rc = xv.init(c, x, dt, T, ldx, b->D))) return rc;
+    DevOut<double> o_llk, o_sum;
+    if ((rc = o_llk.init(c, WS_T0, llk, (size_t)T, true))) return rc; // frames outside the segments keep what the caller has there
+    if ((rc = o_sum.init(c, WS_T1, seg_sum, (size_t)nseg, false))) return rc;
+    ModelPlan p;
+    // the plain log-likelihood needs one double of scratch per frame: chunks by models, and by 16 M frames
+    if (b->KS <= 15 && plan_chunks(b, seg_begin, seg_model, nseg, (int64_t)1 << 24, models_per_chunk(c, b), p)) {
+        if ((rc = upload_plan(c, p))) return rc;
+        void *pt, *lse;
+        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        if ((rc = c->scratch(WS_LSE, (size_t)(p.max_span > 0 ? p.max_span : 1) * sizeof(double), &lse))) return rc;
+        bool first = true; // the first launch of the call restarts the kernel timers
+        for (size_t k = 0; k < p.chunks.size(); ++k) {
+            const ModelChunk &ck = p.chunks[k];
+            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
+            if (n > 0) {
+                XView sub;
+                sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+                if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+                if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
+                c->t_begin("k_llk_mfma", first);
+                first = false;
+                GCHK(gmmk_llk_models(c->stream, b->KS, dt == GMMIV_F64, gmmiv_x_at(xv, dt, ck.base), xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(),
+                                     b->nct, p.d_tiles + ck.tile_off, (long)ck.ntiles, (double *)lse, (int)(c->use_glds & 1)));
+                c->t_end();
+                GCHK(gmmk_count_dead(c->stream, (const double *)lse + (f0 - ck.base), (long)n, c->d_zero_llk));
+            }
+            GCHK(gmmk_llk_seg_finalize(c->stream, (const double *)lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), min_llk, max_llk,
+                                       llk ? o_llk.d + ck.base : nullptr, seg_sum ? o_sum.d + ck.s0 : nullptr, nullptr));
+        }
+        if ((rc = o_llk.finish())) return rc;
+        return o_sum.finish();
+    }
+    // launch-bound walk: per segment one model upload, the single-model log-likelihood kernel, the clamp
+    OneModel om;
+    if (seg_sum) GCHK(hipMemsetAsync(o_sum.d, 0, (size_t)nseg * sizeof(double), c->stream));
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
+        if (n <= 0) continue;
+        if ((rc = om.set(c, b, seg_model[s]))) return rc;
+        XView sub;
+        sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+        if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+        double *lse;
+        long *sb;
+        if ((rc = gmmiv_i_run_lse(c, om.g, sub, dt, n, &lse))) return rc;
+        if ((rc = segment_table(c, n, &sb))) return rc;
+        GCHK(gmmk_llk_seg_finalize(c->stream, lse, sb, 1, min_llk, max_llk, llk ? o_llk.d + f0 : nullptr, seg_sum ? o_sum.d + s : nullptr, nullptr));
+    }
+    if ((rc = o_llk.finish())) return rc;
+    return o_sum.finish();
+}
+
+int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                          const int32_t *seg_model, int64_t nseg, double *N, double *F, double *seg_llk)
+{
+    int rc = check_batch(c, b, "tv_stats_models");
+    if (rc) return rc;
+    if ((rc = check_segments(b, "tv_stats_models", T, seg_begin, seg_model, nseg))) return rc;
+    if (!N || !F) { gmmiv_set_error("tv_stats_models: N and F are required"); return GMMIV_ERR_ARG; }
+    if (nseg == 0) return GMMIV_OK;
+    XView xv;
+    if ((rc = xv.init(c, x, dt, T, ldx, b->D))) return rc;
+    const size_t SV = (size_t)b->C * b->D;
+    DevOut<double> o_n, o_f, o_l;
+    if ((rc = o_n.init(c, WS_T0, N, (size_t)nseg * b->C, false))) return rc;
+    if ((rc = o_f.init(c, WS_T1, F, (size_t)nseg * SV, false))) return rc;
+    if ((rc = o_l.init(c, WS_T4, seg_llk, 2 * (size_t)nseg, false))) return rc;
+    auto finish = [&]() { int r = o_n.finish(); if (!r) r = o_f.finish(); if (!r) r = o_l.finish(); return r; };
+    ModelPlan p;
+    const int64_t Tc = models_chunk_frames(c, b);
+    if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
+        if ((rc = upload_plan(c, p))) return rc;
+        const long nfb = model_tile_blocks(p.max_span);
+        const size_t span = (size_t)(p.max_span > 0 ? p.max_span : 1);
+        void *pt, *lse, *zb, *eit, *inv;
+        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        if ((rc = c->scratch(WS_LSE, span * sizeof(double), &lse))) return rc;
+        if ((rc = c->scratch(WS_Z, (size_t)b->nct * nfb * 2048, &zb))) return rc;
+        if ((rc = c->scratch(WS_EIT, (size_t)(b->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
+        if ((rc = c->scratch(WS_INV, span * (sizeof(double) + sizeof(int)), &inv))) return rc;
+        int *efin = (int *)((double *)inv + span);
+        bool first = true; // the first launch of the call restarts the kernel timers
+        for (size_t k = 0; k < p.chunks.size(); ++k) {
+            const ModelChunk &ck = p.chunks[k];
+            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
+            const void *xb = gmmiv_x_at(xv, dt, ck.base);
+            if (n > 0) {
+                XView sub;
+                sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+                if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+                if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
+                c->t_begin("k_llk_mfma", first);
+                first = false;
+                GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(), b->nct,
+                                       p.d_tiles + ck.tile_off, (long)ck.ntiles, (double *)lse, (int)(c->use_glds & 1), (double *)zb, nfb, (int *)eit,
+                                       (double *)inv, efin));
+                c->t_end();
+                GCHK(gmmk_count_dead(c->stream, (const double *)lse + (f0 - ck.base), (long)n, c->d_zero_llk));
+            }
+            // every (segment, c < C) row is written by exactly one wave (zeros for an empty segment, whose likelihood blocks are never read)
+            c->t_begin("k_stats_z", k == 0);
+            GCHK(gmmk_stats_z(c->stream, b->KS, 0, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
+                              (const double *)inv, efin, 1.0, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
+                              o_f.d + (size_t)ck.s0 * SV, 1, 0, c->prune_thr()));
+            c->t_end();
+            if (seg_llk)
+                GCHK(gmmk_llk_seg_finalize(c->stream, (const double *)lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), 0.0, 0.0, nullptr, nullptr,
+                                           o_l.d + 2 * (size_t)ck.s0));
+        }
+        return finish();
+    }
+    // launch-bound walk: per segment one model upload, the single-model log-likelihood kernel and the recomputing statistics kernel
+    // (k_stats_mfma; the generic posteriors + GEMM for vectSize > 80) -- what gmmiv_tv_stats runs when the stored-likelihood path
+    // does not apply
+    OneModel om;
+    GCHK(hipMemsetAsync(o_n.d, 0, (size_t)nseg * b->C * sizeof(double), c->stream));
+    GCHK(hipMemsetAsync(o_f.d, 0, (size_t)nseg * SV * sizeof(double), c->stream));
+    if (seg_llk) GCHK(hipMemsetAsync(o_l.d, 0, 2 * (size_t)nseg * sizeof(double), c->stream));
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
+        if (n <= 0) continue;
+        if ((rc = om.set(c, b, seg_model[s]))) return rc;
+        const gmmiv_gmm *g = om.g;
+        XView sub;
+        sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+        if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+        double *lse;
+        long *sb;
+        if ((rc = gmmiv_i_run_lse(c, g, sub, dt, n, &lse))) return rc;
+        if ((rc = segment_table(c, n, &sb))) return rc;
+        double *Nrow = o_n.d + (size_t)s * b->C, *Frow = o_f.d + (size_t)s * SV;
+        if (g->KS == GMMK_KS_GENERIC) {
+            const int NC = g->D + 2 - (g->D & 1); // [x | 1] padded to an even width
+            void *S;
+            if ((rc = c->scratch(WS_PART, (size_t)g->C * NC * sizeof(double), &S))) return rc;
+            if ((rc = gmmiv_i_generic_gamma_gemm(c, g, sub, dt, 0, n, lse, false, NC, (double *)S))) return rc;
+            GCHK(gmmk_scatter_nf(c->stream, g->C, g->D, NC, (const double *)S, Nrow, Frow));
+        } else {
+            c->t_begin("k_stats_mfma", s == 0);
+            GCHK(gmmk_stats(c->stream, g->KS, 0, dt == GMMIV_F64, sub.d, sub.ldx, g->D, g->C, g->Pt, g->nct, lse, 0.0, sb, 1, Nrow, Frow, 1,
+                            (int)c->wg_waves, c->prune_arg()));
+            c->t_end();
+        }
+        if (seg_llk) GCHK(gmmk_llk_seg_finalize(c->stream, lse, sb, 1, 0.0, 0.0, nullptr, nullptr, o_l.d + 2 * (size_t)s));
+    }
+    return finish();
+}
+
+// ---- computeMAP for the batch -----------------------------------------------------------------------------------------------------------
+int gmmiv_map_adapt_models(gmmiv_ctx *c, int G, int C, int D, const double *N, const double *F, const double *count, int64_t count_stride,
+                           const double *w0, const double *mean0, const double *cur_mean, int64_t cur_stride, int method, int mean_adapt,
+                           int weight_adapt, double mean_reg, double weight_reg, double mean_alpha, double *mean_out, double *w_out)
+{
+    if (!c || G < 0 || C <= 0 || D <= 0 || !N || !F || !count || count_stride < 1 || !w0 || !mean0 || !cur_mean || cur_stride < 0 || !mean_out ||
+        method < GMMIV_MAP_NONE || method > GMMIV_MAP_CONST2) {
+        gmmiv_set_error("map_adapt_models: bad argument");
+        return GMMIV_ERR_ARG;
+    }
+    const size_t CD = (size_t)C * D;
+    if (cur_stride && cur_stride < (int64_t)CD) { gmmiv_set_error("map_adapt_models: cur_stride must be 0 (shared) or at least C * D"); return GMMIV_ERR_ARG; }
+    if (G == 0) return GMMIV_OK;
+    GBIND(c);
+    int rc;
+    DevIn<double> i_n, i_f, i_c, i_w0, i_m0, i_cur;
+    DevOut<double> o_m, o_w;
+    if ((rc = i_n.init(c, WS_T2, N, (size_t)G * C)) || (rc = i_f.init(c, WS_T3, F, (size_t)G * CD)) ||
+        (rc = i_c.init(c, WS_T4, count, (size_t)(G - 1) * count_stride + 1)) || (rc = i_w0.init(c, WS_T5, w0, (size_t)C)) ||
+        (rc = i_m0.init(c, WS_T6, mean0, CD)) || (rc = i_cur.init(c, WS_T7, cur_mean, cur_stride ? (size_t)(G - 1) * cur_stride + CD : CD)) ||
+        (rc = o_m.init(c, WS_T8, mean_out, (size_t)G * CD, false)) || (rc = o_w.init(c, WS_T9, w_out, (size_t)G * C, false)))
+        return rc;
+    c->t_begin("k_map_adapt");
+    GCHK(gmmk_map_adapt_models(c->stream, G, C, D, i_n.d, i_f.d, i_c.d, (long)count_stride, i_w0.d, i_m0.d, i_cur.d, (long)cur_stride, method, mean_adapt,
+                               weight_adapt, mean_reg, weight_reg, mean_alpha, o_m.d, w_out ? o_w.d : nullptr));
+    c->t_end();
+    if ((rc = o_m.finish())) return rc;
+    if ((rc = o_w.finish())) return rc;
+    // host inputs were staged with asynchronous copies from the caller's arrays
+    if (!o_m.host && !o_w.host && !(gmmiv_is_device_ptr(N) && gmmiv_is_device_ptr(F) && gmmiv_is_device_ptr(count) && gmmiv_is_device_ptr(w0) &&
+                                    gmmiv_is_device_ptr(mean0) && gmmiv_is_device_ptr(cur_mean)))
+        GCHK(hipStreamSynchronize(c->stream));
+    return GMMIV_OK;
+}
+
+} // extern "C"

@@ -36,9 +36,11 @@ enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, 
        WS_T9, WS_TIV, WS_LP, WS_AUX, WS_SLAB, WS_SLOTS, WS_FLAGS, WS_Z, WS_EIT, WS_INV,
        WS_GFLAG, WS_NORM, WS_FEAT_OFF, WS_FEAT_OUT, WS_FEAT_IDX, WS_FEAT_M0, WS_FEAT_M1, WS_FEAT_M2, WS_FEAT_M3,
        WS_NORM_OFF, WS_NORM_STATE, WS_NORM_DECAY,
+       WS_MB_PT, WS_MB_TILES, WS_MB_IDS, WS_MB_SEG,
        WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask;
                    // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables);
                    // WS_NORM_*: gmmiv_feat_norm_online (chunk offsets of the files, the carried states, the chunks' decay products)
+                   // WS_MB_*: gmmiv_*_models (the packed models of a chunk, the tile tables, the model lists, the segment bounds of all chunks)
 
 struct gmmiv_ctx {
     int device = 0;
@@ -95,6 +97,9 @@ struct gmmiv_ctx {
     // 1.1 s for 30 GB, 2.3 s for 60 GB on the FIRST call of a context in a process that had held other buffers, against 0.25 ms for
     // 14 GB.  Rounds 1-3 used 64 GiB: 0.4 % more throughput for up to 2.3 s and 46 GB.
     long z_scratch_mb = 16384;
+    // gmmiv_*_models: MiB of packed models per chunk of segments (2 MiB per model at 2048 x 60: 1024 models; the pack pass writes what
+    // the log-likelihood kernel then reads at least once, so a larger scratch buys nothing but fewer launches)
+    long models_scratch_mb = 2048;
     int n_cu = 256;
     // gmmiv_score_plda: K_n = (n FTJF + I)^-1 and log det K_n per session count n, kept while FTJF stays the same matrix
     // (each costs an O(rankF^3) inverse on the host: 3 ms per call at rankF = 200 when recomputed every time)
@@ -187,6 +192,17 @@ struct gmmiv_ctx {
         }
         return tot;
     }
+};
+
+// G models of one shape (include/gmmiv.h): compact device copies, [G x ..] or one shared row (stride 0), and the constants a_c [G x Cpa]
+struct gmmiv_gmm_batch {
+    gmmiv_ctx *ctx = nullptr;
+    int G = 0, C = 0, D = 0, KS = 0, nct = 0, Cp64 = 0, Cpa = 0;
+    double *w = nullptr, *mean = nullptr, *iv = nullptr, *a = nullptr, *lwc = nullptr;
+    size_t cap_w = 0, cap_mean = 0, cap_iv = 0; // doubles allocated
+    long sw = 0, sm = 0, si = 0;                // doubles between consecutive models, 0 = shared
+    bool loaded = false;
+    size_t packed_doubles() const { return (size_t)nct * (2 * KS + 2) * 64; }
 };
 
 bool gmmiv_is_device_ptr(const void *p);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kopts.h"
+#include "../../include/gmmiv.h" // gmmiv_model_tile
 
 #define GMMK_KS_GENERIC 99 // "no MFMA instantiation for this vectSize": every KS > 15 / KS <= 15 test of the callers routes it to the fallback side
 #define GMMK_MAX_DIM 4096  // the generic kernels keep 4 frames x D doubles in LDS
@@ -63,6 +64,25 @@ int gmmk_gather_runs(hipStream_t st, int x_f64, const void *x, long ldx, int D, 
 // stats_z.hip / k_llk_mfma<WZ>: scaled likelihoods written once by the log-likelihood kernel, statistics from them
 int gmmk_llk_z(hipStream_t st, int KS, int x_f64, const void *x, long T, long ldx, int D, const double *Pt, int nct,
                double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv, int *efin);
+// k_llk_mfma<.., MM>: a model per segment (gmmiv_*_models).  tiles: DEVICE array of ntiles entries (gmmiv_plan_model_tiles; frame numbers
+// relative to x / lse / inv / efin / zbuf block 0), Pt: the packed models of the call's chunk, pt_stride doubles apart.  zbuf / eit hold
+// nfb >= ceil(last written frame / 16) blocks per Gaussian tile; only rows inside the tiles' windows are written.  -1: no instantiation
+int gmmk_llk_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
+                    const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds);
+int gmmk_llk_z_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
+                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv,
+                      int *efin);
+// constants of G models in one launch (tables at p + g * stride, stride 0 = shared; a / lwc [G x Cp]); packed operands of the n models
+// ids[0..n) (device array) into Pt + slot * nct (2 KS + 2) 64 in one launch -- the arithmetic of gmmk_pack_model, the same bits
+int gmmk_const_models(hipStream_t st, int G, int C, int Cp, int D, const double *w, long sw, const double *mean, long sm, const double *iv,
+                      long si, double *a, double *lwc);
+int gmmk_pack_models(hipStream_t st, int n, const int *ids, int C, int Cp, int D, int KS, int nct, const double *mean, long sm,
+                     const double *iv, long si, const double *a, double *Pt);
+int gmmk_llk_seg_finalize(hipStream_t st, const double *lse, const long *sb, long nseg, double lo, double hi, double *llk_out, double *seg_sum,
+                          double *seg_llk); // per segment [sb[s], sb[s+1]): clamped values, their sum, {sum, count} of the finite raw values
+int gmmk_map_adapt_models(hipStream_t st, int G, int C, int D, const double *N, const double *F, const double *count, long count_stride,
+                          const double *w0, const double *mean0, const double *cur, long cur_stride, int method, int mean_adapt,
+                          int weight_adapt, double mean_reg, double weight_reg, double mean_alpha, double *mean_out, double *w_out);
 // k_llk_mfma<TC>: candidates of the top-C' selection collected in the log-likelihood kernel (see gmm_kernels.hip), ranked by
 // gmmk_topc_rank (topc_z.hip)
 int gmmk_topc_cap(void);

@@ -20,12 +20,10 @@ typedef double d2v __attribute__((ext_vector_type(2)));
 // Model packing
 // -------------------------------------------------------------------------------------------
 // a_c = log w_c - D/2 log 2pi + 1/2 sum log iv - 1/2 sum mu^2 iv   (log(w cst) - mu'S^-1mu/2)
-__global__ void k_gmm_const(int C, int Cp, int D, const double *__restrict__ w,
-                            const double *__restrict__ mean, const double *__restrict__ iv,
-                            double *__restrict__ a, double *__restrict__ logwcst)
+// (one body for the single model and the batch of models: model g of a batch gets the bits gmmiv_gmm_create would give it)
+__device__ __forceinline__ void gmm_const_one(int c, int C, int D, const double *__restrict__ w, const double *__restrict__ mean,
+                                              const double *__restrict__ iv, double *__restrict__ a, double *__restrict__ logwcst)
 {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= Cp) return;
     if (c >= C) { a[c] = GMMIV_NEG_BIG; logwcst[c] = GMMIV_NEG_BIG; return; }
     double sl = 0.0, sm = 0.0;
     for (int d = 0; d < D; ++d) {
@@ -39,20 +37,33 @@ __global__ void k_gmm_const(int C, int Cp, int D, const double *__restrict__ w,
     logwcst[c] = lc;
     a[c] = fmax(lc - 0.5 * sm, GMMIV_NEG_BIG);
 }
+__global__ void k_gmm_const(int C, int Cp, int D, const double *__restrict__ w,
+                            const double *__restrict__ mean, const double *__restrict__ iv,
+                            double *__restrict__ a, double *__restrict__ logwcst)
+{
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= Cp) return;
+    gmm_const_one(c, C, D, w, mean, iv, a, logwcst);
+}
+// batch of models (blockIdx.y = model g): tables at p + g * stride, stride 0 = shared; a / logwcst [G x Cp]
+__global__ void k_gmm_const_batch(int C, int Cp, int D, const double *__restrict__ w, long sw, const double *__restrict__ mean, long sm,
+                                  const double *__restrict__ iv, long si, double *__restrict__ a, double *__restrict__ logwcst)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t g = blockIdx.y;
+    if (c >= Cp) return;
+    gmm_const_one(c, C, D, w + g * sw, mean + g * sm, iv + g * si, a + g * Cp, logwcst + g * Cp);
+}
 
 // Pt[ct][row][lane]: B operands of the logit GEMM in MFMA lane order (lane = 16 q + j:
 // Gaussian c = 16 ct + j, contraction index k = 4 s + q).
 //   rows 0..KS-1      mu iv      (x part)        rows KS..2KS-1   -iv/2   (x^2 part)
 //   row 2KS           a_c replicated over q (accumulator init of the LLK kernel)
 //   row 2KS+1         const step of the statistics kernel: q=0 -> a_c, q=1 -> -1, else 0
-__global__ void k_gmm_pack(int C, int D, int KS, int nct, const double *__restrict__ mean,
-                           const double *__restrict__ iv, const double *__restrict__ a,
-                           double *__restrict__ Pt)
+__device__ __forceinline__ double gmm_pack_one(long e, int C, int D, int KS, const double *__restrict__ mean,
+                                               const double *__restrict__ iv, const double *__restrict__ a)
 {
     const int NR = 2 * KS + 2;
-    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)nct * NR * 64;
-    if (e >= total) return;
     int lane = e & 63;
     int row = (e >> 6) % NR;
     int ct = (e >> 6) / NR;
@@ -71,7 +82,26 @@ __global__ void k_gmm_pack(int C, int D, int KS, int nct, const double *__restri
     } else {
         v = q == 0 ? (c < C ? fmax(a[c], GMMIV_PAD_LOGIT) : GMMIV_PAD_LOGIT) : (q == 1 ? -1.0 : 0.0);
     }
-    Pt[e] = v;
+    return v;
+}
+__global__ void k_gmm_pack(int C, int D, int KS, int nct, const double *__restrict__ mean,
+                           const double *__restrict__ iv, const double *__restrict__ a,
+                           double *__restrict__ Pt)
+{
+    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long total = (long)nct * (2 * KS + 2) * 64;
+    if (e >= total) return;
+    Pt[e] = gmm_pack_one(e, C, D, KS, mean, iv, a);
+}
+// batch: blockIdx.y = slot of the chunk's packed scratch, model ids[slot] of the batch goes to Pt + slot * total
+__global__ void k_gmm_pack_batch(int C, int Cp, int D, int KS, int nct, const int *__restrict__ ids, const double *__restrict__ mean, long sm,
+                                 const double *__restrict__ iv, long si, const double *__restrict__ a, double *__restrict__ Pt)
+{
+    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long total = (long)nct * (2 * KS + 2) * 64;
+    if (e >= total) return;
+    const size_t g = (size_t)ids[blockIdx.y];
+    Pt[(size_t)blockIdx.y * total + e] = gmm_pack_one(e, C, D, KS, mean + g * sm, iv + g * si, a + g * Cp);
 }
 
 // transposed copies for the VALU top-C kernel: meanT[d][Cp], ivT[d][Cp] (pads: mean 0, iv 0)
@@ -123,14 +153,21 @@ __global__ void k_gmm_transpose(int C, int Cp, int D, const double *__restrict__
 #ifndef K1_PLAIN_SHARED
 #define K1_PLAIN_SHARED 1
 #endif
-template <int KS, typename XT, int NW, int MODE>
+// MM (a model per segment, gmmiv_*_models): one workgroup per entry of `tiles` (gmmiv_plan_model_tiles, include/gmmiv.h) instead of
+// one per 256 consecutive frames.  Three differences: the packed model is Pt + entry.model * pt_stride; frames of the tile outside
+// the entry's window [lo, hi) are loaded as 0; and none of their outputs is written -- in a 16-frame block that the window cuts, the
+// 32-byte per-lane likelihood store and the 16-byte exponent store become per-row stores (the test is per block and wave: uniform).
+// The arithmetic of a frame does not depend on its row in the tile: the same bits as the plain kernel under that model.
+template <int KS, typename XT, int NW, int MODE, bool MM = false>
 __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict__ x, long T, long ldx, int D,
                                                   const double *__restrict__ Pt, int nct,
                                                   double *__restrict__ lse_out, int use_glds, int dbg,
                                                   double *__restrict__ zbuf, long nfb, int *__restrict__ eit,
-                                                  double *__restrict__ inv_out, int *__restrict__ efin_out)
+                                                  double *__restrict__ inv_out, int *__restrict__ efin_out,
+                                                  const gmmiv_model_tile *__restrict__ tiles, long pt_stride)
 {
     constexpr bool WZ = MODE == 1, TC = MODE == 2;
+    static_assert(!MM || (MODE != 2 && NW == 8), "a model per segment: plain and stored-likelihood modes, 8 waves");
     // dbg (timing experiments only, results are wrong when != 0): 1 = no log-sum-exp epilogue,
     // 2 = additionally no per-tile staging / barrier, 3 = additionally B operands not re-read from LDS
     constexpr int NR = 2 * KS + 2;
@@ -145,7 +182,14 @@ __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict_
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i16 = lane & 15, q = lane >> 4;
-    const long tb = (long)blockIdx.x * (NW * 32) + wave * 32;
+    long tb0 = (long)blockIdx.x * (NW * 32);
+    long wlo = 0, whi = 0, olo = 0, ohi = 0; // MM: the frames evaluated, and the (wider, by < 16 rows) range whose likelihood rows are written
+    if constexpr (MM) {
+        const gmmiv_model_tile me = tiles[blockIdx.x];
+        tb0 = me.first; wlo = me.lo; whi = me.hi; olo = me.lo - me.pad_lo; ohi = me.hi + me.pad_hi;
+        Pt += (size_t)me.model * pt_stride;
+    }
+    const long tb = tb0 + wave * 32;
     gexp_tab_init(etab, tid, NW * 64);
     if (TC) ccnt[tid >> 1] = 0; // NW * 32 counters
 
@@ -161,7 +205,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict_
         for (int s = 0; s < KS; ++s) {
             const int k = 4 * s + q;
             double v = 0.0;
-            if (t < T && k < D) v = feat_load<XT>::get(x, t * ldx + k);
+            if ((MM ? (t >= wlo && t < whi) : t < T) && k < D) v = feat_load<XT>::get(x, t * ldx + k);
             A[h][s] = v;
             if (!TC) A[h][NA - KS + s] = v * v;
         }
@@ -432,6 +476,32 @@ __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict_
                     for (int h = 0; h < 2; ++h) asm volatile("" ::"v"(acc[g][h]));
                 return;
             }
+            if constexpr (MM) {
+                // per 16-frame block h of this wave (uniform): wholly inside the tile's rows -> the stores of the plain kernel; cut by
+                // them -> row by row; outside -> nothing (another workgroup owns the block, or nobody reads it)
+                typedef int i4 __attribute__((ext_vector_type(4)));
+                int *ew = eit + (size_t)te * (nfb * 16) + tb + 4 * q;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const long b0 = tb + 16 * h;
+                    if (b0 >= olo && b0 + 16 <= ohi) {
+#pragma unroll
+                        for (int g = 0; g < GT; ++g) __builtin_nontemporal_store(acc[g][h], (d4 *)(zw + ((size_t)g * nfb + h) * 256));
+                        if (i16 == 0) *(i4 *)(ew + h * 16) = (i4){E[h][0], E[h][1], E[h][2], E[h][3]};
+                    } else if (b0 + 16 > olo && b0 < ohi) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const long t = b0 + q + 4 * r; // row r of this lane = frame 4 r + q of the block, exponent slot 4 q + r
+                            if (t >= olo && t < ohi) {
+#pragma unroll
+                                for (int g = 0; g < GT; ++g) zw[((size_t)g * nfb + h) * 256 + r] = acc[g][h][r];
+                                if (i16 == 0) ew[h * 16 + r] = E[h][r];
+                            }
+                        }
+                    }
+                }
+                return;
+            }
 #pragma unroll
             for (int g = 0; g < GT; ++g)
 #pragma unroll
@@ -543,7 +613,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_llk_mfma(const void *__restrict_
                 if (i16 == 0 && t < T) { lse_out[t] = (double)thf[h][r]; inv_out[t] = sv; efin_out[t] = Em; }
                 continue;
             }
-            if (i16 == 0 && t < T) {
+            if (i16 == 0 && (MM ? (t >= wlo && t < whi) : t < T)) {
                 // A ZERO-LIKELIHOOD frame (include/gmmiv.h, "degenerate inputs"): the scaled sum is not a positive finite number, or
                 // even the largest w_c lk_c is below 2^-1075 -- 0 in the fp64 arithmetic of the reference (far below that the integer
                 // exponent of gexp_tab_reduce saturates and nothing in the row is trustworthy).  log-likelihood -inf, scale 0: every
@@ -1298,7 +1368,178 @@ static int launch_llk(hipStream_t st, const void *x, long T, long ldx, int D, co
     const size_t lds = 2 * 2 * NR * 64 * sizeof(double) + GEXP_TAB_N * sizeof(double) + (MODE == 2 ? NW * 32 * sizeof(int) : 0); // two model stages + the exp table (+ TC: candidate counters)
     HIPCHK((gmmiv_lds_attr<k_llk_mfma<KS, XT, NW, MODE>>(lds))); // per (device, kernel): lds_attr.h
     const unsigned grid = (unsigned)((T + NW * 32 - 1) / (NW * 32));
-    k_llk_mfma<KS, XT, NW, MODE><<<grid, NW * 64, lds, st>>>(x, T, ldx, D, Pt, nct, lse, use_glds & 1, use_glds >> 8, zbuf, nfb, eit, inv, efin);
+    k_llk_mfma<KS, XT, NW, MODE><<<grid, NW * 64, lds, st>>>(x, T, ldx, D, Pt, nct, lse, use_glds & 1, use_glds >> 8, zbuf, nfb, eit, inv, efin, nullptr, 0);
+    return (int)hipGetLastError();
+}
+
+// a model per segment: one 8-wave workgroup per entry of the tile table (device array); Pt = the chunk's packed models, pt_stride doubles apart
+template <int KS, typename XT, int MODE>
+static int launch_llk_models(hipStream_t st, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct, const gmmiv_model_tile *tiles,
+                             long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv, int *efin)
+{
+    constexpr int NR = 2 * KS + 2;
+    const size_t lds = 2 * 2 * NR * 64 * sizeof(double) + GEXP_TAB_N * sizeof(double);
+    HIPCHK((gmmiv_lds_attr<k_llk_mfma<KS, XT, 8, MODE, true>>(lds))); // per (device, kernel): lds_attr.h
+    k_llk_mfma<KS, XT, 8, MODE, true><<<(unsigned)ntiles, 8 * 64, lds, st>>>(x, 0, ldx, D, Pt, nct, lse, use_glds & 1, 0, zbuf, nfb, eit, inv, efin, tiles, pt_stride);
+    return (int)hipGetLastError();
+}
+#define MM_CASE(K, MODE)                                                                                                                      \
+    case K:                                                                                                                                   \
+        return x_f64 ? launch_llk_models<K, double, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, zbuf, nfb, eit, inv, efin) \
+                     : launch_llk_models<K, float, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, zbuf, nfb, eit, inv, efin);
+int gmmk_llk_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
+                    const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds)
+{
+    if (ntiles <= 0) return 0;
+    double *zbuf = nullptr, *inv = nullptr;
+    int *eit = nullptr, *efin = nullptr;
+    const long nfb = 0;
+    switch (KS) {
+        MM_CASE(4, 0) MM_CASE(8, 0) MM_CASE(15, 0)
+    }
+    return -1;
+}
+int gmmk_llk_z_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
+                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv,
+                      int *efin)
+{
+    if (ntiles <= 0) return 0;
+    switch (KS) {
+        MM_CASE(4, 1) MM_CASE(8, 1) MM_CASE(15, 1)
+    }
+    return -1;
+}
+#undef MM_CASE
+
+int gmmk_const_models(hipStream_t st, int G, int C, int Cp, int D, const double *w, long sw, const double *mean, long sm, const double *iv,
+                      long si, double *a, double *lwc)
+{
+    if (G <= 0) return 0;
+    k_gmm_const_batch<<<dim3((unsigned)((Cp + 255) / 256), (unsigned)G), 256, 0, st>>>(C, Cp, D, w, sw, mean, sm, iv, si, a, lwc);
+    return (int)hipGetLastError();
+}
+int gmmk_pack_models(hipStream_t st, int n, const int *ids, int C, int Cp, int D, int KS, int nct, const double *mean, long sm,
+                     const double *iv, long si, const double *a, double *Pt)
+{
+    if (n <= 0) return 0;
+    const long total = (long)nct * (2 * KS + 2) * 64;
+    k_gmm_pack_batch<<<dim3((unsigned)((total + 255) / 256), (unsigned)n), 256, 0, st>>>(C, Cp, D, KS, nct, ids, mean, sm, iv, si, a, Pt);
+    return (int)hipGetLastError();
+}
+
+// per segment s = frames [sb[s], sb[s + 1]) of lse (one workgroup each): llk_out[t] = clamp(lse[t]) (nullable), seg_sum[s] = their sum
+// (nullable), seg_llk[2 s] = sum of the finite raw values, [2 s + 1] = their number (nullable).  Fixed order: 256 strided partial sums,
+// the wave's butterfly, the four waves left to right -- a segment's sums do not depend on its neighbours.
+__global__ __launch_bounds__(256) void k_llk_seg_finalize(const double *__restrict__ lse, const long *__restrict__ sb, double lo, double hi,
+                                                         double *__restrict__ llk_out, double *__restrict__ seg_sum,
+                                                         double *__restrict__ seg_llk)
+{
+    __shared__ double red[3][4];
+    const int s = blockIdx.x;
+    const long b = sb[s], e = sb[s + 1];
+    double sc = 0.0, sr = 0.0, sn = 0.0;
+    for (long t = b + threadIdx.x; t < e; t += 256) {
+        const double v = lse[t];
+        const double c = fmin(fmax(v, lo), hi); // fmax(NaN, lo) = lo
+        if (llk_out) llk_out[t] = c;
+        sc += c;
+        const bool fin = v > -__builtin_inf() && v < __builtin_inf();
+        sr += fin ? v : 0.0;
+        sn += fin ? 1.0 : 0.0;
+    }
+    sc = wave_sum_f64(sc);
+    sr = wave_sum_f64(sr);
+    sn = wave_sum_f64(sn);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[0][wave] = sc; red[1][wave] = sr; red[2][wave] = sn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (seg_sum) seg_sum[s] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        if (seg_llk) {
+            seg_llk[2 * s] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+            seg_llk[2 * s + 1] = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+        }
+    }
+}
+int gmmk_llk_seg_finalize(hipStream_t st, const double *lse, const long *sb, long nseg, double lo, double hi, double *llk_out, double *seg_sum,
+                          double *seg_llk)
+{
+    if (nseg <= 0) return 0;
+    k_llk_seg_finalize<<<(unsigned)nseg, 256, 0, st>>>(lse, sb, lo, hi, llk_out, seg_sum, seg_llk);
+    return (int)hipGetLastError();
+}
+
+// computeMAP for G models (include/gmmiv.h, gmmiv_map_adapt_models): the mean branch, one thread per (g, c, d).  Every operation is
+// rounded on its own like the host's computeMAP* (no fma contraction).
+__device__ __forceinline__ double map_ml_weight(double n, double count) { return count > 0.0 ? n / count : 0.0; }
+__global__ __launch_bounds__(256) void k_map_adapt_mean(long total, int C, int D, const double *__restrict__ N, const double *__restrict__ F,
+                                                       const double *__restrict__ count, long count_stride, const double *__restrict__ w0,
+                                                       const double *__restrict__ mean0, const double *__restrict__ cur, long cur_stride,
+                                                       int method, int mean_adapt, double mean_reg, double mean_alpha,
+                                                       double *__restrict__ mean_out)
+{
+#pragma clang fp contract(off)
+    const long CD = (long)C * D;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long g = e / CD, cd = e - g * CD;
+        const int c = (int)(cd / D);
+        const double n = N[g * C + c], cnt = count[g * count_stride];
+        const double w = map_ml_weight(n, cnt);
+        const double ml = n > 0.0 ? F[e] / n : cur[g * cur_stride + cd];
+        const double m0 = mean0[cd];
+        double r = ml;
+        if (method != GMMIV_MAP_NONE && !mean_adapt) r = m0;
+        else if (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) {
+            const double alpha = w * (double)(unsigned long)cnt;
+            const double a = alpha / (alpha + mean_reg);
+            r = (1 - a) * m0 + a * ml;
+        } else if (method == GMMIV_MAP_CONST) {
+            r = (mean_alpha * m0) + ((1 - mean_alpha) * ml);
+        } else if (method == GMMIV_MAP_CONST2) {
+            r = ((mean_alpha * w0[c] * m0) + ((1 - mean_alpha) * w * ml)) / (w0[c] * mean_alpha + w * (1 - mean_alpha));
+        }
+        mean_out[e] = r;
+    }
+}
+// the weight branch: one workgroup per model, sum over c = 0 .. C-1 left to right like the reference's loop
+__global__ __launch_bounds__(256) void k_map_adapt_weight(int C, const double *__restrict__ N, const double *__restrict__ count, long count_stride,
+                                                         const double *__restrict__ w0, int method, int weight_adapt, double weight_reg,
+                                                         double *__restrict__ w_out)
+{
+#pragma clang fp contract(off)
+    __shared__ double ssum;
+    const size_t g = blockIdx.x;
+    const double cnt = count[g * count_stride];
+    const bool occ = (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) && weight_adapt;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const double w = map_ml_weight(N[g * C + c], cnt);
+        double r = method == GMMIV_MAP_NONE ? w : w0[c];
+        if (occ) {
+            const double alpha = w * (double)(unsigned long)cnt, a = alpha / (alpha + weight_reg);
+            r = a * w + (1 - a) * w0[c];
+        }
+        w_out[g * C + c] = r;
+    }
+    if (!occ) return; // uniform
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int c = 0; c < C; ++c) s += w_out[g * C + c];
+        ssum = s;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) w_out[g * C + c] /= ssum;
+}
+int gmmk_map_adapt_models(hipStream_t st, int G, int C, int D, const double *N, const double *F, const double *count, long count_stride,
+                          const double *w0, const double *mean0, const double *cur, long cur_stride, int method, int mean_adapt,
+                          int weight_adapt, double mean_reg, double weight_reg, double mean_alpha, double *mean_out, double *w_out)
+{
+    if (G <= 0) return 0;
+    const long total = (long)G * C * D;
+    const unsigned blocks = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
+    k_map_adapt_mean<<<blocks, 256, 0, st>>>(total, C, D, N, F, count, count_stride, w0, mean0, cur, cur_stride, method, mean_adapt, mean_reg,
+                                             mean_alpha, mean_out);
+    if (w_out) k_map_adapt_weight<<<(unsigned)G, 256, 0, st>>>(C, N, count, count_stride, w0, method, weight_adapt, weight_reg, w_out);
     return (int)hipGetLastError();
 }
 

@@ -368,6 +368,77 @@ int liagpu_train_target_ex(int device, const float *x, long T, int D, const long
     })
 }
 
+// TrainTarget for MANY clients in one call (adaptModelBatch): client i owns the segments [client_begin[i], client_begin[i + 1]) of the
+// seg_begin / seg_len lists and starts from the world model; w_out [nclients x C], mean_out / cov_out [nclients x C * D]
+int liagpu_train_target_batch(int device, const float *x, long T, int D, const long *client_begin, long nclients, const long *seg_begin,
+                              const long *seg_len, int C, const double *w, const double *mean, const double *cov, const char *method, int nbTrainIt,
+                              double baggedP, int flags, const double *reg, double alphaMean, const long *norm, double *w_out, double *mean_out,
+                              double *cov_out)
+{
+    GUARD({
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD world = make_mixture(C, D, w, mean, cov);
+        std::vector<SegCluster> sel;
+        for (long i = 0; i < nclients; ++i) sel.push_back(make_cluster(seg_begin + client_begin[i], seg_len + client_begin[i], client_begin[i + 1] - client_begin[i]));
+        std::vector<MixtureGD> clients((size_t)nclients, world);
+        adaptModelBatch(fs, sel, world, clients, make_map_cfg(method, nbTrainIt, baggedP, flags, reg, alphaMean, norm));
+        for (long i = 0; i < nclients; ++i) {
+            memcpy(w_out + (size_t)i * C, clients[i].weights().data(), C * sizeof(double));
+            memcpy(mean_out + (size_t)i * C * D, clients[i].means().data(), (size_t)C * D * sizeof(double));
+            memcpy(cov_out + (size_t)i * C * D, clients[i].covs().data(), (size_t)C * D * sizeof(double));
+        }
+    })
+}
+
+// tools/bench_enroll.py: enrolment of nclients clients of frames_per_client frames each (client i = frames [i n, (i + 1) n)) from the world
+// model, timed on the host around the whole adaptation (features resident, the stream drained before and after): which = 0
+// adaptModelBatch, 1 = adaptModel client after client.  ms_out[reps]: every repetition (the caller drops warm-ups); after them one more pass
+// with the context's kernel timers on: kernel_ms[0..2] = k_llk_mfma, k_stats_z, k_gmm_pack of the LAST call of that pass (-1: not run).
+// warm_clients > 0: only that many clients in the first repetition.  mean0_out (nullable): the adapted means of client 0.
+int liagpu_bench_enroll(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
+                        const double *cov, int nbTrainIt, int which, int reps, long warm_clients, double *ms_out, double *kernel_ms, double *mean0_out)
+{
+    GUARD({
+        if (nclients * frames_per_client > T) throw Exception("bench_enroll: not enough frames");
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD world = make_mixture(C, D, w, mean, cov);
+        std::vector<SegCluster> sel((size_t)nclients);
+        for (long i = 0; i < nclients; ++i) {
+            Seg s;
+            s.begin = (unsigned long)(i * frames_per_client); s.length = (unsigned long)frames_per_client;
+            sel[(size_t)i].push_back(s);
+        }
+        MAPCfg cfg;
+        cfg.nbTrainIt = (unsigned long)nbTrainIt;
+        std::vector<MixtureGD> clients;
+        auto run = [&](long n) {
+            clients.assign((size_t)n, world);
+            if (which == 0) {
+                std::vector<SegCluster> part(sel.begin(), sel.begin() + n);
+                adaptModelBatch(fs, part, world, clients, cfg);
+            } else {
+                for (long i = 0; i < n; ++i) adaptModel(fs, sel[(size_t)i], world, clients[(size_t)i], cfg);
+            }
+            srv.sync();
+        };
+        for (int r = 0; r < reps; ++r) {
+            srv.sync();
+            const auto t0 = std::chrono::steady_clock::now();
+            run(r == 0 && warm_clients > 0 && warm_clients < nclients ? warm_clients : nclients);
+            ms_out[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 1);
+        run(nclients);
+        kernel_ms[0] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_llk_mfma");
+        kernel_ms[1] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_stats_z");
+        kernel_ms[2] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_gmm_pack");
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 0);
+        if (mean0_out) memcpy(mean0_out, clients[0].means().data(), (size_t)C * D * sizeof(double));
+    })
+}
+
 // computeMAP on its own (TrainTools.cpp:543-556; host arithmetic only -- no device is touched): w / mean / cov = the ML estimate in, the
 // adapted model out
 int liagpu_compute_map(int C, int D, const double *w0, const double *mean0, const double *cov0, double *w, double *mean, double *cov,

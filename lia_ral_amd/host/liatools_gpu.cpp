@@ -1347,6 +1347,122 @@ void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const Mix
     }
 }
 
+// adaptModel for MANY clients at once: every iteration is ONE selection of all clients' frames, one log-likelihood + statistics pass
+// with a model per client (gmmiv_tv_stats_models), one MAP kernel (gmmiv_map_adapt_models) and a device-to-device reload of the
+// batch -- statistics, ML estimate, MAP and the next iteration's models never leave the device; the clients' means come back once,
+// at the end.  Client i gets the model adaptModel(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg), called client
+// after client in that order, gives -- to the last bits of another summation order (N / F rows instead of the EM accumulator), not
+// bitwise.  Bagging: every client's selection of every iteration is drawn HERE, on the host, before any device work, in the rand() /
+// srand(trainIt) order the sequential calls would produce (client-major: client 0's nbTrainIt draws, each followed by srand(trainIt),
+// then client 1's, ...).
+// NOT batched: varAdapt (needs second-order statistics per segment), normalizeModel (a host pass over each client's model per
+// iteration) -- for those configurations, and for clients of different shapes, this function runs the per-client loop above.
+void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerClient, const MixtureGD &aprioriModel,
+                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg)
+{
+    const size_t G = selectedPerClient.size();
+    if (clientMixtures.size() != G) throw Exception("adaptModelBatch: one mixture per client is needed");
+    if (G == 0) return;
+    const unsigned long C = aprioriModel.getDistribCount(), D = aprioriModel.getVectSize();
+    bool batched = !mapCfg.varAdapt && !mapCfg.normalizeModel;
+    for (size_t i = 0; i < G && batched; ++i) batched = clientMixtures[i].getDistribCount() == C && clientMixtures[i].getVectSize() == D;
+    if (!batched) {
+        for (size_t i = 0; i < G; ++i) adaptModel(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg);
+        return;
+    }
+    const unsigned long nIt = mapCfg.nbTrainIt;
+    if (nIt == 0) return;
+    // the selections, in the sequential calls' order of draws
+    std::vector<std::vector<SegCluster>> bagged(G, std::vector<SegCluster>(nIt));
+    for (size_t i = 0; i < G; ++i)
+        for (unsigned long it = 0; it < nIt; ++it) {
+            baggedSegments(selectedPerClient[i], bagged[i][it], mapCfg.baggedFrameProbability, 3, 7); // before srand(), as adaptModel
+            srand((unsigned)it);
+        }
+    const int method = mapCfg.method == "MAPOccDep" ? GMMIV_MAP_OCC_DEP : mapCfg.method == "MAPModelBased" ? GMMIV_MAP_MODEL_BASED
+                     : mapCfg.method == "MAPConst" ? GMMIV_MAP_CONST : mapCfg.method == "MAPConst2" ? GMMIV_MAP_CONST2 : GMMIV_MAP_NONE;
+    // what computeMAP leaves in the tables this function does not adapt: the a-priori model's (after computeAll() for the two
+    // occupation-dependent methods, which recomputes covInv = 1 / cov); an unknown method keeps the ML estimate -- weights N / count,
+    // and variances, which need the second-order statistics: per-client loop
+    if (method == GMMIV_MAP_NONE) {
+        for (size_t i = 0; i < G; ++i) adaptModel(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg);
+        return;
+    }
+    MixtureGD prior = aprioriModel;
+    if (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) prior.computeAll();
+    const bool perClientW = mapCfg.weightAdapt && (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED);
+
+    GpuServer &srv = fs.server();
+    const size_t CD = (size_t)C * D;
+    struct Batch {
+        gmmiv_gmm_batch *h = nullptr;
+        ~Batch() { gmmiv_gmm_batch_destroy(h); }
+    } batch;
+    srv.check(gmmiv_gmm_batch_create(srv.ctx(), (int)G, (int)C, (int)D, &batch.h));
+    // device buffers of the loop: N | F | seg_llk | means (two, alternating) | weights | w0 | mean0 | the prior's weights | covInv
+    double *buf = (double *)srv.workspace(5, (G * C + G * CD + 2 * G + 2 * G * CD + G * C + 2 * C + 2 * CD) * sizeof(double));
+    double *dN = buf, *dF = dN + G * C, *dL = dF + G * CD, *dM[2] = {dL + 2 * G, dL + 2 * G + G * CD}, *dW = dM[1] + G * CD, *dW0 = dW + G * C,
+           *dMean0 = dW0 + C, *dPW = dMean0 + CD, *dPIv = dPW + C; // dPW / dPIv: the weights / covInv every later iteration reloads
+    hipStream_t st = (hipStream_t)srv.stream();
+    hipcheck(hipMemcpyAsync(dW0, aprioriModel.weights_c().data(), C * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+    hipcheck(hipMemcpyAsync(dMean0, aprioriModel.means_c().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+    hipcheck(hipMemcpyAsync(dPW, prior.weights_c().data(), C * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+    hipcheck(hipMemcpyAsync(dPIv, prior.covInvs().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+    // the models of the first iteration: the clients' own (usually all the world model: one shared table each)
+    bool same = true;
+    for (size_t i = 1; i < G && same; ++i)
+        same = clientMixtures[i].weights_c() == clientMixtures[0].weights_c() && clientMixtures[i].means_c() == clientMixtures[0].means_c() &&
+               clientMixtures[i].covInvs() == clientMixtures[0].covInvs();
+    long curStride = 0;
+    if (same) {
+        hipcheck(hipMemcpyAsync(dM[0], clientMixtures[0].means_c().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+        srv.sync();
+        srv.check(gmmiv_gmm_batch_load(batch.h, clientMixtures[0].weights_c().data(), 0, dM[0], 0, clientMixtures[0].covInvs().data(), 0));
+    } else {
+        std::vector<double> w(G * C), iv(G * CD), m(G * CD);
+        for (size_t i = 0; i < G; ++i) {
+            memcpy(&w[i * C], clientMixtures[i].weights_c().data(), C * sizeof(double));
+            memcpy(&m[i * CD], clientMixtures[i].means_c().data(), CD * sizeof(double));
+            memcpy(&iv[i * CD], clientMixtures[i].covInvs().data(), CD * sizeof(double));
+        }
+        hipcheck(hipMemcpyAsync(dM[0], m.data(), G * CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+        srv.sync();
+        srv.check(gmmiv_gmm_batch_load(batch.h, w.data(), (int64_t)C, dM[0], (int64_t)CD, iv.data(), (int64_t)CD));
+        curStride = (long)CD;
+    }
+    std::vector<int64_t> segBegin(G + 1);
+    std::vector<int32_t> segModel(G);
+    for (size_t i = 0; i < G; ++i) segModel[i] = (int32_t)i;
+    for (unsigned long it = 0; it < nIt; ++it) {
+        SegCluster all;
+        segBegin[0] = 0;
+        for (size_t i = 0; i < G; ++i) {
+            all.insert(all.end(), bagged[i][it].begin(), bagged[i][it].end());
+            segBegin[i + 1] = segBegin[i] + (int64_t)totalFrame(bagged[i][it]);
+        }
+        unsigned long n = 0;
+        const float *x = fs.select(all, n); // one gather of all clients' frames, client after client
+        FiniteScope fin(srv, fs);
+        srv.check(gmmiv_tv_stats_models(srv.ctx(), batch.h, x, GMMIV_F32, (int64_t)n, (int64_t)D, segBegin.data(), segModel.data(), (int64_t)G, dN, dF, dL));
+        double *cur = dM[it & 1], *out = dM[(it + 1) & 1];
+        srv.check(gmmiv_map_adapt_models(srv.ctx(), (int)G, (int)C, (int)D, dN, dF, dL + 1, 2, dW0, dMean0, cur, curStride, method, mapCfg.meanAdapt ? 1 : 0,
+                                         mapCfg.weightAdapt ? 1 : 0, mapCfg.meanReg, mapCfg.weightReg, mapCfg.meanAlpha, out, perClientW ? dW : nullptr));
+        if (it + 1 < nIt) // the next iteration's models: means (and adapted weights) straight from the device, the rest is the prior's
+            srv.check(gmmiv_gmm_batch_load(batch.h, perClientW ? dW : dPW, perClientW ? (int64_t)C : 0, out, (int64_t)CD, dPIv, 0));
+        curStride = (long)CD;
+    }
+    std::vector<double> means(G * CD), weights(perClientW ? G * C : 0);
+    hipcheck(hipMemcpyAsync(means.data(), dM[nIt & 1], G * CD * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    if (perClientW) hipcheck(hipMemcpyAsync(weights.data(), dW, G * C * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    srv.sync();
+    for (size_t i = 0; i < G; ++i) {
+        MixtureGD m = prior; // weights, variances (and covInv) as computeMAP leaves them
+        memcpy(m.means().data(), &means[i * CD], CD * sizeof(double));
+        if (perClientW) memcpy(m.weights().data(), &weights[i * C], C * sizeof(double));
+        clientMixtures[i] = m;
+    }
+}
+
 // ---- ComputeTest -------------------------------------------------------------------------------------
 std::vector<double> computeTestLLR(FeatureBuffer &fs, const SegCluster &selectedSegments, DeviceMixture &world,
                                    std::vector<DeviceMixture *> &clients, int topDistribsCount, bool complete,

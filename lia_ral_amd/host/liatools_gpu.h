@@ -137,6 +137,8 @@ class MixtureGD {
     std::vector<double> &means() { return _mean; }
     std::vector<double> &covs() { return _cov; }
     const std::vector<double> &covInvs() const { return _covInv; }
+    const std::vector<double> &weights_c() const { return _w; }
+    const std::vector<double> &means_c() const { return _mean; }
 
   private:
     unsigned long _c, _d;
@@ -349,6 +351,12 @@ void computeMAP(const MixtureGD &initModel, MixtureGD &client, unsigned long fra
 // client model = MAP(aprioriModel, EM estimate on the selected frames), nbTrainIt times
 void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const MixtureGD &aprioriModel,
                 MixtureGD &clientMixture, const MAPCfg &mapCfg);
+// The same for many clients at once (the client loop of TrainTarget.cpp:150-270): client i = adaptModel(fs, selectedPerClient[i],
+// aprioriModel, clientMixtures[i], mapCfg) called client after client in that order -- same bagging draws, results to the last bits of
+// another summation order -- with ONE statistics pass per iteration for all clients (gmmiv_tv_stats_models, a model per client) and the
+// MAP step on the device (gmmiv_map_adapt_models).  varAdapt, normalizeModel and an unknown MAPAlgo run the per-client loop.
+void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerClient, const MixtureGD &aprioriModel,
+                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg);
 
 // ---- ComputeTest (LIA_SpkDet/ComputeTest/src/ComputeTest.cpp:129-215) -----------------------------
 // LLR of each client against the world for one test file: per segment when segmentalMode, else one

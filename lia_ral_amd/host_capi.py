@@ -220,6 +220,28 @@ def train_target_ex(x, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, b
     return wo, mo, co
 
 
+def train_target_batch(x, client_begin, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, bagged_p=1.0, mean=True, var=False, weight=False,
+                       reg=(16.0, 16.0, 16.0), alpha_mean=0.75, normalize=False, normalize_mean_only=False, normalize_nb_it=1, device=0):
+    """TrainTarget for many clients at once (adaptModelBatch): client i owns the segments client_begin[i] .. client_begin[i + 1] of the
+    seg_begin / seg_len lists and starts from `world` -> (w [G, C], mean [G, C, D], cov [G, C, D]); row i is what train_target_ex gives
+    for client i when the clients are adapted one after the other in this order (var / normalize: it runs exactly that loop)."""
+    x = np.ascontiguousarray(x, np.float32)
+    T, D = x.shape
+    w, m, c = [np.ascontiguousarray(a, np.float64) for a in world]
+    C = len(w)
+    cb = np.ascontiguousarray(client_begin, np.int64); b = np.ascontiguousarray(seg_begin, np.int64); l = np.ascontiguousarray(seg_len, np.int64)
+    G = len(cb) - 1
+    assert len(b) == len(l) and cb[0] == 0 and cb[-1] == len(b)
+    lp = lambda a: a.ctypes.data_as(ct.POINTER(ct.c_long))
+    r = np.ascontiguousarray(reg, np.float64)
+    norm = (ct.c_long * 3)(int(normalize), int(normalize_mean_only), int(normalize_nb_it))
+    wo = np.empty((G, C)); mo = np.empty((G, C, D)); co = np.empty((G, C, D))
+    _chk(lib.liagpu_train_target_batch(device, x.ctypes.data_as(_fp), ct.c_long(T), D, lp(cb), ct.c_long(G), lp(b), lp(l), C, _d(w), _d(m), _d(c),
+                                       method.encode(), nb_it, ct.c_double(bagged_p), _map_flags(mean, var, weight), _d(r), ct.c_double(alpha_mean), norm,
+                                       _d(wo), _d(mo), _d(co)))
+    return wo, mo, co
+
+
 def compute_map(method, init, client, frame_count, mean=True, var=False, weight=False, reg=(16.0, 16.0, 16.0), alpha_mean=0.75):
     """computeMAP (TrainTools.cpp:543-556) on its own, host arithmetic only: init / client = (w, mean, cov) -> adapted (w, mean, cov)."""
     w0, m0, c0 = [np.ascontiguousarray(a, np.float64) for a in init]
