@@ -481,6 +481,33 @@ int gmmiv_map_adapt_models(gmmiv_ctx *ctx, int G, int C, int D, const double *N,
                            int method, int mean_adapt, int weight_adapt, double mean_reg, double weight_reg, double mean_alpha,
                            double *mean_out, double *w_out);
 
+/* computeMLLR (TrainTools.cpp:788-866) for G clients at once, from the statistics rows of gmmiv_tv_stats_models: one global affine
+ * transform of the a-priori means per client.  With xi_j = [1, mean0_j] (D + 1 values), a_j = N_gj / cov0_jp and the ML mean
+ * m_jp = F_gjp / N_gj, for every dimension p
+ *   G_p = sum_j a_j xi_j xi_j^T,   z_p = sum_j a_j m_jp xi_j,   W_g[p, :] = G_p^-1 z_p        (G_p symmetric, (D+1) x (D+1))
+ * and mean_out[g, j, :] = W_g[:, 0] + W_g[:, 1:] mean0_j.  The reference weights with occ_j = w_j frameCount = N_gj up to one factor
+ * common to G_p and z_p, so W does not depend on the frame count, on its truncation, or on the normalisation of the ML weights.  A
+ * Gaussian with N_gj = 0 is left out of both sums (its F row is never read into them).  Weights and variances of an MLLR client are
+ * the a-priori model's: nothing to compute here.
+ *   k_mllr_solve   one workgroup per (g, p): the augmented Gram matrix [xi | m]^T diag(a) [xi | m] on the fp64 matrix cores (lower
+ *                  16 x 16 tiles only), then a square-root-free Cholesky factorisation and the two substitutions in LDS.  No atomics:
+ *                  a client's result does not depend on G, on its place in the batch or on the chunking, and is the same bits on
+ *                  every run.  The reference divides by cov0 inside its sums and multiplies by an explicit inverse of G_p; the device
+ *                  divides once per Gaussian and substitutes through the factor -- the same result to within the rounding of a
+ *                  backward-stable solve (tests/test_gpu_mllr.py states the bar), not bitwise.  Dividing by the variance, as here and
+ *                  in the reference, against multiplying by a stored reciprocal 1 / cov0 is a difference of the same kind: within
+ *                  that bar, not bitwise.
+ *   status [G] (nullable): 0, or 1 + p for the first dimension p whose G_p met a pivot that is not positive and finite (fewer than
+ *                  D + 1 occupied Gaussians in general position, a client without frames, NaN statistics).  Such a client gets the
+ *                  identity transform W = [0 | I] and mean_out = mean0, bit for bit.  The call never reads the status back: with
+ *                  device arrays it only enqueues.
+ * W_out [G x D x (D+1)] and mean_out [G x C*D] are nullable, not both; every array may be host or device.  D <= 62
+ * (GMMIV_ERR_UNSUPPORTED above).  Kernel timers: "k_mllr_solve", "k_mllr_pack" (the padded [1 | mean0] table, once per call). */
+int gmmiv_mllr_adapt_models(gmmiv_ctx *ctx, int G, int C, int D, const double *N /* [G x C] */, const double *F /* [G x C*D] */,
+                            const double *mean0 /* [C*D] */, const double *cov0 /* [C*D] variances */,
+                            double *W_out /* [G x D x (D+1)], nullable */, double *mean_out /* [G x C*D], nullable */,
+                            int32_t *status /* [G], nullable */);
+
 /* ---- TVAcc i-vector maths (exact mode) -------------------------------------------------------
  * T: [R x C*D] row-major total-variability matrix; invvar: [C*D] UBM inverse variances.
  * substractM          AccumulateTVStat.cpp:1088-1105   F[u,c,:] -= mean[c,:] N[u,c]  (in place)

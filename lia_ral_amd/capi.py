@@ -1029,3 +1029,26 @@ class GmmBatch:
                                         int(bool(weight)), ct.c_double(reg[0]), ct.c_double(reg[2]), ct.c_double(alpha_mean), _ptr(mean_out),
                                         _ptr(w_out)))
         return mean_out, w_out
+
+    def mllr_adapt(self, N, F, mean0, cov0):
+        """computeMLLR for the G statistics rows (gmmiv_mllr_adapt_models) -> (W [G, D, D + 1], means [G, C*D], status [G] int32)."""
+        return mllr_adapt(self.ctx, N, F, mean0, cov0, C=self.C, D=self.D)
+
+
+def mllr_adapt(ctx, N, F, mean0, cov0, C=None, D=None):
+    """gmmiv_mllr_adapt_models: N [G, C], F [G, C*D] (statistics rows), mean0 / cov0 [C, D] the a-priori means and VARIANCES, numpy or
+    torch device tensors -> (W [G, D, D + 1], means [G, C*D], status [G] int32; 0, or 1 + the first dimension whose system failed: that
+    client has W = [0 | I] and means = mean0).  Outputs live where N lives; with device tensors the call only enqueues."""
+    G = int(N.shape[0])
+    C = int(N.shape[1]) if C is None else int(C)
+    D = (int(F.shape[1]) // C) if D is None else int(D)
+    if _is_torch(N):
+        import torch
+        W = torch.empty((G, D, D + 1), dtype=torch.float64, device=N.device)
+        means = torch.empty((G, C * D), dtype=torch.float64, device=N.device)
+        status = torch.empty((G,), dtype=torch.int32, device=N.device)
+    else:
+        W = np.empty((G, D, D + 1)); means = np.empty((G, C * D)); status = np.empty(G, np.int32)
+    _chk(lib.gmmiv_mllr_adapt_models(ctx._h, G, C, D, _ptr(_f64(N)), _ptr(_f64(F)), _ptr(_f64(mean0)), _ptr(_f64(cov0)), _ptr(W), _ptr(means),
+                                     _ptr(status)))
+    return W, means, status

@@ -370,10 +370,24 @@ int liagpu_train_target_ex(int device, const float *x, long T, int D, const long
 
 // TrainTarget for MANY clients in one call (adaptModelBatch): client i owns the segments [client_begin[i], client_begin[i + 1]) of the
 // seg_begin / seg_len lists and starts from the world model; w_out [nclients x C], mean_out / cov_out [nclients x C * D]
+// liagpu_train_target_batch_w: the same with mllr_out (nullable) [nclients x D x (D+1)] = the last iteration's MLLR transform of every
+// client (method "MLLR"; left untouched for the other methods)
+int liagpu_train_target_batch_w(int device, const float *x, long T, int D, const long *client_begin, long nclients, const long *seg_begin,
+                                const long *seg_len, int C, const double *w, const double *mean, const double *cov, const char *method, int nbTrainIt,
+                                double baggedP, int flags, const double *reg, double alphaMean, const long *norm, double *w_out, double *mean_out,
+                                double *cov_out, double *mllr_out);
 int liagpu_train_target_batch(int device, const float *x, long T, int D, const long *client_begin, long nclients, const long *seg_begin,
                               const long *seg_len, int C, const double *w, const double *mean, const double *cov, const char *method, int nbTrainIt,
                               double baggedP, int flags, const double *reg, double alphaMean, const long *norm, double *w_out, double *mean_out,
                               double *cov_out)
+{
+    return liagpu_train_target_batch_w(device, x, T, D, client_begin, nclients, seg_begin, seg_len, C, w, mean, cov, method, nbTrainIt, baggedP, flags, reg,
+                                       alphaMean, norm, w_out, mean_out, cov_out, nullptr);
+}
+int liagpu_train_target_batch_w(int device, const float *x, long T, int D, const long *client_begin, long nclients, const long *seg_begin,
+                                const long *seg_len, int C, const double *w, const double *mean, const double *cov, const char *method, int nbTrainIt,
+                                double baggedP, int flags, const double *reg, double alphaMean, const long *norm, double *w_out, double *mean_out,
+                                double *cov_out, double *mllr_out)
 {
     GUARD({
         GpuServer srv(device);
@@ -382,7 +396,10 @@ int liagpu_train_target_batch(int device, const float *x, long T, int D, const l
         std::vector<SegCluster> sel;
         for (long i = 0; i < nclients; ++i) sel.push_back(make_cluster(seg_begin + client_begin[i], seg_len + client_begin[i], client_begin[i + 1] - client_begin[i]));
         std::vector<MixtureGD> clients((size_t)nclients, world);
-        adaptModelBatch(fs, sel, world, clients, make_map_cfg(method, nbTrainIt, baggedP, flags, reg, alphaMean, norm));
+        std::vector<MatrixD> Wm;
+        adaptModelBatch(fs, sel, world, clients, make_map_cfg(method, nbTrainIt, baggedP, flags, reg, alphaMean, norm), mllr_out ? &Wm : nullptr);
+        for (size_t i = 0; i < Wm.size(); ++i)
+            if (!Wm[i].v.empty()) memcpy(mllr_out + i * (size_t)D * (D + 1), Wm[i].v.data(), Wm[i].v.size() * sizeof(double));
         for (long i = 0; i < nclients; ++i) {
             memcpy(w_out + (size_t)i * C, clients[i].weights().data(), C * sizeof(double));
             memcpy(mean_out + (size_t)i * C * D, clients[i].means().data(), (size_t)C * D * sizeof(double));
@@ -396,8 +413,23 @@ int liagpu_train_target_batch(int device, const float *x, long T, int D, const l
 // adaptModelBatch, 1 = adaptModel client after client.  ms_out[reps]: every repetition (the caller drops warm-ups); after them one more pass
 // with the context's kernel timers on: kernel_ms[0..2] = k_llk_mfma, k_stats_z, k_gmm_pack of the LAST call of that pass (-1: not run).
 // warm_clients > 0: only that many clients in the first repetition.  mean0_out (nullable): the adapted means of client 0.
+// liagpu_bench_enroll_method (tools/bench_mllr.py): the same with the MAPAlgo given (NULL: "MAPOccDep"); kernel_ms[5] then also holds
+// [3] = k_mllr_solve, [4] = k_mllr_pack of the last call
+int liagpu_bench_enroll_method(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
+                               const double *cov, const char *method, int nbTrainIt, int which, int reps, long warm_clients, double *ms_out,
+                               double *kernel_ms, double *mean0_out);
 int liagpu_bench_enroll(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
                         const double *cov, int nbTrainIt, int which, int reps, long warm_clients, double *ms_out, double *kernel_ms, double *mean0_out)
+{
+    double km[5];
+    const int rc = liagpu_bench_enroll_method(device, x, T, D, nclients, frames_per_client, C, w, mean, cov, nullptr, nbTrainIt, which, reps, warm_clients, ms_out,
+                                              km, mean0_out);
+    if (!rc) memcpy(kernel_ms, km, 3 * sizeof(double));
+    return rc;
+}
+int liagpu_bench_enroll_method(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
+                               const double *cov, const char *method, int nbTrainIt, int which, int reps, long warm_clients, double *ms_out,
+                               double *kernel_ms, double *mean0_out)
 {
     GUARD({
         if (nclients * frames_per_client > T) throw Exception("bench_enroll: not enough frames");
@@ -412,6 +444,7 @@ int liagpu_bench_enroll(int device, const float *x, long T, int D, long nclients
         }
         MAPCfg cfg;
         cfg.nbTrainIt = (unsigned long)nbTrainIt;
+        if (method) cfg.method = method;
         std::vector<MixtureGD> clients;
         auto run = [&](long n) {
             clients.assign((size_t)n, world);
@@ -434,6 +467,8 @@ int liagpu_bench_enroll(int device, const float *x, long T, int D, long nclients
         kernel_ms[0] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_llk_mfma");
         kernel_ms[1] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_stats_z");
         kernel_ms[2] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_gmm_pack");
+        kernel_ms[3] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_mllr_solve");
+        kernel_ms[4] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_mllr_pack");
         (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 0);
         if (mean0_out) memcpy(mean0_out, clients[0].means().data(), (size_t)C * D * sizeof(double));
     })
@@ -450,6 +485,23 @@ int liagpu_compute_map(int C, int D, const double *w0, const double *mean0, cons
         memcpy(w, client.weights().data(), C * sizeof(double));
         memcpy(mean, client.means().data(), (size_t)C * D * sizeof(double));
         memcpy(cov, client.covs().data(), (size_t)C * D * sizeof(double));
+    })
+}
+
+// computeMLLR on its own (TrainTools.cpp:788-866; host arithmetic only -- no device is touched): w / mean = the ML estimate in (cov is not
+// read), the adapted model out (weights and variances of the init model, covInv_out (nullable) = what computeAll() made of them);
+// W_out [D x (D+1)]
+int liagpu_compute_mllr(int C, int D, const double *w0, const double *mean0, const double *cov0, double *w, double *mean, double *cov,
+                        double *covinv_out, double frameCount, double *W_out)
+{
+    GUARD({
+        MixtureGD init = make_mixture(C, D, w0, mean0, cov0), client = make_mixture(C, D, w, mean, cov0);
+        const MatrixD W = computeMLLR(init, client, (unsigned long)frameCount);
+        memcpy(W_out, W.v.data(), W.v.size() * sizeof(double));
+        memcpy(w, client.weights().data(), C * sizeof(double));
+        memcpy(mean, client.means().data(), (size_t)C * D * sizeof(double));
+        memcpy(cov, client.covs().data(), (size_t)C * D * sizeof(double));
+        if (covinv_out) memcpy(covinv_out, client.covInvs().data(), (size_t)C * D * sizeof(double));
     })
 }
 

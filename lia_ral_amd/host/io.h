@@ -43,7 +43,7 @@ MixtureGD readMixtureXML(const std::string &path);
 void writeMixtureXML(const std::string &path, const MixtureGD &m, const std::string &id = "#1");
 MixtureGD readMixture(const std::string &path); // XML when the file starts with '<', else RAW
 
-struct MatrixD { unsigned long rows = 0, cols = 0; std::vector<double> v; };
+// (struct MatrixD { rows, cols, v } lives in liatools_gpu.h: computeMLLR returns one)
 MatrixD readMatrixDT(const std::string &path);
 void writeMatrixDT(const std::string &path, const MatrixD &m);
 // DB matrices (saveMatrixFormat DB, the binary twin of DT written by alize-core's Matrix<double>::save): rows, cols, then

@@ -1,6 +1,7 @@
 // liatools_gpu.cpp -- see liatools_gpu.h.  Host control flow of the LIA_SpkTools hot-path drivers;
 // all frame x Gaussian arithmetic happens in libgmmiv (HIP kernels).
 #include "liatools_gpu.h"
+#include "io.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1326,8 +1327,85 @@ void computeMAP(const MixtureGD &initModel, MixtureGD &client, unsigned long fra
     // else: "mapAlgo unknown, No adaptation will be perform" (TrainTools.cpp:555) -- the client keeps its ML estimate
 }
 
+// computeMLLR (TrainTools.cpp:788-866).  One global affine transform of the a-priori means: per dimension p the (D+1) x (D+1) system
+// G_p w = z_p, accumulated Gaussian by Gaussian in the reference's order of operations; W(p, :) = G_p^-1 z_p through an explicit
+// inverse (DoubleSquareMatrix::invert is alize-core's: here Gauss-Jordan with partial pivoting).  A Gaussian with occ = 0 adds
+// nothing to either sum and is left out, so that an unoccupied Gaussian's undefined ML mean cannot enter as 0 x NaN.
+MatrixD computeMLLR(const MixtureGD &inM, MixtureGD &outM, unsigned long frameCount)
+{
+    const unsigned long C = inM.getDistribCount(), D = inM.getVectSize(), n = D + 1;
+    if (outM.getDistribCount() != C || outM.getVectSize() != D) throw Exception("computeMLLR: the two mixtures differ in shape");
+    MatrixD W;
+    W.rows = D; W.cols = n; W.v.assign(D * n, 0.0);
+    std::vector<double> Z(D * n, 0.0), G(D * n * n, 0.0), xi(n);
+    for (unsigned long j = 0; j < C; ++j) {
+        const double occ = outM.weight(j) * (double)frameCount;
+        if (occ == 0.0) continue;
+        xi[0] = 1.0;
+        for (unsigned long i = 0; i < D; ++i) xi[i + 1] = inM.getMean(j, i);
+        for (unsigned long p = 0; p < D; ++p) {
+            const double occFrame = outM.getMean(j, p) * occ, cov = inM.getCov(j, p);
+            for (unsigned long q = 0; q < n; ++q) Z[p * n + q] += occFrame * xi[q] / cov;
+        }
+        for (unsigned long p = 0; p < D; ++p) {
+            const double cov = inM.getCov(j, p);
+            double *Gp = &G[p * n * n];
+            for (unsigned long q = 0; q < n; ++q) {
+                const double oq = occ * xi[q];
+                for (unsigned long r = 0; r < n; ++r) Gp[q * n + r] += oq * xi[r] / cov;
+            }
+        }
+    }
+    std::vector<double> A(n * n), Inv(n * n);
+    for (unsigned long l = 0; l < D; ++l) {
+        std::copy(G.begin() + l * n * n, G.begin() + (l + 1) * n * n, A.begin());
+        std::fill(Inv.begin(), Inv.end(), 0.0);
+        for (unsigned long i = 0; i < n; ++i) Inv[i * n + i] = 1.0;
+        for (unsigned long k = 0; k < n; ++k) {
+            unsigned long piv = k;
+            for (unsigned long i = k + 1; i < n; ++i)
+                if (std::fabs(A[i * n + k]) > std::fabs(A[piv * n + k])) piv = i;
+            const double d = A[piv * n + k];
+            if (d == 0.0 || !std::isfinite(d))
+                throw Exception("computeMLLR: the system of dimension " + std::to_string(l) + " is singular (fewer than vectSize + 1 occupied Gaussians in general position, or a client without frames)");
+            if (piv != k)
+                for (unsigned long c = 0; c < n; ++c) { std::swap(A[k * n + c], A[piv * n + c]); std::swap(Inv[k * n + c], Inv[piv * n + c]); }
+            for (unsigned long c = 0; c < n; ++c) { A[k * n + c] /= d; Inv[k * n + c] /= d; }
+            for (unsigned long i = 0; i < n; ++i) {
+                if (i == k) continue;
+                const double f = A[i * n + k];
+                if (f == 0.0) continue;
+                for (unsigned long c = 0; c < n; ++c) { A[i * n + c] -= f * A[k * n + c]; Inv[i * n + c] -= f * Inv[k * n + c]; }
+            }
+        }
+        for (unsigned long c = 0; c < n; ++c)
+            for (unsigned long k = 0; k < n; ++k) W.v[l * n + c] += Inv[c * n + k] * Z[l * n + k];
+    }
+    for (unsigned long j = 0; j < C; ++j) {
+        for (unsigned long i = 0; i < D; ++i) {
+            double m = W.v[i * n];
+            for (unsigned long k = 0; k < D; ++k) m += W.v[i * n + k + 1] * inM.getMean(j, k);
+            outM.setMean(j, m, i);
+        }
+    }
+    for (unsigned long j = 0; j < C; ++j) { // copyVar (computeAll() below), copyWeight
+        for (unsigned long i = 0; i < D; ++i) outM.setCov(j, inM.getCov(j, i), i);
+        outM.weight(j) = inM.weight(j);
+    }
+    outM.computeAll();
+    return W;
+}
+
+static void adaptModelW(FeatureBuffer &fs, const SegCluster &selectedSegments, const MixtureGD &aprioriModel, MixtureGD &clientMixture,
+                        const MAPCfg &mapCfg, MatrixD *lastW);
 void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const MixtureGD &aprioriModel, MixtureGD &clientMixture,
                 const MAPCfg &mapCfg)
+{
+    adaptModelW(fs, selectedSegments, aprioriModel, clientMixture, mapCfg, nullptr);
+}
+// lastW (nullable): the MLLR transform of the last iteration
+static void adaptModelW(FeatureBuffer &fs, const SegCluster &selectedSegments, const MixtureGD &aprioriModel, MixtureGD &clientMixture,
+                        const MAPCfg &mapCfg, MatrixD *lastW)
 {
     DeviceMixture dclient(fs.server(), clientMixture);
     EMAcc emAcc(dclient, clientMixture); // one accumulator for all iterations (see trainModelStream)
@@ -1338,7 +1416,12 @@ void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const Mix
         srand((unsigned)trainIt);
         accumulateStatEM(fs, emAcc, bagged);
         clientMixture = emAcc.getEM();
-        computeMAP(aprioriModel, clientMixture, (unsigned long)emAcc.getEMFeatureCount(), mapCfg);
+        if (mapCfg.method == "MLLR") { // TrainTools.cpp:888-894: before computeMAP, which does not know the name
+            MatrixD W = computeMLLR(aprioriModel, clientMixture, (unsigned long)emAcc.getEMFeatureCount());
+            if (!mapCfg.mllrMatrixFile.empty()) writeMatrixDT(mapCfg.mllrMatrixFile, W);
+            if (lastW) *lastW = std::move(W);
+        } else
+            computeMAP(aprioriModel, clientMixture, (unsigned long)emAcc.getEMFeatureCount(), mapCfg);
         if (mapCfg.normalizeModel) // normalizeMixture(clientMixture, mapCfg, config), TrainTools.cpp:898: target N(0, 1)
             normalizeMixture(clientMixture, std::vector<double>(), std::vector<double>(), true,
                              mapCfg.normalizeModelMeanOnly ? mapCfg.normalizeModelNbIt : 1, mapCfg.normalizeModelMeanOnly);
@@ -1358,16 +1441,22 @@ void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const Mix
 // NOT batched: varAdapt (needs second-order statistics per segment), normalizeModel (a host pass over each client's model per
 // iteration) -- for those configurations, and for clients of different shapes, this function runs the per-client loop above.
 void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerClient, const MixtureGD &aprioriModel,
-                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg)
+                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg, std::vector<MatrixD> *mllrW)
 {
     const size_t G = selectedPerClient.size();
     if (clientMixtures.size() != G) throw Exception("adaptModelBatch: one mixture per client is needed");
+    const bool mllr = mapCfg.method == "MLLR";
+    if (mllrW) mllrW->assign(G, MatrixD());
     if (G == 0) return;
     const unsigned long C = aprioriModel.getDistribCount(), D = aprioriModel.getVectSize();
-    bool batched = !mapCfg.varAdapt && !mapCfg.normalizeModel;
+    auto perClientLoop = [&]() {
+        for (size_t i = 0; i < G; ++i) adaptModelW(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg, mllr && mllrW ? &(*mllrW)[i] : nullptr);
+    };
+    // MLLR ignores varAdapt; its device entry serves vectSize <= 62, and the matrix file is the per-client loop's business
+    bool batched = mllr ? !mapCfg.normalizeModel && D <= 62 && mapCfg.mllrMatrixFile.empty() : !mapCfg.varAdapt && !mapCfg.normalizeModel;
     for (size_t i = 0; i < G && batched; ++i) batched = clientMixtures[i].getDistribCount() == C && clientMixtures[i].getVectSize() == D;
     if (!batched) {
-        for (size_t i = 0; i < G; ++i) adaptModel(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg);
+        perClientLoop();
         return;
     }
     const unsigned long nIt = mapCfg.nbTrainIt;
@@ -1384,12 +1473,12 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
     // what computeMAP leaves in the tables this function does not adapt: the a-priori model's (after computeAll() for the two
     // occupation-dependent methods, which recomputes covInv = 1 / cov); an unknown method keeps the ML estimate -- weights N / count,
     // and variances, which need the second-order statistics: per-client loop
-    if (method == GMMIV_MAP_NONE) {
-        for (size_t i = 0; i < G; ++i) adaptModel(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg);
+    if (method == GMMIV_MAP_NONE && !mllr) {
+        perClientLoop();
         return;
     }
     MixtureGD prior = aprioriModel;
-    if (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) prior.computeAll();
+    if (mllr || method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) prior.computeAll(); // computeMLLR: copyVar -> computeAll()
     const bool perClientW = mapCfg.weightAdapt && (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED);
 
     GpuServer &srv = fs.server();
@@ -1400,10 +1489,15 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
     } batch;
     srv.check(gmmiv_gmm_batch_create(srv.ctx(), (int)G, (int)C, (int)D, &batch.h));
     // device buffers of the loop: N | F | seg_llk | means (two, alternating) | weights | w0 | mean0 | the prior's weights | covInv
-    double *buf = (double *)srv.workspace(5, (G * C + G * CD + 2 * G + 2 * G * CD + G * C + 2 * C + 2 * CD) * sizeof(double));
+    // MLLR adds: the a-priori variances | W of every client | the statuses of every iteration (int32, read back once at the end)
+    const size_t WN = (size_t)D * (D + 1), nStat = mllr ? (size_t)nIt * G : 0;
+    double *buf = (double *)srv.workspace(5, (G * C + G * CD + 2 * G + 2 * G * CD + G * C + 2 * C + 2 * CD + (mllr ? CD + G * WN + (nStat + 1) / 2 : 0)) * sizeof(double));
     double *dN = buf, *dF = dN + G * C, *dL = dF + G * CD, *dM[2] = {dL + 2 * G, dL + 2 * G + G * CD}, *dW = dM[1] + G * CD, *dW0 = dW + G * C,
            *dMean0 = dW0 + C, *dPW = dMean0 + CD, *dPIv = dPW + C; // dPW / dPIv: the weights / covInv every later iteration reloads
+    double *dCov0 = dPIv + CD, *dWm = dCov0 + CD;
+    int32_t *dStat = (int32_t *)(dWm + G * WN);
     hipStream_t st = (hipStream_t)srv.stream();
+    if (mllr) hipcheck(hipMemcpyAsync(dCov0, aprioriModel.covs_c().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
     hipcheck(hipMemcpyAsync(dW0, aprioriModel.weights_c().data(), C * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
     hipcheck(hipMemcpyAsync(dMean0, aprioriModel.means_c().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
     hipcheck(hipMemcpyAsync(dPW, prior.weights_c().data(), C * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
@@ -1445,8 +1539,11 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
         FiniteScope fin(srv, fs);
         srv.check(gmmiv_tv_stats_models(srv.ctx(), batch.h, x, GMMIV_F32, (int64_t)n, (int64_t)D, segBegin.data(), segModel.data(), (int64_t)G, dN, dF, dL));
         double *cur = dM[it & 1], *out = dM[(it + 1) & 1];
-        srv.check(gmmiv_map_adapt_models(srv.ctx(), (int)G, (int)C, (int)D, dN, dF, dL + 1, 2, dW0, dMean0, cur, curStride, method, mapCfg.meanAdapt ? 1 : 0,
-                                         mapCfg.weightAdapt ? 1 : 0, mapCfg.meanReg, mapCfg.weightReg, mapCfg.meanAlpha, out, perClientW ? dW : nullptr));
+        if (mllr) // W does not depend on the frame count (a factor common to G_p and z_p): the statistics rows are all it needs
+            srv.check(gmmiv_mllr_adapt_models(srv.ctx(), (int)G, (int)C, (int)D, dN, dF, dMean0, dCov0, dWm, out, dStat + it * G));
+        else
+            srv.check(gmmiv_map_adapt_models(srv.ctx(), (int)G, (int)C, (int)D, dN, dF, dL + 1, 2, dW0, dMean0, cur, curStride, method, mapCfg.meanAdapt ? 1 : 0,
+                                             mapCfg.weightAdapt ? 1 : 0, mapCfg.meanReg, mapCfg.weightReg, mapCfg.meanAlpha, out, perClientW ? dW : nullptr));
         if (it + 1 < nIt) // the next iteration's models: means (and adapted weights) straight from the device, the rest is the prior's
             srv.check(gmmiv_gmm_batch_load(batch.h, perClientW ? dW : dPW, perClientW ? (int64_t)C : 0, out, (int64_t)CD, dPIv, 0));
         curStride = (long)CD;
@@ -1454,7 +1551,21 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
     std::vector<double> means(G * CD), weights(perClientW ? G * C : 0);
     hipcheck(hipMemcpyAsync(means.data(), dM[nIt & 1], G * CD * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
     if (perClientW) hipcheck(hipMemcpyAsync(weights.data(), dW, G * C * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    std::vector<int32_t> stat(nStat);
+    std::vector<double> wm(mllr && mllrW ? G * WN : 0);
+    if (mllr) hipcheck(hipMemcpyAsync(stat.data(), dStat, nStat * sizeof(int32_t), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    if (!wm.empty()) hipcheck(hipMemcpyAsync(wm.data(), dWm, G * WN * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
     srv.sync();
+    for (size_t i = 0; i < G && mllr; ++i) // the first client whose system failed in any iteration: what the per-client loop stops at
+        for (unsigned long it = 0; it < nIt; ++it)
+            if (stat[it * G + i])
+                throw Exception("adaptModelBatch: MLLR of client " + std::to_string(i) + ", iteration " + std::to_string(it) + ": the system of dimension " +
+                                std::to_string(stat[it * G + i] - 1) + " is singular (fewer than vectSize + 1 occupied Gaussians in general position, or a client without frames)");
+    for (size_t i = 0; i < G && !wm.empty(); ++i) {
+        MatrixD &W = (*mllrW)[i];
+        W.rows = D; W.cols = D + 1;
+        W.v.assign(wm.begin() + i * WN, wm.begin() + (i + 1) * WN);
+    }
     for (size_t i = 0; i < G; ++i) {
         MixtureGD m = prior; // weights, variances (and covInv) as computeMAP leaves them
         memcpy(m.means().data(), &means[i * CD], CD * sizeof(double));

@@ -139,6 +139,7 @@ class MixtureGD {
     const std::vector<double> &covInvs() const { return _covInv; }
     const std::vector<double> &weights_c() const { return _w; }
     const std::vector<double> &means_c() const { return _mean; }
+    const std::vector<double> &covs_c() const { return _cov; }
 
   private:
     unsigned long _c, _d;
@@ -332,8 +333,9 @@ std::vector<double> trainModelStream(const TrainCfg &cfg, FeatureBuffer &fs, con
                                      AllReduceFn allReduce = nullptr, void *user = nullptr, gmmiv_comm *comm = nullptr);
 
 // ---- TrainTarget: MAP adaptation (TrainTools.cpp:445-489 computeMAPOccDep, :871-904 adaptModel) ----
+struct MatrixD { unsigned long rows = 0, cols = 0; std::vector<double> v; }; // row-major; io.h reads / writes it (DT, DB)
 struct MAPCfg { // MAPCfg::MAPCfg, TrainTools.cpp:95-147
-    std::string method = "MAPOccDep"; // MAPAlgo: MAPOccDep, MAPModelBased (regulation factors), MAPConst, MAPConst2 (constant alpha)
+    std::string method = "MAPOccDep"; // MAPAlgo: MAPOccDep, MAPModelBased (regulation factors), MAPConst, MAPConst2 (constant alpha), MLLR
     unsigned long nbTrainIt = 1;
     double baggedFrameProbability = 1.0;
     bool meanAdapt = true, varAdapt = false, weightAdapt = false;
@@ -341,6 +343,9 @@ struct MAPCfg { // MAPCfg::MAPCfg, TrainTools.cpp:95-147
     double meanAlpha = 0.75;                                  // MAPAlphaMean: a-priori probability of the init model (MAPConst / MAPConst2)
     bool normalizeModel = false, normalizeModelMeanOnly = false; // :125-135, applied after every iteration's MAP step (:898)
     unsigned long normalizeModelNbIt = 1;
+    // MLLR only: when set, the transform W [D x (D+1)] is saved there (DT matrix) after every iteration.  The reference writes
+    // "MLLR_matrix.mat" into the working directory unconditionally (TrainTools.cpp:892-893); a library does not.
+    std::string mllrMatrixFile;
 };
 void computeMAPOccDep(const MixtureGD &initModel, MixtureGD &client, const MAPCfg &cfg, double frameCount);              // :445-489
 void computeModelBasedMAPOccDep(const MixtureGD &initModel, MixtureGD &client, const MAPCfg &cfg, double frameCount);    // :491-536 (the same arithmetic)
@@ -348,15 +353,27 @@ void computeMAPConst(const MixtureGD &initModel, MixtureGD &client, const MAPCfg
 void computeMAPConst2(const MixtureGD &initModel, MixtureGD &client, const MAPCfg &cfg);                                 // :390-420 (means only, weight-balanced)
 // computeMAP (:543-556): dispatch on cfg.method; an unknown method leaves the client as it is (the reference prints a warning)
 void computeMAP(const MixtureGD &initModel, MixtureGD &client, unsigned long frameCount, const MAPCfg &cfg);
-// client model = MAP(aprioriModel, EM estimate on the selected frames), nbTrainIt times
+// computeMLLR (:788-866), host arithmetic in the reference's order: outM holds the ML estimate (weights, means) of this iteration and
+// comes back with means W [1; mean_in] and inM's weights and variances (copyVar -> computeAll(), copyWeight).  Row p of the returned
+// W [D x (D+1)] is G_p^-1 z_p with occ_j = outM.weight(j) * frameCount; the inverse is a Gauss-Jordan elimination with partial
+// pivoting in double.  meanAdapt / varAdapt / weightAdapt are not consulted.  Throws on a zero or non-finite pivot (a client
+// without frames, fewer than D + 1 occupied Gaussians).
+MatrixD computeMLLR(const MixtureGD &inM, MixtureGD &outM, unsigned long frameCount);
+// client model = MAP(aprioriModel, EM estimate on the selected frames), nbTrainIt times; mapCfg.method == "MLLR" takes computeMLLR
+// instead of computeMAP (:888-894), to which "MLLR" stays an unknown mapAlgo
 void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const MixtureGD &aprioriModel,
                 MixtureGD &clientMixture, const MAPCfg &mapCfg);
 // The same for many clients at once (the client loop of TrainTarget.cpp:150-270): client i = adaptModel(fs, selectedPerClient[i],
 // aprioriModel, clientMixtures[i], mapCfg) called client after client in that order -- same bagging draws, results to the last bits of
 // another summation order -- with ONE statistics pass per iteration for all clients (gmmiv_tv_stats_models, a model per client) and the
 // MAP step on the device (gmmiv_map_adapt_models).  varAdapt, normalizeModel and an unknown MAPAlgo run the per-client loop.
+// "MLLR": the same loop with gmmiv_mllr_adapt_models as the adaptation step (varAdapt is ignored, as computeMLLR ignores it;
+// normalizeModel, clients of another shape and vectSize > 62 run the per-client loop).  The statuses are read once, after the last
+// iteration: a client whose system failed throws an Exception naming the first such client, as the per-client loop would.
+// mllrW (optional): the last iteration's W of every client.  A configuration with mllrMatrixFile set runs the per-client loop (one
+// file, rewritten client after client, iteration after iteration).
 void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerClient, const MixtureGD &aprioriModel,
-                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg);
+                     std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg, std::vector<MatrixD> *mllrW = nullptr);
 
 // ---- ComputeTest (LIA_SpkDet/ComputeTest/src/ComputeTest.cpp:129-215) -----------------------------
 // LLR of each client against the world for one test file: per segment when segmentalMode, else one

@@ -221,10 +221,13 @@ def train_target_ex(x, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, b
 
 
 def train_target_batch(x, client_begin, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, bagged_p=1.0, mean=True, var=False, weight=False,
-                       reg=(16.0, 16.0, 16.0), alpha_mean=0.75, normalize=False, normalize_mean_only=False, normalize_nb_it=1, device=0):
+                       reg=(16.0, 16.0, 16.0), alpha_mean=0.75, normalize=False, normalize_mean_only=False, normalize_nb_it=1, device=0,
+                       return_mllr=False):
     """TrainTarget for many clients at once (adaptModelBatch): client i owns the segments client_begin[i] .. client_begin[i + 1] of the
     seg_begin / seg_len lists and starts from `world` -> (w [G, C], mean [G, C, D], cov [G, C, D]); row i is what train_target_ex gives
-    for client i when the clients are adapted one after the other in this order (var / normalize: it runs exactly that loop)."""
+    for client i when the clients are adapted one after the other in this order (var / normalize: it runs exactly that loop).
+    method="MLLR": one global affine transform of the world means per client (computeMLLR); return_mllr=True appends the last
+    iteration's transforms W [G, D, D + 1] to the result."""
     x = np.ascontiguousarray(x, np.float32)
     T, D = x.shape
     w, m, c = [np.ascontiguousarray(a, np.float64) for a in world]
@@ -236,10 +239,11 @@ def train_target_batch(x, client_begin, seg_begin, seg_len, world, method="MAPOc
     r = np.ascontiguousarray(reg, np.float64)
     norm = (ct.c_long * 3)(int(normalize), int(normalize_mean_only), int(normalize_nb_it))
     wo = np.empty((G, C)); mo = np.empty((G, C, D)); co = np.empty((G, C, D))
-    _chk(lib.liagpu_train_target_batch(device, x.ctypes.data_as(_fp), ct.c_long(T), D, lp(cb), ct.c_long(G), lp(b), lp(l), C, _d(w), _d(m), _d(c),
-                                       method.encode(), nb_it, ct.c_double(bagged_p), _map_flags(mean, var, weight), _d(r), ct.c_double(alpha_mean), norm,
-                                       _d(wo), _d(mo), _d(co)))
-    return wo, mo, co
+    Wm = np.zeros((G, D, D + 1)) if return_mllr else None
+    _chk(lib.liagpu_train_target_batch_w(device, x.ctypes.data_as(_fp), ct.c_long(T), D, lp(cb), ct.c_long(G), lp(b), lp(l), C, _d(w), _d(m), _d(c),
+                                         method.encode(), nb_it, ct.c_double(bagged_p), _map_flags(mean, var, weight), _d(r), ct.c_double(alpha_mean), norm,
+                                         _d(wo), _d(mo), _d(co), _d(Wm)))
+    return (wo, mo, co, Wm) if return_mllr else (wo, mo, co)
 
 
 def compute_map(method, init, client, frame_count, mean=True, var=False, weight=False, reg=(16.0, 16.0, 16.0), alpha_mean=0.75):
@@ -251,6 +255,18 @@ def compute_map(method, init, client, frame_count, mean=True, var=False, weight=
     _chk(lib.liagpu_compute_map(C, D, _d(w0), _d(m0), _d(c0), _d(w), _d(m), _d(c), ct.c_double(frame_count), method.encode(),
                                 _map_flags(mean, var, weight), _d(r), ct.c_double(alpha_mean)))
     return w, m, c
+
+
+def compute_mllr(init, client, frame_count, return_covinv=False):
+    """computeMLLR (TrainTools.cpp:788-866) on its own, host arithmetic only: init = (w, mean, cov) of the a-priori model, client =
+    (w, mean[, cov]) the ML estimate -> (W [D, D + 1], (w, mean, cov)) with the adapted means and the a-priori weights and variances;
+    return_covinv=True appends the covInv the model holds after its computeAll()."""
+    w0, m0, c0 = [np.ascontiguousarray(a, np.float64) for a in init[:3]]
+    w, m = [np.array(a, np.float64, order="C", copy=True) for a in client[:2]]
+    C, D = m0.shape
+    c = np.empty((C, D)); ci = np.empty((C, D)); W = np.empty((D, D + 1))
+    _chk(lib.liagpu_compute_mllr(C, D, _d(w0), _d(m0), _d(c0), _d(w), _d(m), _d(c), _d(ci), ct.c_double(frame_count), _d(W)))
+    return (W, (w, m, c), ci) if return_covinv else (W, (w, m, c))
 
 
 def topgauss(x, seg_begin, seg_len, ubm, top_gauss, path, top_distribs_count=64, model2_mean=None, complete=True, min_llk=-200.0,
