@@ -647,6 +647,24 @@ int gmmiv_score_twocov_mix_part(gmmiv_ctx *ctx, int dim, int64_t M, int64_t S, c
  * other cells keep _scores' initial 0.  All rules above fill the whole M x S block with one GEMM; this call then writes `fill`
  * into every cell whose flag trials[m*S + s] is 0 (bytes, host or device). */
 int gmmiv_score_apply_trials(gmmiv_ctx *ctx, int64_t M, int64_t S, const unsigned char *trials, double fill, double *scores);
+/* The fp64 GEMM every TV / JFA / PLDA step and every scoring rule above is built on (k_dgemm, csrc/tv_kernels.hip), called as they
+ * call it: on the context's stream, with the context's "gemm_*" options.  Row-major, strides in doubles:
+ *     C[b] = epilogue(alpha * op(A[b]) * op(B[b])) + beta * C[b],   b = 0 .. batch-1
+ *     op(A)[m][k] = ta ? A[k*lda + m] : A[m*lda + k]        op(B)[k][n] = tb ? B[n*ldb + k] : B[k*ldb + n]
+ *   A, B, C, rv, cv   DEVICE pointers (GMMIV_ERR_ARG otherwise); nothing is staged or copied, so an unaligned base, an odd leading
+ *                     dimension or an odd batch stride reaches the kernel as given (it then takes its per-element checked loads)
+ *   lda, ldb, ldc     >= the extent they stride (ta ? M : K, tb ? K : N, N); sA, sB, sC >= 0 doubles between the matrices of a batch
+ *                     (0: shared)
+ *   nz                1: one pass over K;  > 1: split-K over at most nz layers of K (each a multiple of 16) whose partial products go
+ *                     to the context's workspace (nz * M * N doubles) and are summed in layer order (deterministic);
+ *                     0: the count the library picks for its own long-K products
+ *   epi_mode          0: none;  1: v * rv[m] * cv[n];  2: v + br * rv[m] + bc * cv[n] + cst   (v = alpha * the product; rv[M], cv[N])
+ * GMMIV_ERR_ARG: a negative size, a leading dimension smaller than its extent, batch > 1 with nz != 1 or epi_mode != 0, nz != 1
+ * with epi_mode != 0, epi_mode outside 0..2 or without rv / cv.  M, N or batch == 0: nothing is done (GMMIV_OK).  K == 0: C = beta * C,
+ * zeros when beta == 0.  beta == 0: C is written, never read.  Only enqueues: gmmiv_ctx_sync (or the stream) orders the result. */
+int gmmiv_dgemm(gmmiv_ctx *ctx, int ta, int tb, int M, int N, int K, double alpha, const double *A, int64_t lda, int64_t sA,
+                const double *B, int64_t ldb, int64_t sB, double beta, double *C, int64_t ldc, int64_t sC, int batch, int nz,
+                int epi_mode, const double *rv, const double *cv, double br, double bc, double cst);
 /* Multi-GPU scoring: the M x S matrix tiles by blocks of MODELS, no collective -- rank g calls any rule above
  * with the columns [m0, m1) of `models` (and the matching nsess / rows of scores); gmmiv_shard_range gives the contiguous range
  * of rank `rank` out of `world` over n items (sizes differ by at most one), the same split as the reference's thread ranges

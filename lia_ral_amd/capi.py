@@ -585,6 +585,35 @@ class Context:
         _chk(lib.gmmiv_score_apply_trials(self._h, ct.c_int64(M), ct.c_int64(S), _ptr(t), ct.c_double(fill), _ptr(scores)))
         return scores
 
+    # ---- the fp64 GEMM under all of the above, as the library calls it
+    def dgemm(self, ta, tb, alpha, A, B, beta, C, nz=1, epi_mode=0, rv=None, cv=None, br=0.0, bc=0.0, cst=0.0, K=None):
+        """C = epilogue(alpha op(A) op(B)) + beta C, in place (gmmiv_dgemm).  A, B, C: 2-D, or 3-D with the batch first,
+        torch.float64 CUDA tensors whose last stride is 1.  The leading dimensions and batch strides are the tensors' strides
+        (a batch stride of 0 -- an expanded operand -- is a shared matrix) and data_ptr() is passed as it is, so a view that
+        starts inside a larger buffer keeps its offset.  K is read from A; pass it when M == 0 leaves it open."""
+        import torch
+        for t in (A, B, C):
+            assert _is_torch(t) and t.is_cuda and t.dtype == torch.float64 and t.dim() in (2, 3) and t.stride(-1) == 1
+        batch = C.shape[0] if C.dim() == 3 else 1
+        assert all(t.dim() == 2 or t.shape[0] == batch for t in (A, B))
+
+        def ld(t):      # a single row has no stride of its own
+            return t.stride(-2) if t.shape[-2] > 1 else max(t.stride(-2), t.shape[-1], 1)
+
+        def bs(t):
+            return t.stride(0) if t.dim() == 3 and batch > 1 else 0
+        M, N = C.shape[-2], C.shape[-1]
+        if K is None:
+            K = A.shape[-2] if ta else A.shape[-1]
+        assert tuple(A.shape[-2:]) == ((K, M) if ta else (M, K)) and tuple(B.shape[-2:]) == ((N, K) if tb else (K, N))
+        for v in (rv, cv):
+            assert v is None or (v.is_cuda and v.dtype == torch.float64 and v.is_contiguous())
+        _chk(lib.gmmiv_dgemm(self._h, int(bool(ta)), int(bool(tb)), M, N, K, ct.c_double(alpha), _vptr(A), ct.c_int64(ld(A)),
+                             ct.c_int64(bs(A)), _vptr(B), ct.c_int64(ld(B)), ct.c_int64(bs(B)), ct.c_double(beta), _vptr(C),
+                             ct.c_int64(ld(C)), ct.c_int64(bs(C)), batch, int(nz), int(epi_mode), _ptr(rv), _ptr(cv),
+                             ct.c_double(br), ct.c_double(bc), ct.c_double(cst)))
+        return C
+
     def score_plda(self, models_sum, nsess, segs, FTJF, out=None):
         M, S, out = self._score_out(models_sum, segs, out)
         ns = np.ascontiguousarray(nsess, dtype=np.int64)

@@ -1010,6 +1010,48 @@ int gmmiv_score_apply_trials(gmmiv_ctx *c, int64_t M, int64_t S, const unsigned 
     return o.finish();
 }
 
+// The fp64 GEMM under every step above, as it is: C[b] = epilogue(alpha op(A[b]) op(B[b])) + beta C[b] on the context's stream with the
+// context's "gemm_*" options bound.  A pass-through to tvk_dgemm / tvk_dgemm_splitk / tvk_dgemm_epi: device pointers only, nothing
+// is staged or copied, so the caller's bases, leading dimensions and batch strides reach launch_dgemm unchanged.
+int gmmiv_dgemm(gmmiv_ctx *c, int ta, int tb, int M, int N, int K, double alpha, const double *A, int64_t lda, int64_t sA,
+                const double *B, int64_t ldb, int64_t sB, double beta, double *C, int64_t ldc, int64_t sC, int batch, int nz,
+                int epi_mode, const double *rv, const double *cv, double br, double bc, double cst)
+{
+    if (!c) { gmmiv_set_error("dgemm: ctx == NULL"); return GMMIV_ERR_ARG; }
+    if (M < 0 || N < 0 || K < 0 || batch < 0 || nz < 0) { gmmiv_set_error("dgemm: negative size"); return GMMIV_ERR_ARG; }
+    if (epi_mode < 0 || epi_mode > 2) { gmmiv_set_error("dgemm: epi_mode %d is not 0, 1 or 2", epi_mode); return GMMIV_ERR_ARG; }
+    if (epi_mode != 0 && (!rv || !cv)) { gmmiv_set_error("dgemm: epi_mode %d needs rv and cv", epi_mode); return GMMIV_ERR_ARG; }
+    if (batch > 1 && (nz != 1 || epi_mode != 0)) { gmmiv_set_error("dgemm: a batch takes neither split-K nor an epilogue"); return GMMIV_ERR_ARG; }
+    if (nz != 1 && epi_mode != 0) { gmmiv_set_error("dgemm: split-K takes no epilogue"); return GMMIV_ERR_ARG; }
+    if (lda < (ta ? M : K) || ldb < (tb ? K : N) || ldc < N) {
+        gmmiv_set_error("dgemm: a leading dimension is smaller than its extent (lda %lld, ldb %lld, ldc %lld)", (long long)lda, (long long)ldb, (long long)ldc);
+        return GMMIV_ERR_ARG;
+    }
+    if (sA < 0 || sB < 0 || sC < 0) { gmmiv_set_error("dgemm: negative batch stride"); return GMMIV_ERR_ARG; }
+    if (M == 0 || N == 0 || batch == 0) return GMMIV_OK;
+    if (!C || (K > 0 && (!A || !B))) { gmmiv_set_error("dgemm: NULL operand"); return GMMIV_ERR_ARG; }
+    if (!gmmiv_is_device_ptr(C) || (K > 0 && (!gmmiv_is_device_ptr(A) || !gmmiv_is_device_ptr(B))) ||
+        (epi_mode != 0 && (!gmmiv_is_device_ptr(rv) || !gmmiv_is_device_ptr(cv)))) {
+        gmmiv_set_error("dgemm: operands must be device pointers");
+        return GMMIV_ERR_ARG;
+    }
+    GBIND(c);
+    if (epi_mode != 0) {
+        GCHK(tvk_dgemm_epi(c->stream, ta != 0, tb != 0, M, N, K, alpha, A, lda, B, ldb, C, ldc, epi_mode, rv, cv, br, bc, cst, beta));
+        return GMMIV_OK;
+    }
+    if (nz == 0) nz = tvk_splitk_count(M, N, K, c->n_cu);
+    if (nz > 1 && K > 0) {
+        void *p;
+        int rc;
+        if ((rc = c->scratch(WS_SLAB, (size_t)nz * M * N * 8, &p))) return rc;
+        GCHK(tvk_dgemm_splitk(c->stream, ta != 0, tb != 0, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, nz, (double *)p));
+        return GMMIV_OK;
+    }
+    GCHK(tvk_dgemm(c->stream, ta != 0, tb != 0, M, N, K, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc, sC, batch));
+    return GMMIV_OK;
+}
+
 // ---- PldaDev: development-set statistics ---------------------------------------------------------
 namespace {
 struct DevSet { // device views shared by the gmmiv_dev_* entry points

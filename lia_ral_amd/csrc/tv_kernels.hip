@@ -356,7 +356,9 @@ static void launch_dgemm(hipStream_t st, bool ta, bool tb, dim3 grid, int M, int
                          long lda, long sA, const double *B, long ldb, long sB, double beta, double *C, long ldc, long sC,
                          int ksplit, DgemmEpi epi = DgemmEpi{nullptr, nullptr, 0.0, 0.0, 0.0, 0, 0})
 {
-    epi.remap = g_gemm_remap && grid.x >= 16; // wide enough for the per-XCD column order to mean something
+    // wide enough for the per-XCD column order to mean something.  The option's VALUE goes on (1 or 2): `g_gemm_remap && ...` made
+    // every non-zero value 1, so "gemm_remap 2" ran order 1 and the 8 x 8 block order of the kernel was never executed
+    epi.remap = grid.x >= 16 ? g_gemm_remap : 0;
     // a partial last k-tile is handled in the kernel; K must be even only when an operand has k as its FASTEST index (16-byte pairs
     // along k).  A^T B products (ta && !tb: `A += N^T E`, `Cmx += W^T F` with K = the number of utterances) take any K -- with an odd
     // utterance count they used to fall to the per-element checked instantiation as a whole

@@ -132,7 +132,9 @@ def test_tv_em_iteration(ctx, C, D, R, U):
 
 
 def test_dgemm_shapes_through_scoring(ctx):
-    """The MFMA GEMM behind every TV step: odd sizes, all transposes exercised via the score rules."""
+    """The MFMA GEMM behind every TV step, as the score rules reach it: odd sizes, the TN and NN products only (even_stride copies an
+    odd-stride operand first, so the unaligned paths are not reached either).  The kernel on its own, every transpose pair and
+    dispatch path, element by element: tests/test_gpu_dgemm.py."""
     rng = np.random.default_rng(1)
     # (64, 400, 432), (400, 190, 150), (30, 258, 322): even sizes a little over a multiple of 128 -> the 32-wide strip tiles, both sides
     for dim, M, S in [(5, 3, 7), (50, 130, 129), (400, 260, 17), (33, 1, 300), (64, 400, 432), (400, 190, 150), (30, 258, 322)]:
