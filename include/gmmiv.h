@@ -64,6 +64,10 @@ const char *gmmiv_version(void);
  *                      order -- depends only on this option, the model shape and the device model, not on the memory
  *                      free at call time: results are bitwise reproducible across runs and ranks.  (The order differs
  *                      from the reference's frame-by-frame accumulation: parity is to a tolerance, see DESIGN.md.)
+ *   "trials_scratch_mb" 2048  gmmiv_llr_trials: MiB of per-frame world results (4 ctop + 16 bytes per frame) kept per chunk of whole segments
+ *   "trials_piece" 0   A/B knob of gmmiv_llr_trials: frames per work item, a multiple of 4 that is >= 4; 0 (default) or any other value =
+ *                      GMMIV_TRIAL_PIECE.  It moves the boundaries of the summation pieces and with them the LAST BITS of every result
+ *                      (the definition and the independence properties hold for any value); not meant for production use
  *   "models_scratch_mb" 2048  gmmiv_*_models: MiB of packed models (nct (2 KS + 2) 512 bytes each, 2 MiB at 2048 x 60) built per chunk
  *                      of segments; a chunk holds at least one model whatever the value
  *   "z_waves" 8        workgroup shape of k_stats_z (8, 16 or 4 waves)
@@ -461,6 +465,53 @@ typedef struct gmmiv_model_tile {
 } gmmiv_model_tile;
 int64_t gmmiv_plan_model_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int tile_frames,
                                gmmiv_model_tile *tiles, int64_t cap);
+
+/* ---- A WHOLE LIST OF TRIALS: batched ComputeTest ---------------------------------------------------------------------------------------
+ * ComputeTest (ComputeTest.cpp:129-215) scores every line of an ndx -- a test file against its handful of clients out of thousands --
+ * with DETERMINE_TOP_DISTRIBS on the world model, USE_TOP_DISTRIBS per client and a mean over the selected frames.  Line by line that is
+ * three launches, a table upload, a stream drain and a read-back around a few tens of microseconds of kernel time.  gmmiv_llr_trials takes
+ * the frames of ALL lines as segments of one matrix (as gmmiv_llk_models), the clients as a gmmiv_gmm_batch of the world's (C, D), and a
+ * list of trials i = (trial_seg[i], trial_model[i]) in any order; a pair may repeat and a segment may have no trial.
+ *   per segment s, n_s frames:  the world's top set, remainder and clamped llk_w(t) are exactly those of gmmiv_llk_determine_top(world,
+ *                               ctop, mode, min_llk, max_llk); world_mean[s] = sum_t llk_w(t) / n_s
+ *   per trial i = (s, g):       llk_c(t) is exactly what gmmiv_llk_use_top returns for model g on the world's indices and remainder of
+ *                               frame t; client_mean[i] = sum_t llk_c(t) / n_s; llr[i] = client_mean[i] - world_mean[s]
+ * Zero-likelihood and NaN frames follow "DEGENERATE INPUTS": both passes give min_llk and the frame counts in n_s (the frames are
+ * screened and counted once, by the world pass).  An empty segment gives 0 for all three.  Frames outside [seg_begin[0],
+ * seg_begin[nseg]) are not read.  seg_begin (nseg + 1, non-decreasing), trial_seg and trial_model are HOST arrays, copied before return;
+ * llr, client_mean (nullable), world_mean (nullable; written for every segment, also with ntrial = 0) are host or device arrays.  T = 0,
+ * nseg = 0 and ntrial = 0 are valid.  GMMIV_ERR_ARG: a batch of another (C, D) than the world, ctop outside 1 .. min(64, C), a trial
+ * index out of range, a table on the device.
+ * Sums: a work item of the kernel is (trial, piece), a piece being P frames counted from the segment's first frame, P = GMMIV_TRIAL_PIECE
+ * unless the A/B option "trials_piece" names another multiple of 4 (gmmiv_trial_piece(ctx) returns the P in effect); frame
+ * j of a piece is added, in frame order, to partial j mod 4, a piece is ((p0 + p1) + p2) + p3, a segment the sum of its pieces in order.
+ * A result therefore depends on its segment's frames and its model only -- not on the rest of the list, its order, or the chunking
+ * (per-frame world results, 4 ctop + 16 bytes per frame, are kept for chunks of whole segments of "trials_scratch_mb" MiB, default 2048).
+ * ctop <= 16 with an even vectSize runs k_topc_use4_trials (no per-frame client value in memory); any other shape walks the trials
+ * through the kernels of gmmiv_llk_use_top into a scratch row that the same piece scheme sums: same definition, launch-bound.
+ * Synchronisation: the call is NOT enqueue-only.  It waits for the context's stream once after uploading its tables (they live in host
+ * memory of the call) and once per chunk inside the world pass (gmmiv_llk_determine_top reads its fallback flags back); with x and the
+ * outputs on the device everything else -- the trial kernel, the reductions, the writes of llr / client_mean / world_mean -- is only
+ * enqueued, so the outputs are valid in stream order (gmmiv_ctx_sync before reading them from another stream).  Host outputs are
+ * complete on return.
+ * Kernel timers: "k_topc_use" (the trial kernel), "k_trial_reduce", and the world pass's own ("k_llk_mfma", "k_topc_rank", ...). */
+#define GMMIV_TRIAL_PIECE 128 /* default frames per work item; a multiple of 4 (DESIGN.md section 3.16 has the A/B) */
+int gmmiv_trial_piece(const gmmiv_ctx *ctx); /* the piece gmmiv_llr_trials uses on ctx: "trials_piece" if set and valid, else (and for NULL) GMMIV_TRIAL_PIECE */
+int gmmiv_llr_trials(gmmiv_ctx *ctx, const gmmiv_gmm *world, const gmmiv_gmm_batch *clients, const void *x, int x_dtype, int64_t T,
+                     int64_t ldx, const int64_t *seg_begin, int64_t nseg, const int32_t *trial_seg, const int32_t *trial_model,
+                     int64_t ntrial, int ctop, int mode, double min_llk, double max_llk, double *llr /* [ntrial] */,
+                     double *client_mean /* [ntrial], nullable */, double *world_mean /* [nseg], nullable */);
+/* The work list of the trial kernel (pure host function): the pieces [b + k P, min(b + (k + 1) P, e)) of every trial's segment [b, e),
+ * P = piece_frames (a positive multiple of 4), sorted by (segment, piece, position of the trial in the list) -- the trials of one
+ * segment and piece run next to each other and share the rows of x and of the world's indices in cache.  An empty segment and a segment
+ * without a trial have no tile.  Returns the number of tiles (entries beyond `cap` are counted, not written; tiles may be NULL), or -1
+ * for a bad argument (a decreasing seg_begin, a bad piece_frames, a trial_seg outside [0, nseg)). */
+typedef struct gmmiv_trial_tile {
+    int64_t lo, hi;                    /* frames [lo, hi) of the segment */
+    int32_t trial, seg, model, piece;  /* position in the trial list, trial_seg / trial_model of it, piece number inside the segment */
+} gmmiv_trial_tile;
+int64_t gmmiv_plan_trial_tiles(const int64_t *seg_begin, int64_t nseg, const int32_t *trial_seg, const int32_t *trial_model,
+                               int64_t ntrial, int piece_frames, gmmiv_trial_tile *tiles, int64_t cap);
 
 /* computeMAP (TrainTools.cpp:445-556) for G models at once, from the statistics rows of gmmiv_tv_stats_models: element-wise over
  * [G x C x D], nothing leaves the device.  Per model g: count_g = count[g * count_stride] (seg_llk + 1 with stride 2 fits), the ML

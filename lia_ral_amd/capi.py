@@ -40,6 +40,7 @@ def _load():
     lib.gmmiv_comm_take_bytes.restype = ct.c_double
     lib.gmmiv_ctx_stream.restype = ct.c_void_p
     lib.gmmiv_plan_model_tiles.restype = ct.c_int64
+    lib.gmmiv_plan_trial_tiles.restype = ct.c_int64
     return lib
 
 
@@ -961,6 +962,33 @@ def plan_model_tiles(seg_begin, seg_model, tile_frames=256):
     return [{k: getattr(buf[i], k) for k, _ in ModelTile._fields_} for i in range(int(n))]
 
 
+TRIAL_PIECE = int(lib.gmmiv_trial_piece(None))  # GMMIV_TRIAL_PIECE, read from the library: frames per work item of gmmiv_llr_trials
+
+
+class TrialTile(ct.Structure):
+    """gmmiv_trial_tile: one workgroup of the trial kernel"""
+    _fields_ = [("lo", ct.c_int64), ("hi", ct.c_int64), ("trial", ct.c_int32), ("seg", ct.c_int32), ("model", ct.c_int32), ("piece", ct.c_int32)]
+
+
+def plan_trial_tiles(seg_begin, trial_seg, trial_model, piece_frames=TRIAL_PIECE, count_only=False):
+    """gmmiv_plan_trial_tiles (host only, needs no GPU) -> list of dicts lo / hi / trial / seg / model / piece, sorted by (segment, piece,
+    position of the trial); count_only: the number of tiles alone (tiles = NULL)"""
+    sb = np.ascontiguousarray(seg_begin, np.int64)
+    ts = np.ascontiguousarray(trial_seg, np.int32)
+    tm = np.ascontiguousarray(trial_model, np.int32)
+    assert len(sb) >= 1 and len(ts) == len(tm)
+    args = (sb.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sb) - 1), ts.ctypes.data_as(ct.c_void_p), tm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(ts)),
+            int(piece_frames))
+    n = lib.gmmiv_plan_trial_tiles(*args, ct.c_void_p(0), ct.c_int64(0))
+    if n < 0:
+        raise GmmivError("gmmiv_plan_trial_tiles: bad argument")
+    if count_only:
+        return int(n)
+    buf = (TrialTile * max(int(n), 1))()
+    lib.gmmiv_plan_trial_tiles(*args, ct.cast(buf, ct.c_void_p), ct.c_int64(n))
+    return [{k: getattr(buf[i], k) for k, _ in TrialTile._fields_} for i in range(int(n))]
+
+
 MAP_METHODS = {"MAPOccDep": 1, "MAPModelBased": 2, "MAPConst": 3, "MAPConst2": 4}  # anything else: 0, the ML estimate (computeMAP's "mapAlgo unknown")
 
 
@@ -1038,6 +1066,30 @@ class GmmBatch:
         _chk(lib.gmmiv_tv_stats_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
                                        sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(N), _ptr(F), _ptr(seg_llk)))
         return N, F, seg_llk
+
+    def llr_trials(self, world, x, seg_begin, trial_seg, trial_model, ctop, complete=True, min_llk=-200.0, max_llk=200.0, llr=None, client_mean=None,
+                   world_mean=None):
+        """gmmiv_llr_trials: the GMM-UBM scores of the trials (trial_seg[i], trial_model[i]) -- segment of x, model of this batch -- against
+        the single-model handle `world`, in one device pass -> (llr [ntrial], client_mean [ntrial], world_mean [nseg]).  The outputs are
+        numpy arrays unless given.  With torch device tensors the results are written in the order of the context's stream: the call
+        itself waits for that stream while it uploads its tables and inside the world pass, but NOT after its last kernels --
+        ctx.sync() before reading the tensors on another stream.  seg_begin / trial_seg / trial_model are host lists."""
+        x, dt, T, ldx = _feat(x)
+        sb = np.ascontiguousarray(seg_begin, np.int64)
+        ts = np.ascontiguousarray(trial_seg, np.int32)
+        tm = np.ascontiguousarray(trial_model, np.int32)
+        assert sb.ndim == 1 and len(sb) >= 1 and ts.shape == tm.shape and ts.ndim == 1
+        if llr is None:
+            llr = np.empty(len(ts))
+        if client_mean is None:
+            client_mean = np.empty(len(ts))
+        if world_mean is None:
+            world_mean = np.empty(len(sb) - 1)
+        _chk(lib.gmmiv_llr_trials(self.ctx._h, world._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
+                                  ct.c_int64(len(sb) - 1), ts.ctypes.data_as(ct.c_void_p), tm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(ts)), int(ctop),
+                                  TOP_COMPLETE if complete else TOP_PARTIAL, ct.c_double(min_llk), ct.c_double(max_llk), _ptr(llr), _ptr(client_mean),
+                                  _ptr(world_mean)))
+        return llr, client_mean, world_mean
 
     def map_adapt(self, N, F, count, w0, mean0, cur_mean, method="MAPOccDep", mean=True, weight=False, reg=(16.0, 16.0, 16.0), alpha_mean=0.75,
                   mean_out=None, w_out=None, count_stride=1):

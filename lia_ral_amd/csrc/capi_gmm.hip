@@ -113,6 +113,8 @@ long gmmiv_ctx_set_option(gmmiv_ctx *c, const char *key, long value)
     else if (!strcmp(key, "stats_z")) slot = &c->stats_z;
     else if (!strcmp(key, "z_scratch_mb")) slot = &c->z_scratch_mb;
     else if (!strcmp(key, "models_scratch_mb")) slot = &c->models_scratch_mb;
+    else if (!strcmp(key, "trials_scratch_mb")) slot = &c->trials_scratch_mb;
+    else if (!strcmp(key, "trials_piece")) slot = &c->trials_piece;
     else if (!strcmp(key, "tv_batch")) slot = &c->tv_batch;
     else if (!strcmp(key, "tv_tett_direct")) slot = &c->tv_tett_direct;
     else if (!strcmp(key, "tv_stats_split")) slot = &c->tv_stats_split;

@@ -37,10 +37,13 @@ enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, 
        WS_GFLAG, WS_NORM, WS_FEAT_OFF, WS_FEAT_OUT, WS_FEAT_IDX, WS_FEAT_M0, WS_FEAT_M1, WS_FEAT_M2, WS_FEAT_M3,
        WS_NORM_OFF, WS_NORM_STATE, WS_NORM_DECAY,
        WS_MB_PT, WS_MB_TILES, WS_MB_IDS, WS_MB_SEG,
+       WS_TR_IDX, WS_TR_NLLK, WS_TR_LLKW, WS_TR_TILES, WS_TR_TAB, WS_TR_PART, WS_TR_ROW,
        WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask;
                    // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables);
                    // WS_NORM_*: gmmiv_feat_norm_online (chunk offsets of the files, the carried states, the chunks' decay products)
                    // WS_MB_*: gmmiv_*_models (the packed models of a chunk, the tile tables, the model lists, the segment bounds of all chunks)
+                   // WS_TR_*: gmmiv_llr_trials (a chunk's world indices / remainders / log-likelihoods, the tile table, the trial and segment
+                   // tables, the piece partials of the whole call, one trial's per-frame row on the any-shape path)
 
 struct gmmiv_ctx {
     int device = 0;
@@ -100,6 +103,10 @@ struct gmmiv_ctx {
     // gmmiv_*_models: MiB of packed models per chunk of segments (2 MiB per model at 2048 x 60: 1024 models; the pack pass writes what
     // the log-likelihood kernel then reads at least once, so a larger scratch buys nothing but fewer launches)
     long models_scratch_mb = 2048;
+    // gmmiv_llr_trials: MiB of per-frame world results (indices, remainder, log-likelihood: 4 ctop + 16 bytes per frame) kept per chunk of
+    // whole segments; "trials_piece" (A/B knob, 0 = GMMIV_TRIAL_PIECE) changes the summation pieces and with them the last bits
+    long trials_scratch_mb = 2048;
+    long trials_piece = 0;
     int n_cu = 256;
     // gmmiv_score_plda: K_n = (n FTJF + I)^-1 and log det K_n per session count n, kept while FTJF stays the same matrix
     // (each costs an O(rankF^3) inverse on the host: 3 ms per call at rankF = 200 when recomputed every time)

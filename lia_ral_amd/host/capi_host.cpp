@@ -5,6 +5,11 @@
 #include <string.h>
 
 #include <chrono>
+#include <fstream>
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
 #include <memory>
 
 #include "liatools_gpu.h"
@@ -1189,6 +1194,238 @@ int liagpu_compute_test_files(int device, const char *world_path, int nClients, 
                                    frameIdxToTime(segs[s].begin, frameLength), frameIdxToTime(segs[s].begin + segs[s].length, frameLength)) + "\n";
         if ((long)text.size() + 1 > out_cap) throw Exception("out_text too small");
         memcpy(out_text, text.c_str(), text.size() + 1);
+    })
+}
+
+// ---- ComputeTest for a whole trial list (computeTestBatch) ------------------------------------------------------------------------------
+// the lists of an ndx in flat form: line l owns the segments [line_seg_off[l], line_seg_off[l + 1]) of seg_begin / seg_len and the clients
+// line_clients[line_cl_off[l] .. line_cl_off[l + 1]) (indices into the nModels models).  Checked before any device is touched.
+static void check_lines(long nlines, const long *line_seg_off, const long *line_cl_off, const long *line_clients, int nModels)
+{
+    if (nlines < 0 || !line_seg_off || !line_cl_off) throw Exception("compute_test_batch: bad line tables");
+    if (line_seg_off[0] != 0 || line_cl_off[0] != 0) throw Exception("compute_test_batch: the offset tables must start at 0");
+    for (long l = 0; l < nlines; ++l) {
+        if (line_seg_off[l + 1] < line_seg_off[l] || line_cl_off[l + 1] < line_cl_off[l]) throw Exception("compute_test_batch: the offset tables must be non-decreasing");
+        for (long k = line_cl_off[l]; k < line_cl_off[l + 1]; ++k)
+            if (line_clients[k] < 0 || line_clients[k] >= nModels)
+                throw Exception("compute_test_batch: line " + std::to_string(l) + " names client " + std::to_string(line_clients[k]) + " of " + std::to_string(nModels));
+    }
+}
+
+// models: nModels client models laid out one after the other, model g with model_C[g] Gaussians (model_C == NULL: all have C), covariances
+// as in liagpu_compute_test.  which = 0: computeTestBatch; 1: the computeTestLLR loop line by line, every model resident as its own
+// DeviceMixture.  llr_out: the lines' results one after the other, each [seg or 0][client]; *n_llr = their total.
+int liagpu_compute_test_batch(int device, const float *x, long T, int D, long nlines, const long *line_seg_off, const long *seg_begin, const long *seg_len,
+                              int C, const double *w_world, const double *mean_world, const double *cov_world, int nModels, const int *model_C,
+                              const double *w_cl, const double *mean_cl, const double *cov_cl, const long *line_cl_off, const long *line_clients,
+                              int topDistribsCount, int complete, double minLLK, double maxLLK, int segmentalMode, int which, double *llr_out, long max_llr,
+                              long *n_llr)
+{
+    GUARD({
+        check_lines(nlines, line_seg_off, line_cl_off, line_clients, nModels);
+        if (which != 0 && which != 1) throw Exception("compute_test_batch: which must be 0 (batch) or 1 (per-line loop)");
+        long need = 0;
+        for (long l = 0; l < nlines; ++l) need += (segmentalMode ? line_seg_off[l + 1] - line_seg_off[l] : 1) * (line_cl_off[l + 1] - line_cl_off[l]);
+        if (need > max_llr) throw Exception("compute_test_batch: llr_out too small");
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD world = make_mixture(C, D, w_world, mean_world, cov_world);
+        DeviceMixture dworld(srv, world);
+        std::vector<MixtureGD> models;
+        size_t ow = 0, om = 0;
+        for (int g = 0; g < nModels; ++g) {
+            const int Cg = model_C ? model_C[g] : C;
+            models.push_back(make_mixture(Cg, D, w_cl + ow, mean_cl + om, cov_cl + om));
+            ow += (size_t)Cg; om += (size_t)Cg * D;
+        }
+        std::vector<SegCluster> sel((size_t)nlines);
+        std::vector<std::vector<unsigned long>> cl((size_t)nlines);
+        for (long l = 0; l < nlines; ++l) {
+            sel[(size_t)l] = make_cluster(seg_begin + line_seg_off[l], seg_len + line_seg_off[l], line_seg_off[l + 1] - line_seg_off[l]);
+            cl[(size_t)l].assign(line_clients + line_cl_off[l], line_clients + line_cl_off[l + 1]);
+        }
+        std::vector<std::vector<double>> out;
+        if (which == 0)
+            out = computeTestBatch(fs, sel, dworld, models, cl, topDistribsCount, complete != 0, minLLK, maxLLK, segmentalMode != 0);
+        else {
+            std::vector<std::unique_ptr<DeviceMixture>> dm;
+            for (const MixtureGD &m : models) dm.emplace_back(new DeviceMixture(srv, m));
+            for (long l = 0; l < nlines; ++l) {
+                std::vector<DeviceMixture *> c;
+                for (unsigned long g : cl[(size_t)l]) c.push_back(dm[g].get());
+                out.push_back(computeTestLLR(fs, sel[(size_t)l], dworld, c, topDistribsCount, complete != 0, minLLK, maxLLK, segmentalMode != 0));
+            }
+        }
+        long k = 0;
+        for (const auto &o : out) { memcpy(llr_out + k, o.data(), o.size() * sizeof(double)); k += (long)o.size(); }
+        if (n_llr) *n_llr = k;
+    })
+}
+
+// the lines of an ndx: test name + client names; empty lines skipped
+static void read_ndx(const char *ndx_path, std::vector<std::string> &tests, std::vector<std::vector<std::string>> &clients)
+{
+    std::ifstream in(ndx_path);
+    if (!in) throw Exception(std::string("cannot open the ndx file ") + ndx_path);
+    std::string line;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::string tok;
+        if (!(ls >> tok)) continue;
+        tests.push_back(tok);
+        clients.emplace_back();
+        while (ls >> tok) clients.back().push_back(tok);
+    }
+}
+
+// What liagpu_compute_test_ndx will produce for this ndx, from the ndx and the label files alone (host only, no device, no feature or
+// model file is opened): *n_llr = the number of scores (selected segments x clients, over all lines), *text_bytes = an upper bound of the
+// size of the result text including its terminator.  The caller sizes llr_out / out_text with them.
+int liagpu_compute_test_ndx_count(const char *ndx_path, const char *label_path, const char *label_ext, const char *label, double frameLength,
+                                  const char *gender, long *n_llr, long *text_bytes)
+{
+    GUARD({
+        std::vector<std::string> tests;
+        std::vector<std::vector<std::string>> cl;
+        read_ndx(ndx_path, tests, cl);
+        long n = 0, bytes = 1;
+        const size_t fixed = strlen(gender ? gender : "") + 96; // separators, the decision, two times and a score of at most 24 characters each
+        for (size_t l = 0; l < tests.size(); ++l) {
+            const size_t nseg = selectSegments(readLabelFile(std::string(label_path) + tests[l] + label_ext), label, frameLength).size();
+            n += (long)(nseg * cl[l].size());
+            for (const std::string &id : cl[l]) bytes += (long)(nseg * (fixed + id.size() + tests[l].size()));
+        }
+        *n_llr = n;
+        *text_bytes = bytes;
+    })
+}
+
+// ComputeTest from FILES for a whole ndx (segmental mode, like liagpu_compute_test_files): every line of ndx_path is a test file name
+// followed by the ids of its clients.  Test file <feature_path><name><feature_ext> with the selection of <label_path><name><label_ext>,
+// client model <model_path><id><model_ext> (RAW; each distinct id is read once).  All lines are scored in one computeTestBatch; out_text
+// receives the result lines in the format of liagpu_compute_test_files, line after line, llr_out the LLRs in the same order.
+int liagpu_compute_test_ndx(int device, const char *world_path, const char *ndx_path, const char *model_path, const char *model_ext,
+                            const char *feature_path, const char *feature_ext, const char *label_path, const char *label_ext, const char *mask,
+                            const char *label, double frameLength, int topDistribsCount, int complete, double minLLK, double maxLLK, const char *gender,
+                            double threshold, double *llr_out, long max_llr, long *n_llr, char *out_text, long out_cap)
+{
+    GUARD({
+        std::vector<std::string> tests, ids;
+        std::vector<std::vector<std::string>> names;
+        read_ndx(ndx_path, tests, names);
+        std::map<std::string, unsigned long> idOf;
+        std::vector<std::vector<unsigned long>> cl(tests.size());
+        for (size_t l = 0; l < tests.size(); ++l)
+            for (const std::string &tok : names[l]) {
+                auto it = idOf.find(tok);
+                if (it == idOf.end()) { it = idOf.emplace(tok, (unsigned long)ids.size()).first; ids.push_back(tok); }
+                cl[l].push_back(it->second);
+            }
+        MixtureGD world = readMixtureRAW(world_path);
+        std::vector<MixtureGD> models;
+        for (const std::string &id : ids) models.push_back(readMixtureRAW(std::string(model_path) + id + model_ext));
+        // the frames of all test files, one source per line
+        std::vector<float> frames;
+        std::vector<unsigned long> first;
+        std::vector<SegCluster> sel(tests.size());
+        for (size_t l = 0; l < tests.size(); ++l) {
+            FeatureFile ff = readFeatureFile(std::string(feature_path) + tests[l] + feature_ext, mask ? mask : "");
+            if (ff.vectSize != world.getVectSize()) throw Exception("vectSize of features and world model differ (" + tests[l] + ")");
+            first.push_back((unsigned long)(frames.size() / ff.vectSize));
+            frames.insert(frames.end(), ff.data.begin(), ff.data.end());
+            sel[l] = selectSegments(readLabelFile(std::string(label_path) + tests[l] + label_ext), label, frameLength, (unsigned long)l);
+        }
+        std::string text;
+        long k = 0;
+        if (!tests.empty()) {
+            GpuServer srv(device);
+            FeatureBuffer fs(srv, frames.data(), (unsigned long)(frames.size() / world.getVectSize()), world.getVectSize(), first);
+            DeviceMixture dworld(srv, world);
+            const std::vector<std::vector<double>> out = computeTestBatch(fs, sel, dworld, models, cl, topDistribsCount, complete != 0, minLLK, maxLLK, true);
+            for (size_t l = 0; l < tests.size(); ++l) {
+                const size_t nc = cl[l].size();
+                if (k + (long)out[l].size() > max_llr) throw Exception("llr_out too small");
+                memcpy(llr_out + k, out[l].data(), out[l].size() * sizeof(double));
+                k += (long)out[l].size();
+                for (size_t s = 0; s < sel[l].size(); ++s)
+                    for (size_t i = 0; i < nc; ++i)
+                        text += resultLine(out[l][s * nc + i], ids[cl[l][i]], tests[l], gender, threshold, true, frameIdxToTime(sel[l][s].begin, frameLength),
+                                           frameIdxToTime(sel[l][s].begin + sel[l][s].length, frameLength)) + "\n";
+            }
+        }
+        if (n_llr) *n_llr = k;
+        if ((long)text.size() + 1 > out_cap) throw Exception("out_text too small");
+        memcpy(out_text, text.c_str(), text.size() + 1);
+    })
+}
+
+// tools/bench_computetest.py: nlines test segments of frames_per_line frames each (line l = frames [l n, (l + 1) n)), every line scored against
+// clients_per_line of the nModels client models (line_clients [nlines x clients_per_line]); the models are the world's with the means
+// mean_cl [nModels x C*D].  Timed on the host around the whole scoring (features and -- for the loop -- the models resident, the stream
+// drained before and after): which = 0 computeTestBatch on a resident DeviceMixtureBatch, 1 = computeTestLLR line after line on resident
+// DeviceMixtures, 2 = computeTestBatch from the host models (their upload is inside the timed region).  ms_out[reps]; then one more pass with the kernel timers on: kernel_ms[0..4] = k_llk_mfma,
+// k_topc_rank, k_topc_use, k_trial_reduce of the LAST call of that pass (-1: not run) and [4] = the trial piece in effect.  llr_out
+// [nlines x clients_per_line].  trial_piece > 0 sets the context's "trials_piece" knob (A/B runs).
+int liagpu_bench_computetest(int device, const float *x, long T, int D, long nlines, long frames_per_line, int C, const double *w, const double *mean,
+                             const double *cov, int nModels, const double *mean_cl, long clients_per_line, const long *line_clients, int topDistribsCount,
+                             int complete, int which, int reps, long trial_piece, double *ms_out, double *kernel_ms, double *llr_out)
+{
+    GUARD({
+        if (nlines * frames_per_line > T) throw Exception("bench_computetest: not enough frames");
+        for (long k = 0; k < nlines * clients_per_line; ++k)
+            if (line_clients[k] < 0 || line_clients[k] >= nModels) throw Exception("bench_computetest: client index out of range");
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD world = make_mixture(C, D, w, mean, cov);
+        DeviceMixture dworld(srv, world);
+        if (trial_piece > 0) (void)gmmiv_ctx_set_option(srv.ctx(), "trials_piece", trial_piece);
+        const size_t CD = (size_t)C * D;
+        std::vector<MixtureGD> models((size_t)nModels, world);
+        for (int g = 0; g < nModels; ++g) memcpy(models[(size_t)g].means().data(), mean_cl + (size_t)g * CD, CD * sizeof(double));
+        std::vector<SegCluster> sel((size_t)nlines);
+        std::vector<std::vector<unsigned long>> cl((size_t)nlines);
+        for (long l = 0; l < nlines; ++l) {
+            Seg s;
+            s.begin = (unsigned long)(l * frames_per_line); s.length = (unsigned long)frames_per_line;
+            sel[(size_t)l].push_back(s);
+            cl[(size_t)l].assign(line_clients + l * clients_per_line, line_clients + (l + 1) * clients_per_line);
+        }
+        std::vector<std::unique_ptr<DeviceMixture>> dm;
+        std::unique_ptr<DeviceMixtureBatch> db;
+        if (which == 1)
+            for (const MixtureGD &m : models) dm.emplace_back(new DeviceMixture(srv, m));
+        if (which == 0) db.reset(new DeviceMixtureBatch(srv, models));
+        std::vector<std::vector<double>> out;
+        auto run = [&]() {
+            if (which == 0)
+                out = computeTestBatch(fs, sel, dworld, *db, cl, topDistribsCount, complete != 0, -200.0, 200.0, false);
+            else if (which == 2)
+                out = computeTestBatch(fs, sel, dworld, models, cl, topDistribsCount, complete != 0, -200.0, 200.0, false);
+            else {
+                out.assign((size_t)nlines, std::vector<double>());
+                for (long l = 0; l < nlines; ++l) {
+                    std::vector<DeviceMixture *> c;
+                    for (unsigned long g : cl[(size_t)l]) c.push_back(dm[g].get());
+                    out[(size_t)l] = computeTestLLR(fs, sel[(size_t)l], dworld, c, topDistribsCount, complete != 0, -200.0, 200.0, false);
+                }
+            }
+            srv.sync();
+        };
+        for (int r = 0; r < reps; ++r) {
+            srv.sync();
+            const auto t0 = std::chrono::steady_clock::now();
+            run();
+            ms_out[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 1);
+        run();
+        kernel_ms[0] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_llk_mfma");
+        kernel_ms[1] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_topc_rank");
+        kernel_ms[2] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_topc_use");
+        kernel_ms[3] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_trial_reduce");
+        kernel_ms[4] = (double)(trial_piece > 0 ? trial_piece : GMMIV_TRIAL_PIECE);
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 0);
+        for (long l = 0; l < nlines; ++l) memcpy(llr_out + l * clients_per_line, out[(size_t)l].data(), (size_t)clients_per_line * sizeof(double));
     })
 }
 

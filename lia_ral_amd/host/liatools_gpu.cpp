@@ -1618,6 +1618,121 @@ std::vector<double> computeTestLLR(FeatureBuffer &fs, const SegCluster &selected
     return out;
 }
 
+std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, DeviceMixture &world,
+                                                  const std::vector<MixtureGD> &clientModels,
+                                                  const std::vector<std::vector<unsigned long>> &clientsPerLine, int topDistribsCount,
+                                                  bool complete, double minLLK, double maxLLK, bool segmentalMode)
+{
+    const size_t L = selectedPerLine.size(), G = clientModels.size();
+    if (clientsPerLine.size() != L) throw Exception("computeTestBatch: one client list per line is needed");
+    for (const auto &cl : clientsPerLine)
+        for (unsigned long g : cl)
+            if (g >= G) throw Exception("computeTestBatch: client " + std::to_string(g) + " outside the " + std::to_string(G) + " models");
+    std::vector<std::vector<double>> out(L);
+    if (L == 0) return out;
+    GpuServer &srv = fs.server();
+    const unsigned long C = world.getDistribCount(), D = world.getVectSize();
+    bool batched = G > 0;
+    for (size_t g = 0; g < G && batched; ++g) batched = clientModels[g].getDistribCount() == C && clientModels[g].getVectSize() == D;
+    if (!batched) { // the per-line loop: the models of a line live on the device while the line is scored
+        for (size_t l = 0; l < L; ++l) {
+            std::vector<std::unique_ptr<DeviceMixture>> own;
+            std::vector<DeviceMixture *> cl;
+            for (unsigned long g : clientsPerLine[l]) {
+                own.emplace_back(new DeviceMixture(srv, clientModels[g]));
+                cl.push_back(own.back().get());
+            }
+            out[l] = computeTestLLR(fs, selectedPerLine[l], world, cl, topDistribsCount, complete, minLLK, maxLLK, segmentalMode);
+        }
+        return out;
+    }
+    DeviceMixtureBatch batch(srv, clientModels);
+    return computeTestBatch(fs, selectedPerLine, world, batch, clientsPerLine, topDistribsCount, complete, minLLK, maxLLK, segmentalMode);
+}
+
+DeviceMixtureBatch::DeviceMixtureBatch(GpuServer &srv, const std::vector<MixtureGD> &models) : _g(models.size())
+{
+    if (models.empty()) throw Exception("DeviceMixtureBatch: no model");
+    const unsigned long C = _c = models[0].getDistribCount(), D = _d = models[0].getVectSize();
+    const size_t G = _g, CD = (size_t)C * D;
+    for (const MixtureGD &m : models)
+        if (m.getDistribCount() != C || m.getVectSize() != D) throw Exception("DeviceMixtureBatch: the models differ in shape");
+    // means per model; weights and covInv ONE shared row when all models have the same (MAP with means only).  The models' tables are
+    // separate host vectors: they go up, vector by vector, into a staging buffer that lives for this constructor only, and
+    // gmmiv_gmm_batch_load copies from there into the batch's own tables (no host copy of G x C x D doubles in between)
+    bool sameW = true, sameIv = true;
+    for (size_t g = 1; g < G && (sameW || sameIv); ++g) {
+        sameW = sameW && models[g].weights_c() == models[0].weights_c();
+        sameIv = sameIv && models[g].covInvs() == models[0].covInvs();
+    }
+    const size_t nW = sameW ? C : G * C, nIv = sameIv ? CD : G * CD;
+    struct Staging {
+        double *p = nullptr;
+        ~Staging() { if (p) (void)hipFree(p); }
+    } stage;
+    hipcheck(hipMalloc((void **)&stage.p, (G * CD + nW + nIv) * sizeof(double)), "DeviceMixtureBatch: staging buffer");
+    double *dM = stage.p, *dW = dM + G * CD, *dIv = dW + nW;
+    hipStream_t st = (hipStream_t)srv.stream();
+    srv.check(gmmiv_gmm_batch_create(srv.ctx(), (int)G, (int)C, (int)D, &_b));
+    try {
+        for (size_t g = 0; g < G; ++g) {
+            hipcheck(hipMemcpyAsync(dM + g * CD, models[g].means_c().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "DeviceMixtureBatch: upload");
+            if (!sameW || g == 0) hipcheck(hipMemcpyAsync(dW + g * C, models[g].weights_c().data(), C * sizeof(double), hipMemcpyHostToDevice, st), "DeviceMixtureBatch: upload");
+            if (!sameIv || g == 0) hipcheck(hipMemcpyAsync(dIv + g * CD, models[g].covInvs().data(), CD * sizeof(double), hipMemcpyHostToDevice, st), "DeviceMixtureBatch: upload");
+        }
+        srv.check(gmmiv_gmm_batch_load(_b, dW, sameW ? 0 : (int64_t)C, dM, (int64_t)CD, dIv, sameIv ? 0 : (int64_t)CD));
+        srv.sync(); // the load's device-to-device copies have read the staging buffer before it is freed
+    } catch (...) { gmmiv_gmm_batch_destroy(_b); throw; }
+}
+DeviceMixtureBatch::~DeviceMixtureBatch() { gmmiv_gmm_batch_destroy(_b); }
+
+std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, DeviceMixture &world,
+                                                  DeviceMixtureBatch &clientModels, const std::vector<std::vector<unsigned long>> &clientsPerLine,
+                                                  int topDistribsCount, bool complete, double minLLK, double maxLLK, bool segmentalMode)
+{
+    const size_t L = selectedPerLine.size(), G = clientModels.size();
+    if (clientsPerLine.size() != L) throw Exception("computeTestBatch: one client list per line is needed");
+    for (const auto &cl : clientsPerLine)
+        for (unsigned long g : cl)
+            if (g >= G) throw Exception("computeTestBatch: client " + std::to_string(g) + " outside the " + std::to_string(G) + " models");
+    const unsigned long C = world.getDistribCount(), D = world.getVectSize();
+    if (clientModels.getDistribCount() != C || clientModels.getVectSize() != D) throw Exception("computeTestBatch: the batch has another shape than the world model");
+    std::vector<std::vector<double>> out(L);
+    if (L == 0) return out;
+    GpuServer &srv = fs.server();
+    topDistribsCount = (int)std::min<unsigned long>((unsigned long)std::max(topDistribsCount, 1), C);
+    // one gather of all lines' frames, line after line; a segment of the call = a selected segment (segmentalMode) or a whole line
+    SegCluster all;
+    std::vector<int64_t> segBegin(1, 0);
+    std::vector<int32_t> trialSeg, trialModel;
+    std::vector<size_t> lineSeg(L + 1, 0);
+    for (size_t l = 0; l < L; ++l) {
+        all.insert(all.end(), selectedPerLine[l].begin(), selectedPerLine[l].end());
+        if (segmentalMode)
+            for (const Seg &s : selectedPerLine[l]) segBegin.push_back(segBegin.back() + (int64_t)s.length);
+        else
+            segBegin.push_back(segBegin.back() + (int64_t)totalFrame(selectedPerLine[l]));
+        lineSeg[l + 1] = segBegin.size() - 1;
+        for (size_t s = lineSeg[l]; s < lineSeg[l + 1]; ++s)
+            for (unsigned long g : clientsPerLine[l]) { trialSeg.push_back((int32_t)s); trialModel.push_back((int32_t)g); }
+    }
+    const size_t nseg = segBegin.size() - 1, ntrial = trialSeg.size();
+    unsigned long n = 0;
+    const float *x = fs.select(all, n);
+    FiniteScope fin(srv, fs);
+    std::vector<double> llr(ntrial, 0.0);
+    srv.check(gmmiv_llr_trials(srv.ctx(), world.handle(), clientModels.handle(), x, GMMIV_F32, (int64_t)n, (int64_t)D, segBegin.data(), (int64_t)nseg, trialSeg.data(),
+                               trialModel.data(), (int64_t)ntrial, topDistribsCount, complete ? GMMIV_TOP_COMPLETE : GMMIV_TOP_PARTIAL, minLLK, maxLLK,
+                               ntrial ? llr.data() : nullptr, nullptr, nullptr));
+    size_t k = 0;
+    for (size_t l = 0; l < L; ++l) {
+        const size_t cnt = (lineSeg[l + 1] - lineSeg[l]) * clientsPerLine[l].size();
+        out[l].assign(llr.begin() + k, llr.begin() + k + cnt);
+        k += cnt;
+    }
+    return out;
+}
+
 WindowLLR::WindowLLR(unsigned long size, unsigned long dec, unsigned long nClient)
     : _size(size), _dec(dec), _nClient(nClient), _bIdx(0), _count(0), _idx(size, 0), _acc(nClient, 0.0), _llr(size * nClient, 0.0) {}
 void WindowLLR::dec(unsigned long idxFrame)

@@ -381,6 +381,39 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
 std::vector<double> computeTestLLR(FeatureBuffer &fs, const SegCluster &selectedSegments, DeviceMixture &world,
                                    std::vector<DeviceMixture *> &clients, int topDistribsCount, bool complete,
                                    double minLLK, double maxLLK, bool segmentalMode);
+// The same for a whole ndx in one device pass (gmmiv_llr_trials): line l scores the selection selectedPerLine[l] against the models
+// clientModels[clientsPerLine[l][..]].  Element l of the result is what computeTestLLR(fs, selectedPerLine[l], world, <those clients>, ...)
+// returns, layout [seg or 0][client] -- to the last bits of another summation order (pieces of GMMIV_TRIAL_PIECE frames instead of
+// gmmiv_segment_means' pieces).  The selections of all lines are gathered once, line after line (the way adaptModelBatch lays out its
+// clients'); the models go into one gmmiv_gmm_batch, weights and covInv as ONE shared row when every client has the same.  Clients of
+// another shape than the world run the per-line computeTestLLR loop.
+std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, DeviceMixture &world,
+                                                  const std::vector<MixtureGD> &clientModels,
+                                                  const std::vector<std::vector<unsigned long>> &clientsPerLine, int topDistribsCount,
+                                                  bool complete, double minLLK, double maxLLK, bool segmentalMode);
+// Device copies of MANY MixtureGD of one shape (what DeviceMixture is for one): a gmmiv_gmm_batch.  A caller that scores several trial
+// lists against the same client set builds it once and passes it to the overload below; the overload above builds one per call (the
+// upload of 1000 models of 2048 x 60 is 1 GB across PCIe).  Throws when the models differ in shape.
+class DeviceMixtureBatch {
+  public:
+    DeviceMixtureBatch(GpuServer &srv, const std::vector<MixtureGD> &models);
+    ~DeviceMixtureBatch();
+    DeviceMixtureBatch(const DeviceMixtureBatch &) = delete;
+    DeviceMixtureBatch &operator=(const DeviceMixtureBatch &) = delete;
+    gmmiv_gmm_batch *handle() const { return _b; }
+    size_t size() const { return _g; }
+    unsigned long getDistribCount() const { return _c; }
+    unsigned long getVectSize() const { return _d; }
+
+  private:
+    gmmiv_gmm_batch *_b = nullptr;
+    size_t _g = 0;
+    unsigned long _c = 0, _d = 0;
+};
+// the batch must have the world's shape
+std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, DeviceMixture &world,
+                                                  DeviceMixtureBatch &clientModels, const std::vector<std::vector<unsigned long>> &clientsPerLine,
+                                                  int topDistribsCount, bool complete, double minLLK, double maxLLK, bool segmentalMode);
 // WindowLLR (LIA_SpkTools/src/UnsupervisedTools.cpp:70-145): sliding window over the per-frame LLRs of ComputeTest
 // (ComputeTest.cpp:165-178).  One WindowOut per position at which the window is full.
 struct WindowLLR {

@@ -664,6 +664,86 @@ def compute_test_files(world_path, client_paths, client_names, prm_path, lbl_pat
     return llr[:len(lines)].reshape(-1, n), lines
 
 
+def _lines(seg_begin_per_line, seg_len_per_line, clients_per_line, n_models):
+    """flat tables of a trial list (liagpu_compute_test_batch); raises HostError for what needs no device to be refused"""
+    if not (len(seg_begin_per_line) == len(seg_len_per_line) == len(clients_per_line)):
+        raise HostError("compute_test_batch: one segment list and one client list per line are needed")
+    so = [0]; co = [0]; sb = []; sl = []; cl = []
+    for l, (b, n, c) in enumerate(zip(seg_begin_per_line, seg_len_per_line, clients_per_line)):
+        if len(b) != len(n):
+            raise HostError("compute_test_batch: line %d has %d segment begins and %d lengths" % (l, len(b), len(n)))
+        for g in c:
+            if not 0 <= int(g) < n_models:
+                raise HostError("compute_test_batch: line %d names client %d of %d" % (l, int(g), n_models))
+        sb += [int(v) for v in b]; sl += [int(v) for v in n]; cl += [int(g) for g in c]
+        so.append(len(sb)); co.append(len(cl))
+    return [np.ascontiguousarray(a, np.int64) for a in (so, sb, sl, co, cl)]
+
+
+def compute_test_batch(x, seg_begin_per_line, seg_len_per_line, world, models, clients_per_line, top_c=10, complete=True, min_llk=-200.0,
+                       max_llk=200.0, segmental=False, loop=False, device=0):
+    """ComputeTest for a whole trial list in one device pass (liagpu::computeTestBatch): line l scores the segments
+    (seg_begin_per_line[l], seg_len_per_line[l]) of x against the models clients_per_line[l] (indices into `models`, a list of
+    (w, mean, cov) like compute_test's clients; the Gaussian counts may differ -- such a list runs the per-line loop).  loop=True: the
+    computeTestLLR loop line by line.  -> list of LLR[n_seg_or_1, n_clients_of_the_line]."""
+    x = np.ascontiguousarray(x, np.float32)
+    T, D = x.shape
+    ww, mw, cw = [np.ascontiguousarray(a, np.float64) for a in world]
+    so, sb, sl, co, cl = _lines(seg_begin_per_line, seg_len_per_line, clients_per_line, len(models))
+    mC = np.ascontiguousarray([len(m[0]) for m in models], np.int32)
+    cat = lambda k: np.ascontiguousarray(np.concatenate([np.asarray(m[k], np.float64).ravel() for m in models]) if models else np.zeros(0))
+    wc, mc, cc = cat(0), cat(1), cat(2)
+    nl = len(so) - 1
+    per = [(int(so[l + 1] - so[l]) if segmental else 1, int(co[l + 1] - co[l])) for l in range(nl)]
+    out = np.empty(max(1, sum(a * b for a, b in per)))
+    n = ct.c_long(0)
+    p = lambda a: a.ctypes.data_as(_lp)
+    _chk(lib.liagpu_compute_test_batch(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(nl), p(so), p(sb), p(sl), len(ww), _d(ww), _d(mw), _d(cw),
+                                       len(models), mC.ctypes.data_as(ct.POINTER(ct.c_int)), _d(wc), _d(mc), _d(cc), p(co), p(cl), int(top_c),
+                                       int(complete), ct.c_double(min_llk), ct.c_double(max_llk), int(segmental), int(bool(loop)), _d(out),
+                                       ct.c_long(len(out)), ct.byref(n)))
+    res, k = [], 0
+    for a, b in per:
+        res.append(out[k:k + a * b].reshape(a, b).copy())
+        k += a * b
+    return res
+
+
+def compute_test_ndx(world_path, ndx_path, model_path, feature_path, label_path, model_ext=".gmm", feature_ext=".prm", label_ext=".lbl", mask="",
+                     label="male", frame_length=0.01, top_c=10, complete=True, min_llk=-200.0, max_llk=200.0, gender="M", threshold=0.0, device=0):
+    """ComputeTest (segmental mode) for a whole ndx -- every line a test file name followed by its client ids -- in one device pass.  Files:
+    <feature_path><test><feature_ext>, <label_path><test><label_ext>, <model_path><id><model_ext> (RAW).  -> (LLR [flat, line after line,
+    each [segment][client]], result lines in the format of compute_test_files)."""
+    n = ct.c_long(0); nbytes = ct.c_long(0)                     # sizes from the ndx and the label files (host only)
+    _chk(lib.liagpu_compute_test_ndx_count(ndx_path.encode(), label_path.encode(), label_ext.encode(), label.encode(), ct.c_double(frame_length),
+                                           gender.encode(), ct.byref(n), ct.byref(nbytes)))
+    llr = np.empty(max(n.value, 1))
+    text = ct.create_string_buffer(max(nbytes.value, 1))
+    _chk(lib.liagpu_compute_test_ndx(device, world_path.encode(), ndx_path.encode(), model_path.encode(), model_ext.encode(), feature_path.encode(),
+                                     feature_ext.encode(), label_path.encode(), label_ext.encode(), mask.encode(), label.encode(),
+                                     ct.c_double(frame_length), int(top_c), int(complete), ct.c_double(min_llk), ct.c_double(max_llk), gender.encode(),
+                                     ct.c_double(threshold), llr.ctypes.data_as(_dp), ct.c_long(len(llr)), ct.byref(n), text, ct.c_long(len(text))))
+    t = text.value.decode().strip()
+    return llr[:n.value].copy(), (t.split("\n") if t else [])
+
+
+def bench_computetest(x, world, mean_cl, line_clients, frames_per_line, top_c=10, complete=True, which=0, reps=3, trial_piece=0, device=0):
+    """liagpu_bench_computetest (tools/bench_computetest.py): len(line_clients) lines of frames_per_line frames of x, line l against the
+    models line_clients[l] (rows of mean_cl [n_models, C*D]; weights and variances the world's); which = 0: computeTestBatch on resident
+    models, 1: the computeTestLLR loop on resident models, 2: computeTestBatch from host models -> dict(ms [reps], kernel_ms, llr)."""
+    x = np.ascontiguousarray(x, np.float32)
+    T, D = x.shape
+    ww, mw, cw = [np.ascontiguousarray(a, np.float64) for a in world]
+    mean_cl = np.ascontiguousarray(mean_cl, np.float64).reshape(-1, len(ww) * D)
+    lc = np.ascontiguousarray(line_clients, np.int64)
+    nl, per = lc.shape
+    ms = np.zeros(max(reps, 1)); km = np.zeros(5); llr = np.empty((nl, per))
+    _chk(lib.liagpu_bench_computetest(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(nl), ct.c_long(frames_per_line), len(ww), _d(ww), _d(mw),
+                                      _d(cw), len(mean_cl), _d(mean_cl), ct.c_long(per), lc.ctypes.data_as(_lp), int(top_c), int(complete), int(which),
+                                      int(reps), ct.c_long(trial_piece), _d(ms), _d(km), _d(llr)))
+    return dict(ms=ms[:reps], kernel_ms=dict(k_llk_mfma=km[0], k_topc_rank=km[1], k_topc_use=km[2], k_trial_reduce=km[3]), piece=int(km[4]), llr=llr)
+
+
 def energy_detector(energy, seg_begin, seg_len, C=2, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.25, device=0):
     """EnergyDetector (meanStd mode) on one energy column -> dict(begin, length, w, mean, cov, threshold)."""
     e = np.ascontiguousarray(energy, np.float32)
