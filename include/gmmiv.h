@@ -765,6 +765,61 @@ int gmmiv_score_normalize(gmmiv_ctx *ctx, int64_t M, int64_t S, double *scores, 
  * (0 when out of range): lets a caller check that a repeated call allocates nothing. */
 size_t gmmiv_ctx_workspace_bytes(gmmiv_ctx *ctx, int slot);
 
+/* ---- score normalisation on lists: sparse trials and per-entity cohorts of different lengths ------------------------------
+ * The reference keeps one growing list of scores per name (DistribNorm, ComputeNorm.cpp:104-118), filled line by line
+ * (getAllScores / getAllScoresFirstNormed, :446-489), and walks the test list with two name lookups per line (:542-554, :576-589,
+ * :634-658, :717-742): nothing there asks for a full cross product.  These two calls are that, on a CSR list over a score array.
+ * gmmiv_score_list_stats: DistribNorm::computeMeanStd (:121-159) for ndist distributions.  Distribution d owns the slots k in
+ *   [off[d], off[d + 1]); slot k holds v = scores[pos ? pos[k] : k], and with pre_id the value
+ *   (v - pre_mean[pre_id[k]]) / pre_std[pre_id[k]] -- exactly these two operations, computed on the fly (:480): the zt / tz chains
+ *   never materialise a normalised copy.  One scores array (the llr of a gmmiv_llr_trials call, say) serves two calls through two
+ *   pos tables, one grouped by model (z), one by segment (t).
+ *   off:      a HOST table of ndist + 1 offsets, non-decreasing, off[0] >= 0; copied before return.  Slots before off[0] are never
+ *             read (pos and pre_id are indexed by slot all the same).  Every other array is a host or a device array.
+ *   mean_mode, percent_h, percent_l: as for gmmiv_score_cohort_stats, with n = off[d + 1] - off[d], discardH = (unsigned long)
+ *             ((double)n * percent_h), discardL likewise and size = n - discardH - discardL taken PER DISTRIBUTION.  The quirk is
+ *             kept: mean_mode 1 with both percentages zero does not sort, its "median" is the score at slot off[d] + n / 2.
+ *   RESULT:   the (mean, std) of a distribution are THE BITS gmmiv_score_cohort_stats returns with axis = 0, select = NULL for a
+ *             one-row matrix holding the same values in the same order (pre_mean / pre_std gathered into vectors of that length).
+ *             Thread count, wave or workgroup path, staging, and with them the fp64 summation order, are functions of the
+ *             distribution's own length; they do not depend on its neighbours, on ndist or on how the call groups distributions
+ *             into launches.  Ties, the sum bound (n - 1) 2^-53 sum|x| and NaN (outside the contract) are therefore the dense call's.
+ *   GMMIV_ERR_ARG, before anything is enqueued and naming the first offending distribution: a decreasing off; a distribution
+ *             with n == 0 or an empty kept range (the reference: "Problem: empty impostor cohort"); pre_id without both pre_*
+ *             vectors or the reverse; a percentage outside [0, 1); an unknown mean_mode; a HOST pos / pre_id entry outside
+ *             [0, nscores) / [0, npre) (device tables are not checked); without pos, a list that ends beyond nscores.  The
+ *             arguments are checked before the context is looked at.  ndist == 0 is valid.
+ *   Planning: the distributions are binned on the host by length class -- the lengths that share a launch shape of the dense call
+ *             -- and every class that occurs is one launch.  gmmiv_score_list_class gives the class of a length (streaming = the
+ *             untrimmed mean_mode 0: 2 classes, else GMMIV_SCORE_LIST_CLASSES), its threads per workgroup and the scores its
+ *             workgroups stage in LDS (0: none); gmmiv_plan_score_lists (pure host function, needs no GPU) gives cls[d], the
+ *             distributions ordered by class (table order inside a class) and class_begin[GMMIV_SCORE_LIST_CLASSES + 1] into that
+ *             order; each output may be NULL.  It returns the number of classes that occur, or -1 for a bad table.
+ *   Device scratch: GMMIV_SCORE_LIST_SCRATCH_BYTES(ndist) = 12 ndist + 8 bytes (+ the workspace's growth slack of 1/8) in the slot
+ *             gmmiv_ctx_workspace_bytes(ctx, -1) reports: off as 8-byte and the class order as 4-byte entries.  Histograms and
+ *             staged keys live in LDS.  A repeated call allocates nothing.  Host arrays are staged like everywhere else.
+ *   Synchronisation: the call is NOT enqueue-only: it waits for the context's stream once, after uploading its two tables (they
+ *             live in host memory of the call).  With device arrays everything after that is only enqueued.
+ * gmmiv_score_normalize_list: scores[i] <- (scores[i] - row_mean[row_id[i]]) / row_std[row_id[i]] and / or the same with the column
+ *   vectors, i < n, in place, every step one subtraction and one true division; order GMMIV_NORM_Z / T / ZT (t first) / TZ (z first)
+ *   as for gmmiv_score_normalize.  first_out: NULL, or [n] for the value after the first of two steps.  The ids and vectors an order
+ *   needs must be present; a HOST id outside [0, nrow) / [0, ncol) is GMMIV_ERR_ARG.  n == 0 is valid.  Only enqueues with device
+ *   arrays.
+ * Kernel timers: "k_norm_stats" (summed over the launches of a call) and "k_norm_apply". */
+#define GMMIV_SCORE_LIST_SCRATCH_BYTES(ndist) ((size_t)12 * (size_t)(ndist) + (size_t)8)
+#define GMMIV_SCORE_LIST_CLASSES 7
+int gmmiv_score_list_class(int64_t n, int streaming, int *threads /* nullable */, int64_t *stage_scores /* nullable */);
+int64_t gmmiv_plan_score_lists(int64_t ndist, const int64_t *off /* ndist + 1 */, int streaming, int32_t *cls /* [ndist] */,
+                               int32_t *order /* [ndist] */, int64_t *class_begin /* [GMMIV_SCORE_LIST_CLASSES + 1] */);
+int gmmiv_score_list_stats(gmmiv_ctx *ctx, int64_t ndist, const int64_t *off /* HOST, ndist + 1 */,
+                           const int64_t *pos /* nullable */, const double *scores, int64_t nscores,
+                           const int32_t *pre_id /* nullable */, const double *pre_mean, const double *pre_std, int64_t npre,
+                           int mean_mode, double percent_h, double percent_l, double *mean /* [ndist] */, double *std /* [ndist] */);
+int gmmiv_score_normalize_list(gmmiv_ctx *ctx, int64_t n, double *scores, int order,
+                               const int32_t *row_id, const double *row_mean, const double *row_std, int64_t nrow,
+                               const int32_t *col_id, const double *col_mean, const double *col_std, int64_t ncol,
+                               double *first_out /* nullable */);
+
 /* ---- JFA (LIA_SpkTools/src/AccumulateJFAStat.cpp): model M_{s,h} = m + V y_s + U x_h + D z_s ---------------------------
  * The factor steps are the total-variability entry points under the JFA names:
  *   JFAAcc::estimateVEVT / estimateUEUT (:1266-1352, :1425-1508)                         -> gmmiv_tv_tett

@@ -41,6 +41,7 @@ def _load():
     lib.gmmiv_ctx_stream.restype = ct.c_void_p
     lib.gmmiv_plan_model_tiles.restype = ct.c_int64
     lib.gmmiv_plan_trial_tiles.restype = ct.c_int64
+    lib.gmmiv_plan_score_lists.restype = ct.c_int64
     return lib
 
 
@@ -654,6 +655,41 @@ class Context:
                                        _ptr(_f64(row_std)), _ptr(_f64(col_mean)), _ptr(_f64(col_std)), _ptr(first_out)))
         return scores
 
+    # ---- score normalisation on lists: CSR distributions of different lengths, a list of trials
+    def score_list_stats(self, off, scores, pos=None, pre_id=None, pre_mean=None, pre_std=None, mean_mode=0, percent_h=0.0,
+                         percent_l=0.0, out_mean=None, out_std=None):
+        """mean, std of the distributions d = slots [off[d], off[d + 1]) of a score list the way DistribNorm::computeMeanStd computes
+        them; slot k holds scores[pos[k]] (scores[k] without pos), pre-normalised by (pre_mean, pre_std)[pre_id[k]] when given.
+        off: host int64.  The bits are those of score_cohort_stats(axis 0) on a one-row matrix of the same values."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        nd = len(off) - 1
+        scores = _f64(scores)
+        pos = pos if pos is None or _is_torch(pos) else np.ascontiguousarray(pos, np.int64)
+        pre_id = pre_id if pre_id is None or _is_torch(pre_id) else np.ascontiguousarray(pre_id, np.int32)
+        pre_mean, pre_std = _f64(pre_mean), _f64(pre_std)
+        if out_mean is None:
+            out_mean = np.empty(max(nd, 0))
+        if out_std is None:
+            out_std = np.empty(max(nd, 0))
+        npre = 0 if pre_mean is None else int(pre_mean.shape[0])
+        _chk(lib.gmmiv_score_list_stats(self._h, ct.c_int64(nd), _ptr(off), _ptr(pos), _ptr(scores), ct.c_int64(int(scores.shape[0])),
+                                        _ptr(pre_id), _ptr(pre_mean), _ptr(pre_std), ct.c_int64(npre), int(mean_mode),
+                                        ct.c_double(percent_h), ct.c_double(percent_l), _ptr(out_mean), _ptr(out_std)))
+        return out_mean, out_std
+
+    def score_normalize_list(self, scores, order, row_id=None, row_mean=None, row_std=None, col_id=None, col_mean=None, col_std=None,
+                             first_out=None):
+        """scores[n] in place: (x - row_mean[row_id[i]]) / row_std[row_id[i]] and / or the same with the column vectors, in the order
+        NORM_Z / NORM_T / NORM_ZT (t first) / NORM_TZ (z first).  first_out: None, or [n] for the value after the first of two."""
+        ids = lambda a: a if a is None or _is_torch(a) else np.ascontiguousarray(a, np.int32)
+        row_id, col_id = ids(row_id), ids(col_id)
+        row_mean, row_std, col_mean, col_std = _f64(row_mean), _f64(row_std), _f64(col_mean), _f64(col_std)
+        cnt = lambda v: 0 if v is None else int(v.shape[0])
+        _chk(lib.gmmiv_score_normalize_list(self._h, ct.c_int64(int(scores.shape[0])), _ptr(scores), int(order), _ptr(row_id),
+                                            _ptr(row_mean), _ptr(row_std), ct.c_int64(cnt(row_mean)), _ptr(col_id), _ptr(col_mean),
+                                            _ptr(col_std), ct.c_int64(cnt(col_mean)), _ptr(first_out)))
+        return scores
+
     def workspace_bytes(self, slot=-1):
         """Bytes held in the score-normalisation scratch slot (slot < 0) or in workspace slot `slot`."""
         return int(lib.gmmiv_ctx_workspace_bytes(self._h, int(slot)))
@@ -667,6 +703,33 @@ def norm_scratch_bytes(ndist):
     return 512 * int(ndist) + 64
 lib.gmmiv_ctx_workspace_bytes.restype = ct.c_size_t
 lib.gmmiv_ctx_workspace_bytes.argtypes = [ct.c_void_p, ct.c_int]
+
+
+SCORE_LIST_CLASSES = 7     # GMMIV_SCORE_LIST_CLASSES
+
+
+def list_scratch_bytes(ndist):
+    """GMMIV_SCORE_LIST_SCRATCH_BYTES(ndist): the device scratch of score_list_stats"""
+    return 12 * int(ndist) + 8
+
+
+def score_list_class(n, streaming):
+    """gmmiv_score_list_class -> (class of a distribution of n scores, threads per workgroup, scores staged in LDS)"""
+    thr = ct.c_int(0); stage = ct.c_int64(0)
+    k = lib.gmmiv_score_list_class(ct.c_int64(int(n)), int(bool(streaming)), ct.byref(thr), ct.byref(stage))
+    return int(k), thr.value, stage.value
+
+
+def plan_score_lists(off, streaming):
+    """gmmiv_plan_score_lists (host only, needs no GPU) -> (cls [ndist], order [ndist], class_begin [SCORE_LIST_CLASSES + 1], classes
+    that occur); streaming: the untrimmed mean_mode 0"""
+    off = np.ascontiguousarray(off, np.int64)
+    nd = len(off) - 1
+    cls = np.zeros(max(nd, 0), np.int32); order = np.zeros(max(nd, 0), np.int32); cb = np.zeros(SCORE_LIST_CLASSES + 1, np.int64)
+    used = lib.gmmiv_plan_score_lists(ct.c_int64(nd), _ptr(off), int(bool(streaming)), _ptr(cls), _ptr(order), _ptr(cb))
+    if used < 0:
+        raise GmmivError("gmmiv_plan_score_lists: bad offsets")
+    return cls, order, cb, int(used)
 
 
 def _data_ptr(a):

@@ -31,33 +31,9 @@
 
 #include "devutil.h"
 #include "lds_attr.h"
+#include "score_norm_dev.h" // keys, constants and shuffles shared with score_norm_lists.hip
 
 #pragma clang fp contract(off) // (x - mean) / std, sum / size, sum2 / size - mean * mean: the reference's IEEE operations, unfused
-
-typedef unsigned long long u64;
-
-#define SN_HS 257       // histogram stride in words (256 bins + 1: adjacent histograms start on different banks)
-#define SN_MAXT 1024    // threads per workgroup, at most
-#define SN_STAGE 16384  // scores of a row staged in LDS, at most
-#define SN_CAND 64      // candidates per rank the select finishes on by counting
-
-__device__ __forceinline__ u64 sn_key(double v)
-{
-    if (v == 0.0) v = 0.0; // -0.0 -> +0.0
-    const u64 b = (u64)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sn_val(u64 k)
-{
-    const u64 b = (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
-__device__ __forceinline__ u64 sn_shfl_xor(u64 v, int m)
-{
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64);
-    return ((u64)hi << 32) | lo;
-}
 
 // ---- counts of a device-resident mask: n, discardH, discardL, position of the (n / 2)-th set byte ----------------------
 __global__ __launch_bounds__(1024) void k_norm_mask_info(const unsigned char *mask, long L, double pH, double pL, long *info)
@@ -426,8 +402,6 @@ __global__ __launch_bounds__(256) void k_norm_colfin(const double *__restrict__ 
 // Rows of at most SN_WAVE_ROW scores: one wave per row, four rows per workgroup; longer rows: one workgroup per row.  Sums are
 // reduced by DPP inside the wave and in wave order through LDS.  vec: every row starts on 16 bytes (base aligned, even ld);
 // a row that does not is read with 8-byte loads in the same order.
-#define SN_WAVE_ROW 4096
-typedef double sn_v2 __attribute__((ext_vector_type(2)));
 
 template <bool WG>
 __global__ __launch_bounds__(256) void k_norm_rowsum(const double *__restrict__ x, long rows, long L, long ld,

@@ -1613,6 +1613,117 @@ int liagpu_compute_norm_files(int device, const char *normType, int meanMode, do
     })
 }
 
+// ComputeNorm on score lists (liagpu::computeNormLists).  normType as liagpu_compute_norm.  x [n] is normalised in place; line_model /
+// line_seg [n]; per list (z, t, zt): ndist, off (HOST, ndist + 1), scores, nscores, pos (nullable), other (nullable), an unused list
+// has ndist 0.  Every array but the offsets may be a host or a device pointer.  Returns when the results are complete.
+int liagpu_compute_norm_lists(int device, int normType, int meanMode, double percentH, double percentL, long n, double *x,
+                              const int32_t *line_model, const int32_t *line_seg, const long *ndist, const int64_t *const *off,
+                              const double *const *scores, const long *nscores, const int64_t *const *pos, const int32_t *const *other,
+                              double *first_out)
+{
+    GUARD({
+        static const char *names[] = {"znorm", "tnorm", "ztnorm", "tznorm"};
+        ComputeNormCfg cfg;
+        cfg.normType = normType >= 0 && normType <= 3 ? names[normType] : "?";
+        cfg.meanMode = meanMode; cfg.percentH = percentH; cfg.percentL = percentL;
+        ScoreListView v[3];
+        for (int i = 0; i < 3; ++i) {
+            v[i].ndist = (unsigned long)ndist[i]; v[i].off = off[i]; v[i].scores = scores[i]; v[i].nscores = (unsigned long)nscores[i];
+            v[i].pos = pos[i]; v[i].other = other[i];
+        }
+        GpuServer srv(device);
+        computeNormLists(srv, cfg, (unsigned long)n, x, line_model, line_seg, v[0], v[1], v[2], first_out);
+        srv.sync();
+    })
+}
+
+namespace {
+ComputeNormFilesCfg normFilesCfg(const char *normType, int meanMode, double percentH, double percentL, const char *testNistFile,
+                                 const char *znormNistFile, const char *tnormNistFile, const char *ztnormNistFile, const char *impostorIDList,
+                                 const char *outputFileBaseName, const int *fields)
+{
+    ComputeNormFilesCfg cfg;
+    cfg.norm.normType = normType; cfg.norm.meanMode = meanMode; cfg.norm.percentH = percentH; cfg.norm.percentL = percentL;
+    cfg.testNistFile = testNistFile; cfg.znormNistFile = znormNistFile ? znormNistFile : "";
+    cfg.tnormNistFile = tnormNistFile ? tnormNistFile : ""; cfg.ztnormNistFile = ztnormNistFile ? ztnormNistFile : "";
+    cfg.impostorIDList = impostorIDList ? impostorIDList : ""; cfg.outputFileBaseName = outputFileBaseName ? outputFileBaseName : "";
+    if (fields) { cfg.fields.fieldGender = fields[0]; cfg.fields.fieldName = fields[1]; cfg.fields.fieldDecision = fields[2];
+                  cfg.fields.fieldSeg = fields[3]; cfg.fields.fieldLLR = fields[4]; }
+    return cfg;
+}
+} // namespace
+
+// ComputeNorm on files, as lists (liagpu::computeNormListFiles): the arguments of liagpu_compute_norm_files, no cross product asked
+// for.  The lists are read and checked BEFORE a device is opened: a test line without a distribution fails without one.
+int liagpu_compute_norm_list_files(int device, const char *normType, int meanMode, double percentH, double percentL, const char *testNistFile,
+                                   const char *znormNistFile, const char *tnormNistFile, const char *ztnormNistFile, const char *impostorIDList,
+                                   const char *outputFileBaseName, const int *fields)
+{
+    GUARD({
+        const ComputeNormFilesCfg cfg = normFilesCfg(normType, meanMode, percentH, percentL, testNistFile, znormNistFile, tnormNistFile,
+                                                     ztnormNistFile, impostorIDList, outputFileBaseName, fields);
+        ComputeNormLists t = loadComputeNormLists(cfg);
+        GpuServer srv(device);
+        computeNormListFiles(srv, cfg, t);
+    })
+}
+
+// liagpu::loadComputeNormLists for callers and tests (host only): *out is a handle to the loaded lists; _sizes fills
+// { test lines, then per list z, t, zt: distributions, slots, 1 if `other` is present, bytes of the keys joined by '\n' };
+// _get copies list `which` (0 z, 1 t, 2 zt) and _lines the test list (each pointer may be NULL); _free releases the handle.
+int liagpu_norm_lists_load(const char *normType, const char *testNistFile, const char *znormNistFile, const char *tnormNistFile,
+                           const char *ztnormNistFile, const char *impostorIDList, const int *fields, void **out)
+{
+    GUARD({
+        const ComputeNormFilesCfg cfg = normFilesCfg(normType, 0, 0.0, 0.0, testNistFile, znormNistFile, tnormNistFile, ztnormNistFile,
+                                                     impostorIDList, nullptr, fields);
+        *out = new ComputeNormLists(loadComputeNormLists(cfg));
+    })
+}
+static const ScoreList &normListOf(const ComputeNormLists *t, int which)
+{
+    if (which < 0 || which > 2) throw Exception("norm_lists: list 0 (z), 1 (t) or 2 (zt)");
+    return which == 0 ? t->z : (which == 1 ? t->t : t->zt);
+}
+static std::string joinedKeys(const ScoreList &l)
+{
+    std::string k;
+    for (size_t i = 0; i < l.keys.size(); ++i) { k += l.keys[i]; k += '\n'; }
+    return k;
+}
+int liagpu_norm_lists_sizes(const void *h, long *sz)
+{
+    GUARD({
+        const ComputeNormLists *t = (const ComputeNormLists *)h;
+        sz[0] = (long)t->test.size();
+        for (int w = 0; w < 3; ++w) {
+            const ScoreList &l = normListOf(t, w);
+            sz[1 + 4 * w] = (long)l.keys.size(); sz[2 + 4 * w] = (long)l.scores.size(); sz[3 + 4 * w] = l.other.empty() ? 0 : 1;
+            sz[4 + 4 * w] = (long)joinedKeys(l).size();
+        }
+    })
+}
+int liagpu_norm_lists_get(const void *h, int which, int64_t *off, double *scores, int32_t *other, char *keys)
+{
+    GUARD({
+        const ScoreList &l = normListOf((const ComputeNormLists *)h, which);
+        if (off) memcpy(off, l.off.data(), l.off.size() * sizeof(int64_t));
+        if (scores) memcpy(scores, l.scores.data(), l.scores.size() * sizeof(double));
+        if (other) memcpy(other, l.other.data(), l.other.size() * sizeof(int32_t));
+        if (keys) { const std::string k = joinedKeys(l); memcpy(keys, k.data(), k.size()); }
+    })
+}
+int liagpu_norm_lists_lines(const void *h, double *x, int32_t *line_model, int32_t *line_seg)
+{
+    GUARD({
+        const ComputeNormLists *t = (const ComputeNormLists *)h;
+        if (x) memcpy(x, t->x.data(), t->x.size() * sizeof(double));
+        if (line_model) memcpy(line_model, t->lineModel.data(), t->lineModel.size() * sizeof(int32_t));
+        if (line_seg) memcpy(line_seg, t->lineSeg.data(), t->lineSeg.size() * sizeof(int32_t));
+    })
+}
+void liagpu_norm_lists_free(void *h) { delete (ComputeNormLists *)h; }
+
 // resultLine / parseResultLine round trip for the tests: writes the line into `line` (cap bytes) and parses `parse_in` (or the
 // line just written when NULL) with the given field positions into name / seg / gender (each cap bytes), decision and llr.
 int liagpu_result_line(double llr, const char *client, const char *test, const char *gender, double threshold, int withTimes, double start,

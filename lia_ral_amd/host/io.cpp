@@ -489,6 +489,130 @@ void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg)
     computeNormFiles(srv, cfg, t);
 }
 
+// ---- ComputeNorm on files, as lists -------------------------------------------------------------------------------------------
+namespace {
+// getAllScores (:446-462) / getAllScoresFirstNormed (:466-489): key = fieldOne, the filter and the first-stage lookup use fieldTwo
+ScoreList buildScoreList(const std::vector<ResultLine> &lines, const std::string &path, bool keyIsSeg, const std::map<std::string, int> *ids,
+                         const ScoreList *first)
+{
+    ScoreList l;
+    std::map<std::string, unsigned long> ki, fi;
+    if (first)
+        for (size_t i = 0; i < first->keys.size(); ++i) fi[first->keys[i]] = i;
+    std::vector<unsigned long> key(lines.size());
+    std::vector<char> in(lines.size(), 0);
+    std::vector<int64_t> cnt;
+    for (size_t i = 0; i < lines.size(); ++i) {
+        const std::string &one = keyIsSeg ? lines[i].seg : lines[i].name, &two = keyIsSeg ? lines[i].name : lines[i].seg;
+        if (ids && !ids->count(two)) continue; // selectImp, :436-445
+        if (first && !fi.count(two)) throw Exception("[" + path + "]: distribution for [" + two + "] not found (line of [" + one + "])"); // :483
+        auto it = ki.find(one);
+        if (it == ki.end()) { it = ki.insert(std::make_pair(one, (unsigned long)l.keys.size())).first; l.keys.push_back(one); cnt.push_back(0); }
+        key[i] = it->second;
+        in[i] = 1;
+        cnt[it->second]++;
+    }
+    l.off.assign(l.keys.size() + 1, 0);
+    for (size_t d = 0; d < l.keys.size(); ++d) l.off[d + 1] = l.off[d] + cnt[d];
+    l.scores.resize((size_t)l.off.back());
+    if (first) l.other.resize((size_t)l.off.back());
+    std::vector<int64_t> at(l.off.begin(), l.off.end() - 1);
+    for (size_t i = 0; i < lines.size(); ++i) { // file order inside a distribution
+        if (!in[i]) continue;
+        const int64_t k = at[key[i]]++;
+        l.scores[(size_t)k] = lines[i].llr;
+        if (first) l.other[(size_t)k] = (int32_t)fi[keyIsSeg ? lines[i].name : lines[i].seg];
+    }
+    return l;
+}
+} // namespace
+
+ComputeNormLists loadComputeNormLists(const ComputeNormFilesCfg &cfg)
+{
+    ComputeNormLists t;
+    t.norm = cfg.norm;
+    t.norm.impModels.clear(); // the selection is applied here, line by line
+    t.norm.impSegs.clear();
+    const std::string &nt = cfg.norm.normType;
+    const bool zn = nt == "znorm", tn = nt == "tnorm", ztn = nt == "ztnorm", tzn = nt == "tznorm";
+    if (!zn && !tn && !ztn && !tzn) throw Exception("unknown normalization mode:" + nt);
+    std::map<std::string, int> idsMap;
+    const std::map<std::string, int> *ids = nullptr;
+    if (!cfg.impostorIDList.empty()) { // selectMode 1 (:511-514)
+        std::ifstream in(cfg.impostorIDList.c_str());
+        if (!in) throw Exception("cannot read [" + cfg.impostorIDList + "]");
+        for (std::string w; in >> w;) idsMap[w] = 1;
+        ids = &idsMap;
+    }
+    t.test = readResultFile(cfg.testNistFile, cfg.fields);
+    auto lines = [&](const std::string &path) { return readResultFile(path, cfg.fields); };
+    if (zn) t.z = buildScoreList(lines(cfg.znormNistFile), cfg.znormNistFile, false, ids, nullptr);                 // :573
+    else if (tn) t.t = buildScoreList(lines(cfg.tnormNistFile), cfg.tnormNistFile, true, ids, nullptr);             // :537
+    else if (ztn) {
+        t.zt = buildScoreList(lines(cfg.ztnormNistFile), cfg.ztnormNistFile, true, ids, nullptr);                    // :618
+        t.t = buildScoreList(lines(cfg.tnormNistFile), cfg.tnormNistFile, true, ids, nullptr);                       // :623
+        t.z = buildScoreList(lines(cfg.znormNistFile), cfg.znormNistFile, false, ids, &t.zt);                        // :629
+    } else {
+        t.z = buildScoreList(lines(cfg.znormNistFile), cfg.znormNistFile, false, ids, nullptr);                      // :690
+        t.zt = buildScoreList(lines(cfg.ztnormNistFile), cfg.ztnormNistFile, false, ids, nullptr);                   // :697
+        t.t = buildScoreList(lines(cfg.tnormNistFile), cfg.tnormNistFile, true, ids, &t.zt);                         // :704
+    }
+    std::map<std::string, int32_t> zi, ti;
+    for (size_t i = 0; i < t.z.keys.size(); ++i) zi[t.z.keys[i]] = (int32_t)i;
+    for (size_t i = 0; i < t.t.keys.size(); ++i) ti[t.t.keys[i]] = (int32_t)i;
+    t.x.resize(t.test.size());
+    if (!tn) t.lineModel.resize(t.test.size());
+    if (!zn) t.lineSeg.resize(t.test.size());
+    for (size_t l = 0; l < t.test.size(); ++l) { // the two lookups of every test line (:547, :582, :642-650, :725-732)
+        t.x[l] = t.test[l].llr;
+        if (!tn) {
+            auto it = zi.find(t.test[l].name);
+            if (it == zi.end()) throw Exception("[" + cfg.testNistFile + "]: znorm distribution not found for id [" + t.test[l].name + "]");
+            t.lineModel[l] = it->second;
+        }
+        if (!zn) {
+            auto it = ti.find(t.test[l].seg);
+            if (it == ti.end()) throw Exception("[" + cfg.testNistFile + "]: tnorm distribution not found for seg [" + t.test[l].seg + "]");
+            t.lineSeg[l] = it->second;
+        }
+    }
+    return t;
+}
+
+void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormLists &t)
+{
+    const std::string &nt = t.norm.normType;
+    const bool two = nt == "ztnorm" || nt == "tznorm";
+    std::vector<double> first(two ? t.x.size() : 0);
+    auto view = [](const ScoreList &l) {
+        ScoreListView v;
+        v.ndist = l.keys.size(); v.off = l.off.empty() ? nullptr : l.off.data(); v.scores = l.scores.data(); v.nscores = l.scores.size();
+        v.other = l.other.empty() ? nullptr : l.other.data();
+        return v;
+    };
+    computeNormLists(srv, t.norm, t.x.size(), t.x.data(), t.lineModel.empty() ? nullptr : t.lineModel.data(),
+                     t.lineSeg.empty() ? nullptr : t.lineSeg.data(), view(t.z), view(t.t), view(t.zt), two ? first.data() : nullptr);
+    srv.sync();
+    auto write = [&](const std::string &ext, const std::vector<double> &v) {
+        const std::string path = cfg.outputFileBaseName + ext;
+        std::ofstream out(path.c_str(), std::ios::out | std::ios::trunc);
+        if (!out) throw Exception("cannot write [" + path + "]");
+        out.precision(17);
+        for (size_t l = 0; l < t.test.size(); ++l) // test-list order; the line of computeNormFiles: decision 0 like the reference (:497), 17 digits
+            out << t.test[l].gender << " " << t.test[l].name << " 0 " << t.test[l].seg << " " << v[l] << "\n";
+    };
+    if (nt == "znorm") write(cfg.znormFilesExtension, t.x);
+    else if (nt == "tnorm") write(cfg.tnormFilesExtension, t.x);
+    else if (nt == "ztnorm") { write(cfg.ztnormFilesExtension, t.x); write(cfg.tnormFilesExtension, first); }   // :656-657
+    else { write(cfg.tznormFilesExtension, t.x); write(cfg.znormFilesExtension, first); }                        // :738-739
+}
+
+void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg)
+{
+    ComputeNormLists t = loadComputeNormLists(cfg);
+    computeNormListFiles(srv, cfg, t);
+}
+
 // ---- NormFeat from files ------------------------------------------------------------------------------
 void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const NormFeatFilesCfg &cfg)
 {

@@ -100,6 +100,30 @@ ComputeNormTables loadComputeNormTables(const ComputeNormFilesCfg &cfg);        
 void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormTables &tables); // normalise + write the output files
 void computeNormFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg);
 
+// ComputeNorm driven by files, on LISTS: no cross product is asked for.  The four NIST files become CSR lists with the reference's
+// semantics (getAllScores / getAllScoresFirstNormed, ComputeNorm.cpp:446-489): a distribution per value of the key field, its scores
+// in FILE ORDER (the unsorted "median" of meanMode 1 without discards is the score at position n / 2 of that order), a line enters
+// only if its OTHER field passes impostorIDList when one is given, a (model, segment) pair listed twice is two scores, names are
+// indexed in order of first appearance.  A test line whose model or segment has no distribution, and a selected cohort line whose
+// other field has no first-stage distribution, is an Exception that names it (the reference prints "... not found ..." and exits).
+struct ScoreList {
+    std::vector<std::string> keys;       // one per distribution
+    std::vector<int64_t> off;            // keys.size() + 1
+    std::vector<double> scores;          // by slot
+    std::vector<int32_t> other;          // by slot: the first-stage distribution of the line's other field (second-stage list only)
+};
+struct ComputeNormLists {
+    std::vector<ResultLine> test;        // the test list, line by line (output order)
+    std::vector<double> x;               // its scores
+    std::vector<int32_t> lineModel, lineSeg; // distribution of z / of t of each test line (empty when the normType does not use it)
+    ScoreList z, t, zt;                  // znormNistFile by model; tnormNistFile by test segment; ztnormNistFile by impostor segment
+                                         // ("ztnorm") or by cohort model ("tznorm")
+    ComputeNormCfg norm;
+};
+ComputeNormLists loadComputeNormLists(const ComputeNormFilesCfg &cfg);                      // host only
+void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormLists &lists); // normalise + write the output files
+void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg);
+
 
 // NormFeat driven by files (NormFeat.cpp:302-509): every feature file <featureFilesPath><name><loadFeatureFileExtension> of the list is
 // loaded at its full width into ONE resident buffer (the files must share their dimension), the clusters come from

@@ -2935,4 +2935,48 @@ void computeNorm(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long M, uns
     srv.check(gmmiv_score_normalize(c, (int64_t)M, (int64_t)S, X, order, muZ, sdZ, muT, sdT, (zt || tz) ? firstOut : nullptr)); // :552, :587, :647-654, :730-736
 }
 
+void computeNormLists(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long n, double *x, const int32_t *lineModel, const int32_t *lineSeg,
+                      const ScoreListView &z, const ScoreListView &t, const ScoreListView &zt, double *firstOut)
+{
+    const bool zn = cfg.normType == "znorm", tn = cfg.normType == "tnorm", ztn = cfg.normType == "ztnorm", tzn = cfg.normType == "tznorm";
+    if (!zn && !tn && !ztn && !tzn) throw Exception("unknown normalization mode:" + cfg.normType); // :752-755
+    if (n == 0) return;
+    if (!x) throw Exception("computeNormLists: no test scores");
+    if (!tn && (z.ndist == 0 || !z.off || !lineModel)) throw Exception("computeNormLists: " + cfg.normType + " needs the znorm list (znormNistFile) and lineModel");
+    if (!zn && (t.ndist == 0 || !t.off || !lineSeg)) throw Exception("computeNormLists: " + cfg.normType + " needs the tnorm list (tnormNistFile) and lineSeg");
+    if ((ztn || tzn) && (zt.ndist == 0 || !zt.off)) throw Exception("computeNormLists: " + cfg.normType + " needs the ztnorm list (ztnormNistFile)");
+    if (ztn && !z.other) throw Exception("computeNormLists: ztnorm needs, per slot of the znorm list, the impostor segment's distribution (other)");
+    if (tzn && !t.other) throw Exception("computeNormLists: tznorm needs, per slot of the tnorm list, the cohort model's distribution (other)");
+    gmmiv_ctx *c = srv.ctx();
+    // the parameter vectors stay on the device: [mu_z, sd_z](z.ndist) [mu_t, sd_t](t.ndist) [mu_first, sd_first](zt.ndist)
+    const size_t nz = tn ? 0 : z.ndist, nt = zn ? 0 : t.ndist, nf = (ztn || tzn) ? zt.ndist : 0;
+    double *v = (double *)srv.workspace(7, (2 * nz + 2 * nt + 2 * nf + 1) * sizeof(double));
+    double *muZ = v, *sdZ = v + nz, *muT = sdZ + nz, *sdT = muT + nt, *muF = sdT + nt, *sdF = muF + nf;
+    auto stats = [&](const ScoreListView &l, bool pre, double *mu, double *sd) {
+        srv.check(gmmiv_score_list_stats(c, (int64_t)l.ndist, l.off, l.pos, l.scores, (int64_t)l.nscores, pre ? l.other : nullptr,
+                                         pre ? muF : nullptr, pre ? sdF : nullptr, pre ? (int64_t)nf : 0, cfg.meanMode, cfg.percentH,
+                                         cfg.percentL, mu, sd));
+    };
+    int order;
+    if (zn) { // :573
+        stats(z, false, muZ, sdZ);
+        order = GMMIV_NORM_Z;
+    } else if (tn) { // :537
+        stats(t, false, muT, sdT);
+        order = GMMIV_NORM_T;
+    } else if (ztn) {
+        stats(zt, false, muF, sdF); // :618 t-norm parameters of the impostor segments
+        stats(t, false, muT, sdT);  // :623 t-norm parameters of the test segments
+        stats(z, true, muZ, sdZ);   // :629 z-norm parameters of the t-normed impostor scores
+        order = GMMIV_NORM_ZT;
+    } else {
+        stats(z, false, muZ, sdZ);  // :690 z-norm parameters of the models
+        stats(zt, false, muF, sdF); // :697 z-norm parameters of the cohort models
+        stats(t, true, muT, sdT);   // :704 t-norm parameters of the z-normed cohort scores
+        order = GMMIV_NORM_TZ;
+    }
+    srv.check(gmmiv_score_normalize_list(c, (int64_t)n, x, order, tn ? nullptr : lineModel, muZ, sdZ, (int64_t)nz, zn ? nullptr : lineSeg, muT, sdT,
+                                         (int64_t)nt, (ztn || tzn) ? firstOut : nullptr)); // :552, :587, :647-654, :730-736
+}
+
 } // namespace liagpu

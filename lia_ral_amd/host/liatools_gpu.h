@@ -798,6 +798,28 @@ struct ComputeNormCfg {
 void computeNorm(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long M, unsigned long S, unsigned long Nt, unsigned long Nz,
                  double *X, const double *Z, const double *T, const double *ZT, double *firstOut = nullptr);
 
+// ---- ComputeNorm on score LISTS: sparse trial lists and per-entity cohorts of different lengths -----------------------------------
+// What the reference does by name (one DistribNorm per name, ComputeNorm.cpp:104-118, filled line by line, :446-489; two lookups per
+// test line, :542-554, :576-589, :634-658, :717-742), by index: a list holds one distribution per value of its key field as a CSR
+// table over a score array (include/gmmiv.h, "score normalisation on lists").  The impostorIDList selection is applied when a list
+// is BUILT (loadComputeNormLists, io.h): cfg.impModels / cfg.impSegs are not looked at here.
+//   z  znormNistFile:  a distribution per MODEL (its impostor-segment scores)       lineModel[i] names the one of test line i
+//   t  tnormNistFile:  a distribution per TEST SEGMENT (its cohort-model scores)     lineSeg[i] names the one of test line i
+//   zt ztnormNistFile: per IMPOSTOR SEGMENT for "ztnorm" (:618), per COHORT MODEL for "tznorm" (:697): the first-stage statistics
+// `other` (by slot) names the zt distribution of the slot's second field; "ztnorm" needs it on z (:629), "tznorm" on t (:704).
+struct ScoreListView {
+    unsigned long ndist = 0;
+    const int64_t *off = nullptr;    // HOST, ndist + 1
+    const double *scores = nullptr;  // host or device
+    unsigned long nscores = 0;
+    const int64_t *pos = nullptr;    // host or device, by slot; NULL: slot k holds scores[k]
+    const int32_t *other = nullptr;  // host or device, by slot
+};
+// x [n]: the scores of the test lines, normalised IN PLACE (host or device); firstOut: NULL, or [n] -- the t-normed scores of "ztnorm",
+// the z-normed scores of "tznorm".  lineModel / lineSeg: host or device; the one a normType does not use may be NULL.
+void computeNormLists(GpuServer &srv, const ComputeNormCfg &cfg, unsigned long n, double *x, const int32_t *lineModel, const int32_t *lineSeg,
+                      const ScoreListView &z, const ScoreListView &t, const ScoreListView &zt, double *firstOut = nullptr);
+
 // TVAcc::computeEigenProblem (AccumulateTVStat.cpp:2997-3102) for the SYMMETRIC matrices it is used on (the weighted
 // covariance W): cyclic Jacobi on the host, eigenvalues sorted descending, eigenVect[k*rank + j] = component k of
 // the j-th eigenvector (the reference's Eigen / LAPACK solver returns its own column order and sign; any orthonormal

@@ -838,6 +838,88 @@ def compute_norm_files(test_nist_file, output_base, norm_type="znorm", znorm_nis
                                        e(output_base), fl))
 
 
+def _ip(a):
+    """void* of an index array: numpy (made contiguous by the caller) or a torch tensor, None -> NULL"""
+    if a is None:
+        return ct.c_void_p(0)
+    if type(a).__module__.startswith("torch"):
+        assert a.is_contiguous()
+        return ct.c_void_p(a.data_ptr())
+    assert a.flags["C_CONTIGUOUS"]
+    return ct.c_void_p(a.ctypes.data)
+
+
+def _idx(a, dtype):
+    if a is None or type(a).__module__.startswith("torch"):
+        return a
+    return np.ascontiguousarray(a, dtype)
+
+
+def compute_norm_lists(x, line_model=None, line_seg=None, z=None, t=None, zt=None, norm_type="znorm", mean_mode=0, percent_h=0.0,
+                       percent_l=0.0, first_out=None, device=0):
+    """liagpu::computeNormLists: x [n] (numpy float64 or a torch CUDA tensor) is normalised IN PLACE.  line_model / line_seg [n]
+    (int32) name the z / t distribution of every test line.  z, t, zt: None or a dict with "off" (host int64, ndist + 1), "scores"
+    (float64), and optionally "pos" (int64, by slot) and "other" (int32, by slot: the zt distribution of the slot's second field, on z
+    for ztnorm and on t for tznorm).  zt holds a distribution per impostor segment for ztnorm, per cohort model for tznorm.
+    first_out: None, or [n] for the t-normed (ztnorm) / z-normed (tznorm) scores.  -> x"""
+    keep = []
+    nd = (ct.c_long * 3)(); ns = (ct.c_long * 3)()
+    po = (ct.c_void_p * 3)(); ps = (ct.c_void_p * 3)(); pp = (ct.c_void_p * 3)(); pt = (ct.c_void_p * 3)()
+    for i, l in enumerate((z, t, zt)):
+        if l is None:
+            continue
+        off = np.ascontiguousarray(l["off"], np.int64)
+        sc = l["scores"] if type(l["scores"]).__module__.startswith("torch") else np.ascontiguousarray(l["scores"], np.float64)
+        pos, oth = _idx(l.get("pos"), np.int64), _idx(l.get("other"), np.int32)
+        keep += [off, sc, pos, oth]
+        nd[i] = len(off) - 1; ns[i] = int(sc.shape[0])
+        po[i] = _ip(off).value; ps[i] = _vp(sc).value; pp[i] = _ip(pos).value; pt[i] = _ip(oth).value
+    lm, ls = _idx(line_model, np.int32), _idx(line_seg, np.int32)
+    _chk(lib.liagpu_compute_norm_lists(device, NORM_TYPES.get(norm_type, -1), int(mean_mode), ct.c_double(percent_h), ct.c_double(percent_l),
+                                       ct.c_long(int(x.shape[0])), _vp(x), _ip(lm), _ip(ls), nd, po, ps, ns, pp, pt, _vp(first_out)))
+    return x
+
+
+def compute_norm_list_files(test_nist_file, output_base, norm_type="znorm", znorm_nist_file=None, tnorm_nist_file=None,
+                            ztnorm_nist_file=None, impostor_id_list=None, mean_mode=0, percent_h=0.0, percent_l=0.0, fields=None, device=0):
+    """liagpu::computeNormListFiles: compute_norm_files without its demand for full cross products -- sparse test lists, ragged
+    cohorts, repeated pairs, as the reference's per-name DistribNorm takes them.  Writes the same files."""
+    e = lambda p: None if p is None else str(p).encode()
+    fl = None if fields is None else (ct.c_int * 5)(*[int(v) for v in fields])
+    _chk(lib.liagpu_compute_norm_list_files(device, norm_type.encode(), int(mean_mode), ct.c_double(percent_h), ct.c_double(percent_l),
+                                            e(test_nist_file), e(znorm_nist_file), e(tnorm_nist_file), e(ztnorm_nist_file),
+                                            e(impostor_id_list), e(output_base), fl))
+
+
+def load_compute_norm_lists(test_nist_file, norm_type="znorm", znorm_nist_file=None, tnorm_nist_file=None, ztnorm_nist_file=None,
+                            impostor_id_list=None, fields=None):
+    """liagpu::loadComputeNormLists (host only, opens no device) -> dict: "x", "line_model", "line_seg" (None where the normType does not
+    use it) and per list "z" / "t" / "zt" a dict keys / off / scores / other (None without a first stage), ready for compute_norm_lists"""
+    e = lambda p: None if p is None else str(p).encode()
+    fl = None if fields is None else (ct.c_int * 5)(*[int(v) for v in fields])
+    h = ct.c_void_p(0)
+    _chk(lib.liagpu_norm_lists_load(norm_type.encode(), e(test_nist_file), e(znorm_nist_file), e(tnorm_nist_file), e(ztnorm_nist_file),
+                                    e(impostor_id_list), fl, ct.byref(h)))
+    try:
+        sz = (ct.c_long * 13)()
+        _chk(lib.liagpu_norm_lists_sizes(h, sz))
+        out = {}
+        for w, name in enumerate(("z", "t", "zt")):
+            nd, nslot, has_other, nkey = [int(v) for v in sz[1 + 4 * w:5 + 4 * w]]
+            off = np.zeros(nd + 1, np.int64); sc = np.zeros(nslot); oth = np.zeros(nslot, np.int32) if has_other else None
+            keys = ct.create_string_buffer(max(nkey, 1))
+            _chk(lib.liagpu_norm_lists_get(h, w, _ip(off) if nd else None, _ip(sc), _ip(oth), keys))
+            out[name] = dict(keys=keys.raw[:nkey].decode().split("\n")[:-1], off=off, scores=sc, other=oth)
+        n = int(sz[0])
+        x = np.zeros(n); lm = np.zeros(n, np.int32); ls = np.zeros(n, np.int32)
+        use_m, use_s = norm_type != "tnorm", norm_type != "znorm"
+        _chk(lib.liagpu_norm_lists_lines(h, _ip(x), _ip(lm) if use_m else None, _ip(ls) if use_s else None))
+        out.update(x=x, line_model=lm if use_m else None, line_seg=ls if use_s else None)
+        return out
+    finally:
+        lib.liagpu_norm_lists_free(h)
+
+
 def result_line(llr, client, test, gender="M", threshold=0.0, times=None, parse=None, fields=None):
     """-> (the line liagpu::resultLine writes, its fields as liagpu::parseResultLine reads them back: dict).  parse: another
     line to read instead; fields: the five field positions."""
