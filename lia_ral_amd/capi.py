@@ -3,6 +3,7 @@
 import ctypes as ct
 import os
 import sys
+import weakref
 
 import numpy as np
 
@@ -126,6 +127,7 @@ class Context:
     def __init__(self, device=0, stream=None):
         self._h = ct.c_void_p()
         self.device = int(device)
+        self._models = weakref.WeakSet()   # Gmm / GmmBatch handles of this context: destroyed with it, at the latest
         if stream is not None and int(stream) == 0:
             stream = STREAM_DEFAULT
         _chk(lib.gmmiv_ctx_create(ct.c_int(device), ct.c_void_p(stream or 0), ct.byref(self._h)))
@@ -162,6 +164,10 @@ class Context:
 
     def close(self):
         if self._h:
+            # a model handle holds a pointer to its context: one that outlives it (kept alive by a traceback, say) must not be
+            # destroyed afterwards -- gmmiv_gmm_destroy would read the freed context
+            for m in list(self._models):
+                m.close()
             lib.gmmiv_ctx_destroy(self._h)
             self._h = ct.c_void_p()
 
@@ -849,6 +855,7 @@ class Gmm:
         self.C, self.D = mean.shape
         self._h = ct.c_void_p()
         _chk(lib.gmmiv_gmm_create(ctx._h, self.C, self.D, _ptr(w), _ptr(mean), _ptr(covinv), ct.byref(self._h)))
+        ctx._models.add(self)
 
     def set(self, w, mean, covinv):
         _chk(lib.gmmiv_gmm_set(self._h, _ptr(_f64(w)), _ptr(_f64(mean)), _ptr(_f64(covinv))))
@@ -1062,6 +1069,7 @@ class GmmBatch:
         self.ctx, self.G, self.C, self.D = ctx, int(G), int(C), int(D)
         self._h = ct.c_void_p()
         _chk(lib.gmmiv_gmm_batch_create(ctx._h, self.G, self.C, self.D, ct.byref(self._h)))
+        ctx._models.add(self)
 
     def close(self):
         if self._h:
