@@ -524,13 +524,63 @@ int64_t gmmiv_plan_trial_tiles(const int64_t *seg_begin, int64_t nseg, const int
  *   GMMIV_MAP_CONST2       mean = (mean_alpha w0 mean0 + (1 - mean_alpha) w mean_ml) / (w0 mean_alpha + w (1 - mean_alpha))
  *   GMMIV_MAP_NONE         the ML estimate itself (an unknown mapAlgo: "No adaptation will be perform")
  * mean_adapt = 0 gives mean0; without weight_adapt (and for the two constant methods) the weights are w0.  Variances are not touched
- * (varAdapt needs second-order statistics per segment: not batched).  mean_out [G x C*D], w_out [G x C] (nullable): device or
- * host; device outputs can be handed straight to gmmiv_gmm_batch_load.  Every operation is rounded on its own (no contraction). */
+ * here: varAdapt is gmmiv_map_adapt_models_full below, on the second-order rows of gmmiv_em_stats_models.  mean_out [G x C*D],
+ * w_out [G x C] (nullable): device or host; device outputs can be handed straight to gmmiv_gmm_batch_load.  Every operation is rounded
+ * on its own (no contraction). */
 enum { GMMIV_MAP_NONE = 0, GMMIV_MAP_OCC_DEP = 1, GMMIV_MAP_MODEL_BASED = 2, GMMIV_MAP_CONST = 3, GMMIV_MAP_CONST2 = 4 };
 int gmmiv_map_adapt_models(gmmiv_ctx *ctx, int G, int C, int D, const double *N, const double *F, const double *count,
                            int64_t count_stride, const double *w0, const double *mean0, const double *cur_mean, int64_t cur_stride,
                            int method, int mean_adapt, int weight_adapt, double mean_reg, double weight_reg, double mean_alpha,
                            double *mean_out, double *w_out);
+
+/* ---- batched enrolment WITH VARIANCES: second-order statistics per segment, the variance branch of computeMAP, normalizeMixture ------
+ * gmmiv_em_stats_models: the contract of gmmiv_tv_stats_models (host segment tables, an empty segment gives zeros, frames outside the
+ * segments are not read, zero-likelihood / NaN frames left out and counted once, rows OVERWRITTEN, seg_llk nullable, host or device
+ * outputs; with device pointers the call only enqueues beyond what gmmiv_tv_stats_models waits for) plus
+ *   S [nseg x C*D],  S[s*C*D + c*D + i] = sum_t g_tc x_ti^2.
+ * vectSize <= 60: the per-model tiles of the batched log-likelihood kernel, then the stored-likelihood statistics kernel in its EM shape
+ * (x^2 staged in LDS) with one segment per workgroup row and a row epilogue that writes N, F and S directly: every (segment, Gaussian)
+ * row is written by one wave in the fixed order of its own segment's 16-frame blocks.  No floating-point atomics; a row depends only on
+ * its own segment's frames (at their position modulo 16 in x) and model -- not on the other segments, their order, the chunking or the
+ * scratch options: the same bits when the segment is the only one of the call.  Other shapes (vectSize 61-80, > 80, a segment longer than
+ * the likelihood scratch) walk the segments through the single-model second-order kernels (the recomputing statistics kernel with x^2,
+ * the generic gamma^T [x | 1 | x^2] GEMM): the same definition, launch-bound.  "prune_log2", "z_waves" and "z_depth_em" apply as in
+ * gmmiv_em_accumulate.  Kernel timers: "k_llk_mfma", "k_stats_z", "k_gmm_pack" ("k_stats_mfma", "k_posteriors" on the walk).
+ *
+ * gmmiv_map_adapt_models_full: computeMAP for G models with all three branches.  N, F, count, w0, mean0, cur_mean, method, mean_adapt,
+ * weight_adapt, the regulation factors and mean_alpha are those of gmmiv_map_adapt_models, and mean_out / w_out are ITS BITS (the same
+ * device function) whatever var_adapt says.  The variance: the ML estimate cov_ml = S / N - mean_ml^2 as gmmiv_em_get (a Gaussian with
+ * N = 0 keeps cur_cov, model g at cur_cov + g * cur_cov_stride, stride 0 = shared, like its mean); then
+ *   GMMIV_MAP_OCC_DEP / GMMIV_MAP_MODEL_BASED with var_adapt   alpha = w_c n and n as for the mean, aV = alpha / (alpha + var_reg),
+ *                          cov = (1 - aV) cov0 + aV cov_ml + ((1 - aV) aV) (mean0 - mean_ml)^2      (TrainTools.cpp:468-475, :518-525)
+ *   ... without var_adapt, GMMIV_MAP_CONST, GMMIV_MAP_CONST2    cov0 (the reference has a TODO for the constant methods)
+ *   GMMIV_MAP_NONE         cov_ml
+ * S and cur_cov may be NULL when no branch reads them (var_adapt = 0 and a method other than NONE, or cov_out = NULL).  mean_out, cov_out,
+ * w_out: each nullable, not all three.  status [G] (int32, required, where the outputs live: device or host) = the number of entries of
+ * cov_out of model g that are not positive and finite (0 without cov_out); it is written on the device and not read by the call.
+ * Every operation is rounded on its own (no contraction).
+ *
+ * gmmiv_normalize_models: normalizeMixture (TrainTools.cpp:287-315) towards N(0, 1), in place, for G models: nb_it times {mixtureFusion
+ * (:241-284): per dimension the single Gaussian with the mixture's first two moments, a LEFT FOLD over the Gaussians c = 0 .. C-1;
+ * mean = (mean - m) / sqrt(v); unless mean_only, cov = cov / v}.  One thread per (model, dimension) in the host code's order of
+ * operations.  w at w + g * w_stride (0 = shared), mean / cov [G x C*D] DEVICE arrays.  cov is read in either mode (the fusion needs the
+ * variances) and written unless mean_only.
+ *
+ * gmmiv_gmm_batch_load_cov: gmmiv_gmm_batch_load from VARIANCES, covInv = 1 / cov on the device as gmmiv_gmm_set_cov does -- the device
+ * outputs of the two calls above go back into the batch without a host round trip. */
+int gmmiv_em_stats_models(gmmiv_ctx *ctx, const gmmiv_gmm_batch *b, const void *x, int x_dtype, int64_t T, int64_t ldx,
+                          const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, double *N, double *F, double *S,
+                          double *seg_llk /* [2 nseg], nullable */);
+int gmmiv_map_adapt_models_full(gmmiv_ctx *ctx, int G, int C, int D, const double *N, const double *F, const double *S /* nullable */,
+                                const double *count, int64_t count_stride, const double *w0, const double *mean0, const double *cov0,
+                                const double *cur_mean, int64_t cur_mean_stride, const double *cur_cov /* nullable */,
+                                int64_t cur_cov_stride, int method, int mean_adapt, int var_adapt, int weight_adapt, double mean_reg,
+                                double var_reg, double weight_reg, double mean_alpha, double *mean_out, double *cov_out, double *w_out,
+                                int32_t *status);
+int gmmiv_normalize_models(gmmiv_ctx *ctx, int G, int C, int D, const double *w, int64_t w_stride, double *mean, double *cov, int nb_it,
+                           int mean_only);
+int gmmiv_gmm_batch_load_cov(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride,
+                             const double *cov, int64_t cov_stride);
 
 /* computeMLLR (TrainTools.cpp:788-866) for G clients at once, from the statistics rows of gmmiv_tv_stats_models: one global affine
  * transform of the a-priori means per client.  With xi_j = [1, mean0_j] (D + 1 values), a_j = N_gj / cov0_jp and the ML mean

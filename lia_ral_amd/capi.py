@@ -1098,6 +1098,14 @@ class GmmBatch:
                                       _ptr(covinv), ct.c_int64(self._stride(covinv, CD))))
         return self
 
+    def load_cov(self, w, mean, cov):
+        """load() from VARIANCES (gmmiv_gmm_batch_load_cov): covInv = 1 / cov on the device, as Gmm.set_cov"""
+        w, mean, cov = _f64(w), _f64(mean), _f64(cov)
+        CD = self.C * self.D
+        _chk(lib.gmmiv_gmm_batch_load_cov(self._h, _ptr(w), ct.c_int64(self._stride(w, self.C)), _ptr(mean), ct.c_int64(self._stride(mean, CD)),
+                                          _ptr(cov), ct.c_int64(self._stride(cov, CD))))
+        return self
+
     def packed(self, g):
         """the packed MFMA operands of model g as a call builds them (tests: bit for bit those of a single-model handle)"""
         n = ct.c_int64()
@@ -1137,6 +1145,18 @@ class GmmBatch:
         _chk(lib.gmmiv_tv_stats_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
                                        sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(N), _ptr(F), _ptr(seg_llk)))
         return N, F, seg_llk
+
+    def em_stats(self, x, seg_begin, seg_model, N=None, F=None, S=None, seg_llk=None):
+        """gmmiv_em_stats_models -> (N [nseg, C], F [nseg, C*D], S [nseg, C*D] = sum g x^2, seg_llk [nseg, 2])"""
+        x, dt, T, ldx = _feat(x)
+        sb, sm = self._segs(seg_begin, seg_model)
+        if N is None:
+            N = np.empty((len(sm), self.C)); F = np.empty((len(sm), self.C * self.D)); S = np.empty((len(sm), self.C * self.D))
+        if seg_llk is None:
+            seg_llk = np.empty((len(sm), 2))
+        _chk(lib.gmmiv_em_stats_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
+                                       sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(N), _ptr(F), _ptr(S), _ptr(seg_llk)))
+        return N, F, S, seg_llk
 
     def llr_trials(self, world, x, seg_begin, trial_seg, trial_model, ctop, complete=True, min_llk=-200.0, max_llk=200.0, llr=None, client_mean=None,
                    world_mean=None):
@@ -1181,6 +1201,40 @@ class GmmBatch:
                                         int(bool(weight)), ct.c_double(reg[0]), ct.c_double(reg[2]), ct.c_double(alpha_mean), _ptr(mean_out),
                                         _ptr(w_out)))
         return mean_out, w_out
+
+    def map_adapt_full(self, N, F, S, count, w0, mean0, cov0, cur_mean, cur_cov, method="MAPOccDep", mean=True, var=False, weight=False,
+                       reg=(16.0, 16.0, 16.0), alpha_mean=0.75, count_stride=1, want=("mean", "cov", "w")):
+        """computeMAP with the variance branch (gmmiv_map_adapt_models_full) -> (means [G, C*D], covs [G, C*D], weights [G, C], status [G]
+        int32); an output not named in `want` is None.  S / cur_cov may be None when no branch reads them.  Outputs live where N lives."""
+        G, C, D = self.G, self.C, self.D
+        if _is_torch(N):
+            import torch
+            mk = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=N.device)
+            status = mk((G,), torch.int32)
+        else:
+            mk = lambda shape: np.empty(shape)
+            status = np.empty(G, np.int32)
+        mo = mk((G, C * D)) if "mean" in want else None
+        co = mk((G, C * D)) if "cov" in want else None
+        wo = mk((G, C)) if "w" in want else None
+        cm = _f64(cur_mean)
+        cc = None if cur_cov is None else _f64(cur_cov)
+        opt = lambda a: ct.c_void_p(0) if a is None else _ptr(a)
+        _chk(lib.gmmiv_map_adapt_models_full(self.ctx._h, G, C, D, _ptr(_f64(N)), _ptr(_f64(F)), opt(None if S is None else _f64(S)), _ptr(_f64(count)),
+                                             ct.c_int64(count_stride), _ptr(_f64(w0)), _ptr(_f64(mean0)), _ptr(_f64(cov0)), _ptr(cm),
+                                             ct.c_int64(self._stride(cm, C * D)), opt(cc), ct.c_int64(0 if cc is None else self._stride(cc, C * D)),
+                                             MAP_METHODS.get(method, 0), int(bool(mean)), int(bool(var)), int(bool(weight)), ct.c_double(reg[0]),
+                                             ct.c_double(reg[1]), ct.c_double(reg[2]), ct.c_double(alpha_mean), opt(mo), opt(co), opt(wo), _ptr(status)))
+        return mo, co, wo, status
+
+    def normalize(self, w, mean, cov, nb_it=1, mean_only=False):
+        """normalizeMixture towards N(0, 1) for the G models IN PLACE (gmmiv_normalize_models): mean, cov [G, C*D] torch device tensors,
+        w [C] (shared) or [G, C]"""
+        assert _is_torch(mean) and _is_torch(cov)
+        w = _f64(w)
+        _chk(lib.gmmiv_normalize_models(self.ctx._h, self.G, self.C, self.D, _ptr(w), ct.c_int64(self._stride(w, self.C)), _ptr(mean), _ptr(cov),
+                                        int(nb_it), int(bool(mean_only))))
+        return mean, cov
 
     def mllr_adapt(self, N, F, mean0, cov0):
         """computeMLLR for the G statistics rows (gmmiv_mllr_adapt_models) -> (W [G, D, D + 1], means [G, C*D], status [G] int32)."""

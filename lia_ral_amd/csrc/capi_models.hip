@@ -76,25 +76,32 @@ void gmmiv_gmm_batch_destroy(gmmiv_gmm_batch *b)
     delete b;
 }
 
-// one table: G rows of `row` doubles `stride` apart (or one shared row) into a compact device copy
-static int batch_table(gmmiv_gmm_batch *b, double **dst, size_t *cap, long *dst_stride, const double *src, int64_t stride, size_t row)
+static int batch_reserve(gmmiv_gmm_batch *b, double **dst, size_t *cap, size_t need)
 {
     gmmiv_ctx *c = b->ctx;
-    const size_t rows = stride == 0 ? 1 : (size_t)b->G, need = rows * row;
     if (*cap < need) {
         if (*dst) { GCHK(hipStreamSynchronize(c->stream)); GCHK(hipFree(*dst)); *dst = nullptr; *cap = 0; }
         const hipError_t e = hipMalloc((void **)dst, need * sizeof(double));
         if (e != hipSuccess) { (void)hipGetLastError(); *dst = nullptr; gmmiv_set_error("gmm_batch_load: hipMalloc of %zu bytes -> %s", need * sizeof(double), hipGetErrorString(e)); return GMMIV_ERR_HIP; }
         *cap = need;
     }
+    return GMMIV_OK;
+}
+// one table: G rows of `row` doubles `stride` apart (or one shared row) into a compact device copy
+static int batch_table(gmmiv_gmm_batch *b, double **dst, size_t *cap, long *dst_stride, const double *src, int64_t stride, size_t row)
+{
+    gmmiv_ctx *c = b->ctx;
+    const size_t rows = stride == 0 ? 1 : (size_t)b->G, need = rows * row;
+    const int rc = batch_reserve(b, dst, cap, need);
+    if (rc) return rc;
     const hipMemcpyKind kind = gmmiv_is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     GCHK(hipMemcpy2DAsync(*dst, row * sizeof(double), src, (stride == 0 ? row : (size_t)stride) * sizeof(double), row * sizeof(double), rows, kind, c->stream));
     *dst_stride = stride == 0 ? 0 : (long)row;
     return GMMIV_OK;
 }
 
-int gmmiv_gmm_batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride, const double *covinv,
-                         int64_t covinv_stride)
+static int batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride, const double *covinv,
+                      int64_t covinv_stride, bool from_cov)
 {
     if (!b || !w || !mean || !covinv) { gmmiv_set_error("gmm_batch_load: bad argument"); return GMMIV_ERR_ARG; }
     const size_t CD = (size_t)b->C * b->D;
@@ -108,11 +115,31 @@ int gmmiv_gmm_batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, 
     b->loaded = false;
     if ((rc = batch_table(b, &b->w, &b->cap_w, &b->sw, w, w_stride, (size_t)b->C))) return rc;
     if ((rc = batch_table(b, &b->mean, &b->cap_mean, &b->sm, mean, mean_stride, CD))) return rc;
-    if ((rc = batch_table(b, &b->iv, &b->cap_iv, &b->si, covinv, covinv_stride, CD))) return rc;
+    if (from_cov) { // the variances compact into a scratch, covInv = 1 / cov from there into the batch's table (gmmiv_gmm_set_cov)
+        const size_t rows = covinv_stride == 0 ? 1 : (size_t)b->G;
+        void *tmp;
+        if ((rc = c->scratch(WS_T0, rows * CD * sizeof(double), &tmp))) return rc;
+        if ((rc = batch_reserve(b, &b->iv, &b->cap_iv, rows * CD))) return rc;
+        GCHK(hipMemcpy2DAsync(tmp, CD * sizeof(double), covinv, (covinv_stride == 0 ? CD : (size_t)covinv_stride) * sizeof(double), CD * sizeof(double), rows,
+                              gmmiv_is_device_ptr(covinv) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        GCHK(gmmk_reciprocal(c->stream, (long)(rows * CD), (const double *)tmp, b->iv));
+        b->si = covinv_stride == 0 ? 0 : (long)CD;
+    } else if ((rc = batch_table(b, &b->iv, &b->cap_iv, &b->si, covinv, covinv_stride, CD))) return rc;
     GCHK(gmmk_const_models(c->stream, b->G, b->C, b->Cpa, b->D, b->w, b->sw, b->mean, b->sm, b->iv, b->si, b->a, b->lwc));
     if (!gmmiv_is_device_ptr(w) || !gmmiv_is_device_ptr(mean) || !gmmiv_is_device_ptr(covinv)) GCHK(hipStreamSynchronize(c->stream)); // host sources may be freed by the caller on return
     b->loaded = true;
     return GMMIV_OK;
+}
+
+int gmmiv_gmm_batch_load(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride, const double *covinv,
+                         int64_t covinv_stride)
+{
+    return batch_load(b, w, w_stride, mean, mean_stride, covinv, covinv_stride, false);
+}
+int gmmiv_gmm_batch_load_cov(gmmiv_gmm_batch *b, const double *w, int64_t w_stride, const double *mean, int64_t mean_stride, const double *cov,
+                             int64_t cov_stride)
+{
+    return batch_load(b, w, w_stride, mean, mean_stride, cov, cov_stride, true);
 }
 
 static int check_batch(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const char *who)
@@ -356,22 +383,24 @@ int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int 
     return o_sum.finish();
 }
 
-int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
-                          const int32_t *seg_model, int64_t nseg, double *N, double *F, double *seg_llk)
+// N / F rows (second = false: gmmiv_tv_stats_models) or N / F / S rows (gmmiv_em_stats_models) of every segment under its model
+static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                        const int32_t *seg_model, int64_t nseg, double *N, double *F, double *S, double *seg_llk, bool second, const char *who)
 {
-    int rc = check_batch(c, b, "tv_stats_models");
+    int rc = check_batch(c, b, who);
     if (rc) return rc;
-    if ((rc = check_segments(b, "tv_stats_models", T, seg_begin, seg_model, nseg))) return rc;
-    if (!N || !F) { gmmiv_set_error("tv_stats_models: N and F are required"); return GMMIV_ERR_ARG; }
+    if ((rc = check_segments(b, who, T, seg_begin, seg_model, nseg))) return rc;
+    if (!N || !F || (second && !S)) { gmmiv_set_error("%s: %s are required", who, second ? "N, F and S" : "N and F"); return GMMIV_ERR_ARG; }
     if (nseg == 0) return GMMIV_OK;
     XView xv;
     if ((rc = xv.init(c, x, dt, T, ldx, b->D))) return rc;
     const size_t SV = (size_t)b->C * b->D;
-    DevOut<double> o_n, o_f, o_l;
+    DevOut<double> o_n, o_f, o_s, o_l;
     if ((rc = o_n.init(c, WS_T0, N, (size_t)nseg * b->C, false))) return rc;
     if ((rc = o_f.init(c, WS_T1, F, (size_t)nseg * SV, false))) return rc;
+    if (second && (rc = o_s.init(c, WS_T5, S, (size_t)nseg * SV, false))) return rc;
     if ((rc = o_l.init(c, WS_T4, seg_llk, 2 * (size_t)nseg, false))) return rc;
-    auto finish = [&]() { int r = o_n.finish(); if (!r) r = o_f.finish(); if (!r) r = o_l.finish(); return r; };
+    auto finish = [&]() { int r = o_n.finish(); if (!r) r = o_f.finish(); if (!r && second) r = o_s.finish(); if (!r) r = o_l.finish(); return r; };
     ModelPlan p;
     const int64_t Tc = models_chunk_frames(c, b);
     if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
@@ -405,9 +434,14 @@ int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x,
             }
             // every (segment, c < C) row is written by exactly one wave (zeros for an empty segment, whose likelihood blocks are never read)
             c->t_begin("k_stats_z", k == 0);
-            GCHK(gmmk_stats_z(c->stream, b->KS, 0, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
-                              (const double *)inv, efin, 1.0, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
-                              o_f.d + (size_t)ck.s0 * SV, 1, 0, c->prune_thr()));
+            if (second) // the EM shape (x^2 accumulators) with the row epilogue
+                GCHK(gmmk_stats_z_rows(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
+                                       (const double *)inv, efin, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
+                                       o_f.d + (size_t)ck.s0 * SV, o_s.d + (size_t)ck.s0 * SV, c->prune_thr()));
+            else
+                GCHK(gmmk_stats_z(c->stream, b->KS, 0, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
+                                  (const double *)inv, efin, 1.0, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
+                                  o_f.d + (size_t)ck.s0 * SV, 1, 0, c->prune_thr()));
             c->t_end();
             if (seg_llk)
                 GCHK(gmmk_llk_seg_finalize(c->stream, (const double *)lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), 0.0, 0.0, nullptr, nullptr,
@@ -421,7 +455,13 @@ int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x,
     OneModel om;
     GCHK(hipMemsetAsync(o_n.d, 0, (size_t)nseg * b->C * sizeof(double), c->stream));
     GCHK(hipMemsetAsync(o_f.d, 0, (size_t)nseg * SV * sizeof(double), c->stream));
+    if (second) GCHK(hipMemsetAsync(o_s.d, 0, (size_t)nseg * SV * sizeof(double), c->stream));
     if (seg_llk) GCHK(hipMemsetAsync(o_l.d, 0, 2 * (size_t)nseg * sizeof(double), c->stream));
+    // second order: the single-model EM kernels fill a flat accumulator [occ | sum g x | sum g x^2] (zeroed per segment: they add),
+    // unpacked into the segment's rows
+    const size_t nacc = (size_t)b->C * (1 + 2 * b->D);
+    void *accw = nullptr;
+    if (second && (rc = c->scratch(WS_T6, nacc * sizeof(double), &accw))) return rc;
     for (int64_t s = 0; s < nseg; ++s) {
         const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
         if (n <= 0) continue;
@@ -435,7 +475,25 @@ int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x,
         if ((rc = gmmiv_i_run_lse(c, g, sub, dt, n, &lse))) return rc;
         if ((rc = segment_table(c, n, &sb))) return rc;
         double *Nrow = o_n.d + (size_t)s * b->C, *Frow = o_f.d + (size_t)s * SV;
-        if (g->KS == GMMK_KS_GENERIC) {
+        if (second) {
+            GCHK(hipMemsetAsync(accw, 0, nacc * sizeof(double), c->stream));
+            if (g->KS == GMMK_KS_GENERIC) {
+                const int NC = 2 * g->D + 2; // [x | 1 | x^2 | 0]
+                void *Sg;
+                if ((rc = c->scratch(WS_PART, (size_t)g->C * NC * sizeof(double), &Sg))) return rc;
+                if ((rc = gmmiv_i_generic_gamma_gemm(c, g, sub, dt, 0, n, lse, true, NC, (double *)Sg))) return rc;
+                GCHK(gmmk_scatter_em(c->stream, g->C, g->D, NC, (const double *)Sg, 1.0, (double *)accw));
+            } else {
+                void *part;
+                if ((rc = c->scratch(WS_PART, (size_t)g->nct * 16 * 2 * gmmk_rl_for_ks(g->KS) * sizeof(double), &part))) return rc;
+                c->t_begin("k_stats_mfma", s == 0);
+                GCHK(gmmk_stats(c->stream, g->KS, 1, dt == GMMIV_F64, sub.d, sub.ldx, g->D, g->C, g->Pt, g->nct, lse, 0.0, sb, 1, (double *)part, nullptr, 0,
+                                (int)c->wg_waves, c->prune_arg()));
+                c->t_end();
+                GCHK(gmmk_em_reduce(c->stream, (const double *)part, 1, g->C, g->nct * 16, g->D, g->KS, (double *)accw));
+            }
+            GCHK(gmmk_acc_to_rows(c->stream, g->C, g->D, (const double *)accw, Nrow, Frow, o_s.d + (size_t)s * SV));
+        } else if (g->KS == GMMK_KS_GENERIC) {
             const int NC = g->D + 2 - (g->D & 1); // [x | 1] padded to an even width
             void *S;
             if ((rc = c->scratch(WS_PART, (size_t)g->C * NC * sizeof(double), &S))) return rc;
@@ -450,6 +508,17 @@ int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x,
         if (seg_llk) GCHK(gmmk_llk_seg_finalize(c->stream, lse, sb, 1, 0.0, 0.0, nullptr, nullptr, o_l.d + 2 * (size_t)s));
     }
     return finish();
+}
+
+int gmmiv_tv_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                          const int32_t *seg_model, int64_t nseg, double *N, double *F, double *seg_llk)
+{
+    return stats_models(c, b, x, dt, T, ldx, seg_begin, seg_model, nseg, N, F, nullptr, seg_llk, false, "tv_stats_models");
+}
+int gmmiv_em_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                          const int32_t *seg_model, int64_t nseg, double *N, double *F, double *S, double *seg_llk)
+{
+    return stats_models(c, b, x, dt, T, ldx, seg_begin, seg_model, nseg, N, F, S, seg_llk, true, "em_stats_models");
 }
 
 // ---- computeMAP for the batch -----------------------------------------------------------------------------------------------------------
@@ -484,6 +553,71 @@ int gmmiv_map_adapt_models(gmmiv_ctx *c, int G, int C, int D, const double *N, c
     if (!o_m.host && !o_w.host && !(gmmiv_is_device_ptr(N) && gmmiv_is_device_ptr(F) && gmmiv_is_device_ptr(count) && gmmiv_is_device_ptr(w0) &&
                                     gmmiv_is_device_ptr(mean0) && gmmiv_is_device_ptr(cur_mean)))
         GCHK(hipStreamSynchronize(c->stream));
+    return GMMIV_OK;
+}
+
+int gmmiv_map_adapt_models_full(gmmiv_ctx *c, int G, int C, int D, const double *N, const double *F, const double *S, const double *count,
+                                int64_t count_stride, const double *w0, const double *mean0, const double *cov0, const double *cur_mean,
+                                int64_t cur_mean_stride, const double *cur_cov, int64_t cur_cov_stride, int method, int mean_adapt, int var_adapt,
+                                int weight_adapt, double mean_reg, double var_reg, double weight_reg, double mean_alpha, double *mean_out,
+                                double *cov_out, double *w_out, int32_t *status)
+{
+    if (!c || G < 0 || C <= 0 || D <= 0 || !N || !F || !count || count_stride < 1 || !w0 || !mean0 || !cov0 || !cur_mean || cur_mean_stride < 0 ||
+        cur_cov_stride < 0 || (!mean_out && !cov_out && !w_out) || !status || method < GMMIV_MAP_NONE || method > GMMIV_MAP_CONST2) {
+        gmmiv_set_error("map_adapt_models_full: bad argument");
+        return GMMIV_ERR_ARG;
+    }
+    const size_t CD = (size_t)C * D;
+    const bool ml_cov = cov_out && (method == GMMIV_MAP_NONE || (var_adapt && (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED)));
+    if (ml_cov && (!S || !cur_cov)) { gmmiv_set_error("map_adapt_models_full: this configuration reads S and cur_cov"); return GMMIV_ERR_ARG; }
+    if ((cur_mean_stride && cur_mean_stride < (int64_t)CD) || (cur_cov_stride && cur_cov_stride < (int64_t)CD)) {
+        gmmiv_set_error("map_adapt_models_full: a stride must be 0 (shared) or at least C * D");
+        return GMMIV_ERR_ARG;
+    }
+    if (G == 0) return GMMIV_OK;
+    GBIND(c);
+    int rc;
+    auto span = [&](int64_t stride) { return stride ? (size_t)(G - 1) * stride + CD : CD; };
+    DevIn<double> i_n, i_f, i_s, i_c, i_w0, i_m0, i_c0, i_cm, i_cc;
+    DevOut<double> o_m, o_v, o_w;
+    DevOut<int32_t> o_st;
+    if ((rc = i_n.init(c, WS_T2, N, (size_t)G * C)) || (rc = i_f.init(c, WS_T3, F, (size_t)G * CD)) || (rc = i_s.init(c, WS_T0, ml_cov ? S : nullptr, (size_t)G * CD)) ||
+        (rc = i_c.init(c, WS_T4, count, (size_t)(G - 1) * count_stride + 1)) || (rc = i_w0.init(c, WS_T5, w0, (size_t)C)) ||
+        (rc = i_m0.init(c, WS_T6, mean0, CD)) || (rc = i_c0.init(c, WS_T1, cov0, CD)) || (rc = i_cm.init(c, WS_T7, cur_mean, span(cur_mean_stride))) ||
+        (rc = i_cc.init(c, WS_TIV, ml_cov ? cur_cov : nullptr, span(cur_cov_stride))) || (rc = o_m.init(c, WS_T8, mean_out, (size_t)G * CD, false)) ||
+        (rc = o_v.init(c, WS_LP, cov_out, (size_t)G * CD, false)) || (rc = o_w.init(c, WS_T9, w_out, (size_t)G * C, false)) ||
+        (rc = o_st.init(c, WS_AUX, status, (size_t)G, false)))
+        return rc;
+    c->t_begin("k_map_adapt");
+    GCHK(gmmk_map_adapt_models_full(c->stream, G, C, D, i_n.d, i_f.d, i_s.d, i_c.d, (long)count_stride, i_w0.d, i_m0.d, i_c0.d, i_cm.d, (long)cur_mean_stride,
+                                    i_cc.d, (long)cur_cov_stride, method, mean_adapt, var_adapt, weight_adapt, mean_reg, var_reg, weight_reg, mean_alpha,
+                                    mean_out ? o_m.d : nullptr, cov_out ? o_v.d : nullptr, w_out ? o_w.d : nullptr, o_st.d));
+    c->t_end();
+    if ((rc = o_m.finish()) || (rc = o_v.finish()) || (rc = o_w.finish()) || (rc = o_st.finish())) return rc;
+    // host inputs were staged with asynchronous copies from the caller's arrays
+    const void *ins[] = {N, F, ml_cov ? S : nullptr, count, w0, mean0, cov0, cur_mean, ml_cov ? cur_cov : nullptr};
+    bool host_in = false;
+    for (const void *q : ins) host_in |= q && !gmmiv_is_device_ptr(q);
+    if (host_in && !o_m.host && !o_v.host && !o_w.host && !o_st.host) GCHK(hipStreamSynchronize(c->stream));
+    return GMMIV_OK;
+}
+
+int gmmiv_normalize_models(gmmiv_ctx *c, int G, int C, int D, const double *w, int64_t w_stride, double *mean, double *cov, int nb_it, int mean_only)
+{
+    if (!c || G < 0 || C <= 0 || D <= 0 || !w || !mean || !cov || nb_it < 0 || (w_stride && w_stride < C)) {
+        gmmiv_set_error("normalize_models: bad argument (cov is read in either mode: the fusion needs the variances)");
+        return GMMIV_ERR_ARG;
+    }
+    if (!gmmiv_is_device_ptr(mean) || !gmmiv_is_device_ptr(cov)) { gmmiv_set_error("normalize_models: mean and cov are device arrays (updated in place)"); return GMMIV_ERR_ARG; }
+    if (G == 0 || nb_it == 0) return GMMIV_OK;
+    GBIND(c);
+    DevIn<double> i_w;
+    int rc = i_w.init(c, WS_T0, w, w_stride ? (size_t)(G - 1) * w_stride + C : (size_t)C);
+    if (rc) return rc;
+    c->t_begin("k_normalize_models");
+    GCHK(gmmk_normalize_models(c->stream, G, C, D, i_w.d, (long)w_stride, mean, cov, nb_it, mean_only));
+    c->t_end();
+    if (!gmmiv_is_device_ptr(w)) GCHK(hipStreamSynchronize(c->stream));
     return GMMIV_OK;
 }
 

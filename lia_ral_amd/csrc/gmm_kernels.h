@@ -83,6 +83,18 @@ int gmmk_llk_seg_finalize(hipStream_t st, const double *lse, const long *sb, lon
 int gmmk_map_adapt_models(hipStream_t st, int G, int C, int D, const double *N, const double *F, const double *count, long count_stride,
                           const double *w0, const double *mean0, const double *cur, long cur_stride, int method, int mean_adapt,
                           int weight_adapt, double mean_reg, double weight_reg, double mean_alpha, double *mean_out, double *w_out);
+// computeMAP with the variance branch (gmmiv_map_adapt_models_full): S / cur_cov / cov0 / any of the outputs nullable as the header says;
+// status [G] (int32) = entries of cov_out that are not positive and finite, written on the device
+int gmmk_map_adapt_models_full(hipStream_t st, int G, int C, int D, const double *N, const double *F, const double *S, const double *count,
+                               long count_stride, const double *w0, const double *mean0, const double *cov0, const double *cur_mean,
+                               long cur_mean_stride, const double *cur_cov, long cur_cov_stride, int method, int mean_adapt, int var_adapt,
+                               int weight_adapt, double mean_reg, double var_reg, double weight_reg, double mean_alpha, double *mean_out,
+                               double *cov_out, double *w_out, int *status);
+// normalizeMixture towards N(0, 1) for G models in place: one thread per (model, dimension), the fold of mixtureFusion over c = 0 .. C-1
+int gmmk_normalize_models(hipStream_t st, int G, int C, int D, const double *w, long w_stride, double *mean, double *cov, int nb_it,
+                          int mean_only);
+// three pieces of a flat EM accumulator [occ | sum g x | sum g x^2 | ..] into statistics rows (the segment walk of gmmiv_em_stats_models)
+int gmmk_acc_to_rows(hipStream_t st, int C, int D, const double *acc, double *Nrow, double *Frow, double *Srow);
 // k_llk_mfma<TC>: candidates of the top-C' selection collected in the log-likelihood kernel (see gmm_kernels.hip), ranked by
 // gmmk_topc_rank (topc_z.hip)
 int gmmk_topc_cap(void);
@@ -102,6 +114,10 @@ int gmmk_stats_z_wg_per_cu(void);
 int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf,
                  long nfb, const int *eit, const double *inv, const int *efin, double scale, const long *seg_begin, int nseg,
                  double *out0, double *out1, int mode, int accum, double prune_thr);
+// the EM shape with a row epilogue: N [nseg x C], F, X2 [nseg x C*D] = sum_t gamma [1 | x | x^2] of every segment, written directly
+int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
+                      const int *eit, const double *inv, const int *efin, const long *seg_begin, int nseg, double *N, double *F, double *X2,
+                      double prune_thr);
 size_t gmmk_topc_z_lds(int nct, int D);
 int gmmk_topc_from_z(hipStream_t st, int x_f64, const void *x, long n, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
                      const int *eit, const int *efin, const double *mean, const double *iv, const double *lwc,

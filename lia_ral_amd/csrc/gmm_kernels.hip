@@ -1472,6 +1472,24 @@ int gmmk_llk_seg_finalize(hipStream_t st, const double *lse, const long *sb, lon
 // computeMAP for G models (include/gmmiv.h, gmmiv_map_adapt_models): the mean branch, one thread per (g, c, d).  Every operation is
 // rounded on its own like the host's computeMAP* (no fma contraction).
 __device__ __forceinline__ double map_ml_weight(double n, double count) { return count > 0.0 ? n / count : 0.0; }
+// the mean branch for one element: ml = the ML mean (or the current mean of a Gaussian without occupancy), w = the ML weight
+__device__ __forceinline__ double map_mean_one(double ml, double m0, double w, double w0c, double cnt, int method, int mean_adapt, double mean_reg,
+                                               double mean_alpha)
+{
+#pragma clang fp contract(off)
+    double r = ml;
+    if (method != GMMIV_MAP_NONE && !mean_adapt) r = m0;
+    else if (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) {
+        const double alpha = w * (double)(unsigned long)cnt;
+        const double a = alpha / (alpha + mean_reg);
+        r = (1 - a) * m0 + a * ml;
+    } else if (method == GMMIV_MAP_CONST) {
+        r = (mean_alpha * m0) + ((1 - mean_alpha) * ml);
+    } else if (method == GMMIV_MAP_CONST2) {
+        r = ((mean_alpha * w0c * m0) + ((1 - mean_alpha) * w * ml)) / (w0c * mean_alpha + w * (1 - mean_alpha));
+    }
+    return r;
+}
 __global__ __launch_bounds__(256) void k_map_adapt_mean(long total, int C, int D, const double *__restrict__ N, const double *__restrict__ F,
                                                        const double *__restrict__ count, long count_stride, const double *__restrict__ w0,
                                                        const double *__restrict__ mean0, const double *__restrict__ cur, long cur_stride,
@@ -1486,20 +1504,92 @@ __global__ __launch_bounds__(256) void k_map_adapt_mean(long total, int C, int D
         const double n = N[g * C + c], cnt = count[g * count_stride];
         const double w = map_ml_weight(n, cnt);
         const double ml = n > 0.0 ? F[e] / n : cur[g * cur_stride + cd];
-        const double m0 = mean0[cd];
-        double r = ml;
-        if (method != GMMIV_MAP_NONE && !mean_adapt) r = m0;
-        else if (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) {
-            const double alpha = w * (double)(unsigned long)cnt;
-            const double a = alpha / (alpha + mean_reg);
-            r = (1 - a) * m0 + a * ml;
-        } else if (method == GMMIV_MAP_CONST) {
-            r = (mean_alpha * m0) + ((1 - mean_alpha) * ml);
-        } else if (method == GMMIV_MAP_CONST2) {
-            r = ((mean_alpha * w0[c] * m0) + ((1 - mean_alpha) * w * ml)) / (w0[c] * mean_alpha + w * (1 - mean_alpha));
-        }
-        mean_out[e] = r;
+        mean_out[e] = map_mean_one(ml, mean0[cd], w, w0[c], cnt, method, mean_adapt, mean_reg, mean_alpha);
     }
+}
+// all three branches (gmmiv_map_adapt_models_full): one thread per (c, d) of model g = blockIdx.y, so that a wave stays inside one
+// model and the count of bad variances is one integer atomic per wave that has any.  The mean is map_mean_one on the same operands as
+// k_map_adapt_mean: the same bits.  ML variance S / N - mean_ml^2 as gmmiv_em_get; a Gaussian without occupancy keeps cur_cov.
+__global__ __launch_bounds__(256) void k_map_adapt_full(int C, int D, const double *__restrict__ N, const double *__restrict__ F,
+                                                       const double *__restrict__ S, const double *__restrict__ count, long count_stride,
+                                                       const double *__restrict__ w0, const double *__restrict__ mean0,
+                                                       const double *__restrict__ cov0, const double *__restrict__ cur_mean, long cur_mean_stride,
+                                                       const double *__restrict__ cur_cov, long cur_cov_stride, int method, int mean_adapt,
+                                                       int var_adapt, double mean_reg, double var_reg, double mean_alpha,
+                                                       double *__restrict__ mean_out, double *__restrict__ cov_out, int *__restrict__ status)
+{
+#pragma clang fp contract(off)
+    const long CD = (long)C * D, g = blockIdx.y;
+    const bool ml_cov = method == GMMIV_MAP_NONE || (var_adapt && (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED));
+    const double cnt = count[g * count_stride];
+    for (long cd0 = (long)blockIdx.x * blockDim.x; cd0 < CD; cd0 += (long)gridDim.x * blockDim.x) { // uniform per workgroup
+        const long cd = cd0 + threadIdx.x;
+        bool bad = false;
+        if (cd < CD) {
+            const long e = g * CD + cd;
+            const int c = (int)(cd / D);
+            const double n = N[g * C + c];
+            const double w = map_ml_weight(n, cnt);
+            const double ml = n > 0.0 ? F[e] / n : cur_mean[g * cur_mean_stride + cd];
+            const double m0 = mean0[cd];
+            if (mean_out) mean_out[e] = map_mean_one(ml, m0, w, w0[c], cnt, method, mean_adapt, mean_reg, mean_alpha);
+            if (cov_out) {
+                double r;
+                if (ml_cov) {
+                    const double cml = n > 0.0 ? S[e] / n - ml * ml : cur_cov[g * cur_cov_stride + cd];
+                    if (method == GMMIV_MAP_NONE) r = cml;
+                    else {
+                        const double alpha = w * (double)(unsigned long)cnt;
+                        const double a = alpha / (alpha + var_reg);
+                        const double dm = m0 - ml;
+                        r = (1 - a) * cov0[cd] + a * cml + (1 - a) * a * dm * dm;
+                    }
+                } else r = cov0[cd]; // the two constant methods and var_adapt = 0: the a-priori variance
+                cov_out[e] = r;
+                bad = !(r > 0.0 && r < __builtin_inf());
+            }
+        }
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
+        if (m && (threadIdx.x & 63) == 0) atomicAdd(&status[g], (int)__builtin_popcountll(m));
+    }
+}
+// normalizeMixture(zeroOne) for model g, dimension d per thread (consecutive threads = consecutive d: coalesced rows).  The fold and the
+// update are liagpu::mixtureFusion / normalizeMixture statement for statement, every operation rounded on its own.
+__global__ __launch_bounds__(64) void k_normalize_models(int G, int C, int D, const double *__restrict__ w, long w_stride, double *__restrict__ mean,
+                                                        double *__restrict__ cov, int nb_it, int mean_only)
+{
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)G * D) return;
+    const long g = t / D;
+    const int d = (int)(t - g * D);
+    const double *wg = w + g * w_stride;
+    double *m = mean + g * (long)C * D + d, *v = cov + g * (long)C * D + d;
+    for (int it = 0; it < nb_it; ++it) {
+        double tm = m[0], tc = v[0], wtmp = wg[0];
+        for (int i = 1; i < C; ++i) {
+            const double w1 = wg[i], a1 = w1 / (w1 + wtmp), a2 = 1.0 - a1;
+            const double mi = m[(long)i * D], dd = mi - tm;
+            tc = a1 * v[(long)i * D] + a2 * tc + a1 * a2 * dd * dd;
+            tm = (a1 * mi) + (a2 * tm);
+            wtmp = w1 + wtmp;
+        }
+        const double sd = __builtin_sqrt(tc);
+        for (int i = 0; i < C; ++i) {
+            double nm = m[(long)i * D] - tm;
+            nm /= sd;
+            m[(long)i * D] = nm;
+            if (!mean_only) v[(long)i * D] = v[(long)i * D] / tc;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_acc_to_rows(int C, int D, const double *__restrict__ acc, double *__restrict__ Nrow, double *__restrict__ Frow,
+                                                    double *__restrict__ Srow)
+{
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x, CD = (long)C * D;
+    if (e < C) Nrow[e] = acc[e];
+    else if (e < C + CD) Frow[e - C] = acc[e];
+    else if (e < C + 2 * CD) Srow[e - C - CD] = acc[e];
 }
 // the weight branch: one workgroup per model, sum over c = 0 .. C-1 left to right like the reference's loop
 __global__ __launch_bounds__(256) void k_map_adapt_weight(int C, const double *__restrict__ N, const double *__restrict__ count, long count_stride,
@@ -1540,6 +1630,45 @@ int gmmk_map_adapt_models(hipStream_t st, int G, int C, int D, const double *N, 
     k_map_adapt_mean<<<blocks, 256, 0, st>>>(total, C, D, N, F, count, count_stride, w0, mean0, cur, cur_stride, method, mean_adapt, mean_reg,
                                              mean_alpha, mean_out);
     if (w_out) k_map_adapt_weight<<<(unsigned)G, 256, 0, st>>>(C, N, count, count_stride, w0, method, weight_adapt, weight_reg, w_out);
+    return (int)hipGetLastError();
+}
+
+int gmmk_map_adapt_models_full(hipStream_t st, int G, int C, int D, const double *N, const double *F, const double *S, const double *count,
+                               long count_stride, const double *w0, const double *mean0, const double *cov0, const double *cur_mean,
+                               long cur_mean_stride, const double *cur_cov, long cur_cov_stride, int method, int mean_adapt, int var_adapt,
+                               int weight_adapt, double mean_reg, double var_reg, double weight_reg, double mean_alpha, double *mean_out,
+                               double *cov_out, double *w_out, int *status)
+{
+    if (G <= 0) return 0;
+    hipError_t e = hipMemsetAsync(status, 0, (size_t)G * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    if (mean_out || cov_out) {
+        const long CD = (long)C * D;
+        const unsigned bx = (unsigned)((CD + 255) / 256 > 1024 ? 1024 : (CD + 255) / 256);
+        for (int g0 = 0; g0 < G; g0 += 65535) { // grid.y limit
+            const int ng = G - g0 < 65535 ? G - g0 : 65535;
+            const long o = (long)g0 * CD;
+            k_map_adapt_full<<<dim3(bx, (unsigned)ng), 256, 0, st>>>(C, D, N + (long)g0 * C, F + o, S ? S + o : nullptr, count + g0 * count_stride, count_stride,
+                                                                     w0, mean0, cov0, cur_mean + g0 * cur_mean_stride, cur_mean_stride,
+                                                                     cur_cov ? cur_cov + g0 * cur_cov_stride : nullptr, cur_cov_stride, method, mean_adapt,
+                                                                     var_adapt, mean_reg, var_reg, mean_alpha, mean_out ? mean_out + o : nullptr,
+                                                                     cov_out ? cov_out + o : nullptr, status + g0);
+        }
+    }
+    if (w_out) k_map_adapt_weight<<<(unsigned)G, 256, 0, st>>>(C, N, count, count_stride, w0, method, weight_adapt, weight_reg, w_out);
+    return (int)hipGetLastError();
+}
+int gmmk_normalize_models(hipStream_t st, int G, int C, int D, const double *w, long w_stride, double *mean, double *cov, int nb_it, int mean_only)
+{
+    if (G <= 0 || nb_it <= 0) return 0;
+    const long n = (long)G * D;
+    k_normalize_models<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(G, C, D, w, w_stride, mean, cov, nb_it, mean_only);
+    return (int)hipGetLastError();
+}
+int gmmk_acc_to_rows(hipStream_t st, int C, int D, const double *acc, double *Nrow, double *Frow, double *Srow)
+{
+    const long n = (long)C * (1 + 2 * D);
+    k_acc_to_rows<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(C, D, acc, Nrow, Frow, Srow);
     return (int)hipGetLastError();
 }
 

@@ -21,6 +21,9 @@
 //   mode 0 (EM):  out0[seg][c][2 RL] partial sums (cols: x | x^2 halves; col Dp = occupancy);
 //                 accum != 0 adds to what is there (frame chunks processed by successive launches)
 //   mode 1 (TV):  N = out0[seg][C], F = out1[seg][C*D] written directly
+//   ROWS (compile time, with SQ; gmmk_stats_z_rows): N = out0[seg][C], F = out1[seg][C*D], sum g x^2 = out2[seg][C*D] written directly --
+//                 second-order statistics per segment (gmmiv_em_stats_models).  `mode` and `accum` are not consulted; the default
+//                 ROWS = false leaves the epilogue of every other instantiation as it was
 // Segment bounds are frame indices relative to x / inv / efin / zbuf block 0; a segment may start
 // anywhere: its first tile starts at the 16-frame block holding f0 and rows before f0 are masked
 // (1 / S_t = 0).
@@ -47,14 +50,15 @@
 static constexpr bool z_x2_in_lds(bool SQ, bool PRUNE, int NW, int TPW, int FT) { return SQ && !PRUNE && NW == 8 && TPW == 2 && FT == 64; }
 static constexpr int z_row_len(int RL, bool x2) { return x2 ? 2 * RL : RL + 32; } // doubles per LDS row
 
-template <int KS, bool SQ, typename XT, bool PRUNE, int NW = 8, int TPW = 2, int FT = 64, int ZD = 2>
+template <int KS, bool SQ, typename XT, bool PRUNE, int NW = 8, int TPW = 2, int FT = 64, int ZD = 2, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64, (TPW == 1 ? 4 : 2)) void k_stats_z(const void *__restrict__ x, long ldx, int D, int C, int nct,
                                                     const double *__restrict__ zbuf, long nfb, const int *__restrict__ eit,
                                                     const double *__restrict__ inv, const int *__restrict__ efin, double scale,
                                                     const long *__restrict__ seg_begin, int nseg, int ngrp,
                                                     double *__restrict__ out0, double *__restrict__ out1, int mode, int accum,
-                                                    unsigned magicD, double prune_arg)
+                                                    unsigned magicD, double prune_arg, double *__restrict__ out2)
 {
+    static_assert(!ROWS || SQ, "the row epilogue writes the x^2 accumulators");
     constexpr int Dp = 4 * KS;
     constexpr int RL = ((Dp + 2 + 31) / 32) * 32;
     constexpr int JT = RL / 16;
@@ -298,7 +302,22 @@ __global__ __launch_bounds__(NW * 64, (TPW == 1 ? 4 : 2)) void k_stats_z(const v
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
         const int ct = ct0 + t;
-        if (mode == 0) {
+        if constexpr (ROWS) {
+            double *N = out0 + (size_t)seg * C;
+            double *F = out1 + (size_t)seg * C * D;
+            double *X2s = out2 + (size_t)seg * C * D;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = ct * 16 + q + 4 * r;
+                if (c >= C) continue;
+#pragma unroll
+                for (int j = 0; j < JT; ++j) {
+                    const int col = 16 * j + i16;
+                    if (col < D) { F[(size_t)c * D + col] = S[t][j][r]; X2s[(size_t)c * D + col] = S2[t][SQ ? j : 0][r]; }
+                    else if (col == Dp) N[c] = S[t][j][r];
+                }
+            }
+        } else if (mode == 0) {
             const size_t Cp = (size_t)nct * 16;
             double *o = out0 + (size_t)seg * Cp * (2 * RL);
 #pragma unroll
@@ -345,28 +364,28 @@ __global__ __launch_bounds__(NW * 64, (TPW == 1 ? 4 : 2)) void k_stats_z(const v
 int gmmk_stats_z_groups(int nct) { const int tpg = g_stats_z_waves == 4 ? 8 : 16; return (nct + tpg - 1) / tpg; }
 int gmmk_stats_z_wg_per_cu(void) { return g_stats_z_waves == 4 ? 2 : 1; }
 
-template <int KS, bool SQ, typename XT, bool PRUNE, int NW, int TPW, int FT, int ZD = 2>
+template <int KS, bool SQ, typename XT, bool PRUNE, int NW, int TPW, int FT, int ZD = 2, bool ROWS = false>
 static int launch_z(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
                     const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
-                    int mode, int accum, double prune_thr)
+                    int mode, int accum, double prune_thr, double *out2)
 {
     constexpr int RL = ((4 * KS + 2 + 31) / 32) * 32;
     constexpr int PF = TPW > 2 ? TPW / 2 : 1;
     const size_t lds = (size_t)2 * FT * z_row_len(RL, z_x2_in_lds(SQ, PRUNE, NW, TPW, FT)) * sizeof(double) + (size_t)2 * NW * PF * FT * sizeof(double); // two frame tiles + posterior factors
-    HIPCHK((gmmiv_lds_attr<k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD>>(lds))); // per (device, kernel): lds_attr.h
+    HIPCHK((gmmiv_lds_attr<k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD, ROWS>>(lds))); // per (device, kernel): lds_attr.h
     const int ngrp = (nct + TPW * NW - 1) / (TPW * NW);
     const unsigned grid = (unsigned)(ngrp * 8 * ((nseg + 7) / 8));
     const unsigned magicD = gmmiv_div_magic(D);
-    k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD><<<grid, NW * 64, lds, st>>>(x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg, ngrp,
-                                                              out0, out1, mode, accum, magicD, prune_thr);
+    k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD, ROWS><<<grid, NW * 64, lds, st>>>(x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg,
+                                                                    ngrp, out0, out1, mode, accum, magicD, prune_thr, out2);
     return (int)hipGetLastError();
 }
 
-#define ZARGS st, x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg, out0, out1, mode, accum, prune_thr
+#define ZARGS st, x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg, out0, out1, mode, accum, prune_thr, out2
 template <int KS, bool SQ, typename XT>
 static int launch_z_p(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
                       const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
-                      int mode, int accum, double prune_thr)
+                      int mode, int accum, double prune_thr, double *out2)
 {
     if (prune_thr > 0.0) return launch_z<KS, SQ, XT, true, 8, 2, 64>(ZARGS);
     if (g_stats_z_waves == 4) return launch_z<KS, SQ, XT, false, 4, 2, 32>(ZARGS);
@@ -380,6 +399,18 @@ static int launch_z_p(hipStream_t st, const void *x, long ldx, int D, int C, int
     } else if (g_stats_z_depth_em == 4) return launch_z<KS, SQ, XT, false, 8, 2, 64, 4>(ZARGS);
     return launch_z<KS, SQ, XT, false, 8, 2, 64>(ZARGS);
 }
+// the EM shapes with the row epilogue (N, F, sum g x^2 per segment): the same choice of workgroup shape / stream depth / pruning
+template <int KS, typename XT>
+static int launch_z_rows(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
+                         const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
+                         int mode, int accum, double prune_thr, double *out2)
+{
+    if (prune_thr > 0.0) return launch_z<KS, true, XT, true, 8, 2, 64, 2, true>(ZARGS);
+    if (g_stats_z_waves == 4) return launch_z<KS, true, XT, false, 4, 2, 32, 2, true>(ZARGS);
+    if (g_stats_z_waves == 16) return launch_z<KS, true, XT, false, 16, 1, 64, 2, true>(ZARGS);
+    if (g_stats_z_depth_em == 4) return launch_z<KS, true, XT, false, 8, 2, 64, 4, true>(ZARGS);
+    return launch_z<KS, true, XT, false, 8, 2, 64, 2, true>(ZARGS);
+}
 
 // scale multiplies every posterior (the EM frame weight); prune_thr > 0: groups of 4 frames x 32
 // Gaussians whose posteriors are all below prune_thr are skipped (opt-in, see ctx.h)
@@ -388,10 +419,30 @@ int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long 
                  double *out0, double *out1, int mode, int accum, double prune_thr)
 {
     if (nseg <= 0) return 0;
+    double *const out2 = nullptr;
 #define CASE(K)                                                                                      \
     case K:                                                                                          \
         if (sq) return x_f64 ? launch_z_p<K, true, double>(ZARGS) : launch_z_p<K, true, float>(ZARGS); \
         return x_f64 ? launch_z_p<K, false, double>(ZARGS) : launch_z_p<K, false, float>(ZARGS);
+    switch (KS) {
+        CASE(4) CASE(8) CASE(15)
+    }
+#undef CASE
+    return -1;
+}
+
+// N [nseg x C], F [nseg x C*D], X2 [nseg x C*D] = sum_t gamma [1 | x | x^2] per segment, rows written directly (every (segment, c < C)
+// row by exactly one wave, in the fixed order of the segment's own blocks: no atomics, no dependence on the other segments)
+int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
+                      const int *eit, const double *inv, const int *efin, const long *seg_begin, int nseg, double *N, double *F, double *X2,
+                      double prune_thr)
+{
+    if (nseg <= 0) return 0;
+    const double scale = 1.0;
+    double *const out0 = N, *const out1 = F, *const out2 = X2;
+    const int mode = 1, accum = 0;
+#define CASE(K) \
+    case K: return x_f64 ? launch_z_rows<K, double>(ZARGS) : launch_z_rows<K, float>(ZARGS);
     switch (KS) {
         CASE(4) CASE(8) CASE(15)
     }

@@ -348,6 +348,7 @@ static MAPCfg make_map_cfg(const char *method, int nbTrainIt, double baggedP, in
     cfg.method = method ? method : "MAPOccDep";
     cfg.nbTrainIt = (unsigned long)nbTrainIt; cfg.baggedFrameProbability = baggedP;
     cfg.meanAdapt = (flags & 1) != 0; cfg.varAdapt = (flags & 2) != 0; cfg.weightAdapt = (flags & 4) != 0;
+    cfg.batchVariances = (flags & 8) != 0; // adaptModelBatch only
     if (reg) { cfg.meanReg = reg[0]; cfg.varReg = reg[1]; cfg.weightReg = reg[2]; }
     cfg.meanAlpha = alphaMean;
     if (norm) { cfg.normalizeModel = norm[0] != 0; cfg.normalizeModelMeanOnly = norm[1] != 0; cfg.normalizeModelNbIt = (unsigned long)norm[2]; }
@@ -355,7 +356,7 @@ static MAPCfg make_map_cfg(const char *method, int nbTrainIt, double baggedP, in
 }
 
 // TrainTarget with every MAPCfg parameter (TrainTools.cpp:95-147): method = MAPAlgo, flags bit 0 / 1 / 2 = meanAdapt / varAdapt /
-// weightAdapt, reg[3] = MAPRegFactorMean / Var / Weight, alphaMean = MAPAlphaMean, norm[3] = normalizeModel, MeanOnly, NbIt (nullable)
+// weightAdapt (bit 3, batched calls only: MAPCfg::batchVariances), reg[3] = MAPRegFactorMean / Var / Weight, alphaMean = MAPAlphaMean, norm[3] = normalizeModel, MeanOnly, NbIt (nullable)
 int liagpu_train_target_ex(int device, const float *x, long T, int D, const long *seg_begin, const long *seg_len, long nseg, int C,
                            const double *w, const double *mean, const double *cov, const char *method, int nbTrainIt, double baggedP,
                            int flags, const double *reg, double alphaMean, const long *norm, double *w_out, double *mean_out, double *cov_out)
@@ -432,9 +433,21 @@ int liagpu_bench_enroll(int device, const float *x, long T, int D, long nclients
     if (!rc) memcpy(kernel_ms, km, 3 * sizeof(double));
     return rc;
 }
+// liagpu_bench_enroll_flags (tools/bench_enroll_var.py): the same with the MAPCfg flags of liagpu_train_target_ex (bit 1 varAdapt, bit 3
+// batchVariances, ...); cov0_out (nullable): the adapted variances of client 0
+int liagpu_bench_enroll_flags(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
+                              const double *cov, const char *method, int nbTrainIt, int flags, int which, int reps, long warm_clients, double *ms_out,
+                              double *kernel_ms, double *mean0_out, double *cov0_out);
 int liagpu_bench_enroll_method(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
                                const double *cov, const char *method, int nbTrainIt, int which, int reps, long warm_clients, double *ms_out,
                                double *kernel_ms, double *mean0_out)
+{
+    return liagpu_bench_enroll_flags(device, x, T, D, nclients, frames_per_client, C, w, mean, cov, method, nbTrainIt, 1, which, reps, warm_clients, ms_out,
+                                     kernel_ms, mean0_out, nullptr);
+}
+int liagpu_bench_enroll_flags(int device, const float *x, long T, int D, long nclients, long frames_per_client, int C, const double *w, const double *mean,
+                              const double *cov, const char *method, int nbTrainIt, int flags, int which, int reps, long warm_clients, double *ms_out,
+                              double *kernel_ms, double *mean0_out, double *cov0_out)
 {
     GUARD({
         if (nclients * frames_per_client > T) throw Exception("bench_enroll: not enough frames");
@@ -450,6 +463,7 @@ int liagpu_bench_enroll_method(int device, const float *x, long T, int D, long n
         MAPCfg cfg;
         cfg.nbTrainIt = (unsigned long)nbTrainIt;
         if (method) cfg.method = method;
+        cfg.meanAdapt = (flags & 1) != 0; cfg.varAdapt = (flags & 2) != 0; cfg.weightAdapt = (flags & 4) != 0; cfg.batchVariances = (flags & 8) != 0;
         std::vector<MixtureGD> clients;
         auto run = [&](long n) {
             clients.assign((size_t)n, world);
@@ -476,6 +490,7 @@ int liagpu_bench_enroll_method(int device, const float *x, long T, int D, long n
         kernel_ms[4] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_mllr_pack");
         (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 0);
         if (mean0_out) memcpy(mean0_out, clients[0].means().data(), (size_t)C * D * sizeof(double));
+        if (cov0_out) memcpy(cov0_out, clients[0].covs().data(), (size_t)C * D * sizeof(double));
     })
 }
 

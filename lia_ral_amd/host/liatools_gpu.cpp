@@ -1438,8 +1438,114 @@ static void adaptModelW(FeatureBuffer &fs, const SegCluster &selectedSegments, c
 // bitwise.  Bagging: every client's selection of every iteration is drawn HERE, on the host, before any device work, in the rand() /
 // srand(trainIt) order the sequential calls would produce (client-major: client 0's nbTrainIt draws, each followed by srand(trainIt),
 // then client 1's, ...).
-// NOT batched: varAdapt (needs second-order statistics per segment), normalizeModel (a host pass over each client's model per
-// iteration) -- for those configurations, and for clients of different shapes, this function runs the per-client loop above.
+// varAdapt, normalizeModel and an unknown MAPAlgo (the ML estimate, variances included) run the per-client loop above unless
+// mapCfg.batchVariances is set: then adaptModelBatchVar below keeps them on the device.  Clients of different shapes always run the loop.
+//
+// adaptModelBatchVar: per iteration gmmiv_em_stats_models (N, F and sum g x^2 per client), gmmiv_map_adapt_models_full (all three
+// branches of computeMAP), gmmiv_normalize_models when normalizeModel is set, and gmmiv_gmm_batch_load_cov for the next iteration --
+// nothing leaves the device until the models come back at the end.  The statuses (variances that are not positive and finite, per
+// client and iteration) are read once, after the last iteration.  adaptModel itself does not examine the variances it computes: the
+// client gets the model as computed (its next pass then drops every frame as a zero-likelihood frame) and nothing is thrown.  The same
+// here; the first such client and iteration are named on stderr.
+static void adaptModelBatchVar(FeatureBuffer &fs, const std::vector<std::vector<SegCluster>> &bagged, const MixtureGD &aprioriModel, const MixtureGD &prior,
+                               std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg, int method)
+{
+    const size_t G = clientMixtures.size();
+    const unsigned long C = aprioriModel.getDistribCount(), D = aprioriModel.getVectSize(), nIt = mapCfg.nbTrainIt;
+    const size_t CD = (size_t)C * D;
+    const bool occ = method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED;
+    const bool perClientW = method == GMMIV_MAP_NONE || (mapCfg.weightAdapt && occ);
+    const bool covChanges = method == GMMIV_MAP_NONE || (occ && mapCfg.varAdapt) || (mapCfg.normalizeModel && !mapCfg.normalizeModelMeanOnly);
+    GpuServer &srv = fs.server();
+    struct Batch {
+        gmmiv_gmm_batch *h = nullptr;
+        ~Batch() { gmmiv_gmm_batch_destroy(h); }
+    } batch;
+    srv.check(gmmiv_gmm_batch_create(srv.ctx(), (int)G, (int)C, (int)D, &batch.h));
+    // N | F | S | seg_llk | means (two, alternating) | variances (two) | weights | w0 | mean0 | cov0 | the prior's weights | statuses
+    const size_t nStat = (size_t)nIt * G;
+    double *buf = (double *)srv.workspace(5, (G * C + 2 * G * CD + 2 * G + 4 * G * CD + G * C + 2 * C + 2 * CD + (nStat + 1) / 2) * sizeof(double));
+    double *dN = buf, *dF = dN + G * C, *dS = dF + G * CD, *dL = dS + G * CD, *dM[2] = {dL + 2 * G, dL + 2 * G + G * CD},
+           *dV[2] = {dM[1] + G * CD, dM[1] + 2 * G * CD}, *dW = dV[1] + G * CD, *dW0 = dW + G * C, *dMean0 = dW0 + C, *dCov0 = dMean0 + CD, *dPW = dCov0 + CD;
+    int32_t *dStat = (int32_t *)(dPW + C);
+    hipStream_t st = (hipStream_t)srv.stream();
+    auto up = [&](double *dst, const std::vector<double> &src) {
+        hipcheck(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, st), "adaptModelBatch: upload");
+    };
+    up(dW0, aprioriModel.weights_c()); up(dMean0, aprioriModel.means_c()); up(dCov0, aprioriModel.covs_c()); up(dPW, prior.weights_c());
+    bool same = true;
+    for (size_t i = 1; i < G && same; ++i)
+        same = clientMixtures[i].weights_c() == clientMixtures[0].weights_c() && clientMixtures[i].means_c() == clientMixtures[0].means_c() &&
+               clientMixtures[i].covInvs() == clientMixtures[0].covInvs() && clientMixtures[i].covs_c() == clientMixtures[0].covs_c();
+    long curStride = 0;
+    if (same) {
+        up(dM[0], clientMixtures[0].means_c()); up(dV[0], clientMixtures[0].covs_c());
+        srv.sync();
+        srv.check(gmmiv_gmm_batch_load(batch.h, clientMixtures[0].weights_c().data(), 0, dM[0], 0, clientMixtures[0].covInvs().data(), 0));
+    } else {
+        std::vector<double> w(G * C), iv(G * CD), m(G * CD), cv(G * CD);
+        for (size_t i = 0; i < G; ++i) {
+            memcpy(&w[i * C], clientMixtures[i].weights_c().data(), C * sizeof(double));
+            memcpy(&m[i * CD], clientMixtures[i].means_c().data(), CD * sizeof(double));
+            memcpy(&iv[i * CD], clientMixtures[i].covInvs().data(), CD * sizeof(double));
+            memcpy(&cv[i * CD], clientMixtures[i].covs_c().data(), CD * sizeof(double));
+        }
+        up(dM[0], m); up(dV[0], cv);
+        srv.sync();
+        srv.check(gmmiv_gmm_batch_load(batch.h, w.data(), (int64_t)C, dM[0], (int64_t)CD, iv.data(), (int64_t)CD));
+        curStride = (long)CD;
+    }
+    std::vector<int64_t> segBegin(G + 1);
+    std::vector<int32_t> segModel(G);
+    for (size_t i = 0; i < G; ++i) segModel[i] = (int32_t)i;
+    const double *wNext = perClientW ? dW : dPW;
+    const int64_t wStride = perClientW ? (int64_t)C : 0;
+    for (unsigned long it = 0; it < nIt; ++it) {
+        SegCluster all;
+        segBegin[0] = 0;
+        for (size_t i = 0; i < G; ++i) {
+            all.insert(all.end(), bagged[i][it].begin(), bagged[i][it].end());
+            segBegin[i + 1] = segBegin[i] + (int64_t)totalFrame(bagged[i][it]);
+        }
+        unsigned long n = 0;
+        const float *x = fs.select(all, n);
+        FiniteScope fin(srv, fs);
+        srv.check(gmmiv_em_stats_models(srv.ctx(), batch.h, x, GMMIV_F32, (int64_t)n, (int64_t)D, segBegin.data(), segModel.data(), (int64_t)G, dN, dF, dS, dL));
+        double *out = dM[(it + 1) & 1], *outV = dV[(it + 1) & 1];
+        srv.check(gmmiv_map_adapt_models_full(srv.ctx(), (int)G, (int)C, (int)D, dN, dF, dS, dL + 1, 2, dW0, dMean0, dCov0, dM[it & 1], curStride, dV[it & 1], curStride,
+                                              method, mapCfg.meanAdapt ? 1 : 0, mapCfg.varAdapt ? 1 : 0, mapCfg.weightAdapt ? 1 : 0, mapCfg.meanReg, mapCfg.varReg,
+                                              mapCfg.weightReg, mapCfg.meanAlpha, out, outV, perClientW ? dW : nullptr, dStat + it * G));
+        if (mapCfg.normalizeModel)
+            srv.check(gmmiv_normalize_models(srv.ctx(), (int)G, (int)C, (int)D, wNext, wStride, out, outV,
+                                             mapCfg.normalizeModelMeanOnly ? (int)mapCfg.normalizeModelNbIt : 1, mapCfg.normalizeModelMeanOnly ? 1 : 0));
+        if (it + 1 < nIt) srv.check(gmmiv_gmm_batch_load_cov(batch.h, wNext, wStride, out, (int64_t)CD, outV, (int64_t)CD));
+        curStride = (long)CD;
+    }
+    std::vector<double> means(G * CD), covs(covChanges ? G * CD : 0), weights(perClientW ? G * C : 0);
+    std::vector<int32_t> stat(nStat);
+    hipcheck(hipMemcpyAsync(means.data(), dM[nIt & 1], G * CD * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    if (covChanges) hipcheck(hipMemcpyAsync(covs.data(), dV[nIt & 1], G * CD * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    if (perClientW) hipcheck(hipMemcpyAsync(weights.data(), dW, G * C * sizeof(double), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    hipcheck(hipMemcpyAsync(stat.data(), dStat, nStat * sizeof(int32_t), hipMemcpyDeviceToHost, st), "adaptModelBatch: download");
+    srv.sync();
+    for (size_t i = 0, told = 0; i < G && !told; ++i)
+        for (unsigned long it = 0; it < nIt && !told; ++it)
+            if (stat[it * G + i]) {
+                fprintf(stderr, "[liagpu] adaptModelBatch: client %zu, iteration %lu: %d variances are not positive and finite\n", i, it, (int)stat[it * G + i]);
+                told = 1;
+            }
+    for (size_t i = 0; i < G; ++i) {
+        MixtureGD m = prior; // what computeMAP leaves in the tables it does not adapt
+        memcpy(m.means().data(), &means[i * CD], CD * sizeof(double));
+        if (perClientW) memcpy(m.weights().data(), &weights[i * C], C * sizeof(double));
+        if (covChanges) {
+            memcpy(m.covs().data(), &covs[i * CD], CD * sizeof(double));
+            m.computeAll();
+        }
+        clientMixtures[i] = m;
+    }
+}
+
 void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerClient, const MixtureGD &aprioriModel,
                      std::vector<MixtureGD> &clientMixtures, const MAPCfg &mapCfg, std::vector<MatrixD> *mllrW)
 {
@@ -1453,7 +1559,8 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
         for (size_t i = 0; i < G; ++i) adaptModelW(fs, selectedPerClient[i], aprioriModel, clientMixtures[i], mapCfg, mllr && mllrW ? &(*mllrW)[i] : nullptr);
     };
     // MLLR ignores varAdapt; its device entry serves vectSize <= 62, and the matrix file is the per-client loop's business
-    bool batched = mllr ? !mapCfg.normalizeModel && D <= 62 && mapCfg.mllrMatrixFile.empty() : !mapCfg.varAdapt && !mapCfg.normalizeModel;
+    const bool batchVar = !mllr && mapCfg.batchVariances; // opt-in: varAdapt / normalizeModel / the ML estimate on the device too
+    bool batched = mllr ? !mapCfg.normalizeModel && D <= 62 && mapCfg.mllrMatrixFile.empty() : batchVar || (!mapCfg.varAdapt && !mapCfg.normalizeModel);
     for (size_t i = 0; i < G && batched; ++i) batched = clientMixtures[i].getDistribCount() == C && clientMixtures[i].getVectSize() == D;
     if (!batched) {
         perClientLoop();
@@ -1473,13 +1580,17 @@ void adaptModelBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedP
     // what computeMAP leaves in the tables this function does not adapt: the a-priori model's (after computeAll() for the two
     // occupation-dependent methods, which recomputes covInv = 1 / cov); an unknown method keeps the ML estimate -- weights N / count,
     // and variances, which need the second-order statistics: per-client loop
-    if (method == GMMIV_MAP_NONE && !mllr) {
+    if (method == GMMIV_MAP_NONE && !mllr && !batchVar) {
         perClientLoop();
         return;
     }
     MixtureGD prior = aprioriModel;
     if (mllr || method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED) prior.computeAll(); // computeMLLR: copyVar -> computeAll()
     const bool perClientW = mapCfg.weightAdapt && (method == GMMIV_MAP_OCC_DEP || method == GMMIV_MAP_MODEL_BASED);
+    if (batchVar && (mapCfg.varAdapt || mapCfg.normalizeModel || method == GMMIV_MAP_NONE)) {
+        adaptModelBatchVar(fs, bagged, aprioriModel, prior, clientMixtures, mapCfg, method);
+        return;
+    }
 
     GpuServer &srv = fs.server();
     const size_t CD = (size_t)C * D;

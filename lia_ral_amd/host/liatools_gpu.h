@@ -343,6 +343,9 @@ struct MAPCfg { // MAPCfg::MAPCfg, TrainTools.cpp:95-147
     double meanAlpha = 0.75;                                  // MAPAlphaMean: a-priori probability of the init model (MAPConst / MAPConst2)
     bool normalizeModel = false, normalizeModelMeanOnly = false; // :125-135, applied after every iteration's MAP step (:898)
     unsigned long normalizeModelNbIt = 1;
+    // adaptModelBatch only: keep varAdapt / normalizeModel / an unknown MAPAlgo's ML estimate on the device too (second-order statistics
+    // per client, gmmiv_em_stats_models + gmmiv_map_adapt_models_full + gmmiv_normalize_models).  Off: those run the per-client loop.
+    bool batchVariances = false;
     // MLLR only: when set, the transform W [D x (D+1)] is saved there (DT matrix) after every iteration.  The reference writes
     // "MLLR_matrix.mat" into the working directory unconditionally (TrainTools.cpp:892-893); a library does not.
     std::string mllrMatrixFile;
@@ -366,7 +369,10 @@ void adaptModel(FeatureBuffer &fs, const SegCluster &selectedSegments, const Mix
 // The same for many clients at once (the client loop of TrainTarget.cpp:150-270): client i = adaptModel(fs, selectedPerClient[i],
 // aprioriModel, clientMixtures[i], mapCfg) called client after client in that order -- same bagging draws, results to the last bits of
 // another summation order -- with ONE statistics pass per iteration for all clients (gmmiv_tv_stats_models, a model per client) and the
-// MAP step on the device (gmmiv_map_adapt_models).  varAdapt, normalizeModel and an unknown MAPAlgo run the per-client loop.
+// MAP step on the device (gmmiv_map_adapt_models).  varAdapt, normalizeModel and an unknown MAPAlgo run the per-client loop, unless
+// mapCfg.batchVariances is set: then they stay on the device as well (gmmiv_em_stats_models, gmmiv_map_adapt_models_full,
+// gmmiv_normalize_models, gmmiv_gmm_batch_load_cov per iteration); a client whose MAP step leaves a variance that is not positive and
+// finite gets its model as computed, as adaptModel gives it, and the first such client is named on stderr after the last iteration.
 // "MLLR": the same loop with gmmiv_mllr_adapt_models as the adaptation step (varAdapt is ignored, as computeMLLR ignores it;
 // normalizeModel, clients of another shape and vectSize > 62 run the per-client loop).  The statuses are read once, after the last
 // iteration: a client whose system failed throws an Exception naming the first such client, as the per-client loop would.

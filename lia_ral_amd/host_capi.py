@@ -200,8 +200,8 @@ def train_target(x, seg_begin, seg_len, world, nb_it=1, mean_reg=16.0, device=0)
     return wo, mo, co
 
 
-def _map_flags(mean, var, weight):
-    return int(mean) | (int(var) << 1) | (int(weight) << 2)
+def _map_flags(mean, var, weight, batch_variances=False):
+    return int(mean) | (int(var) << 1) | (int(weight) << 2) | (int(batch_variances) << 3)
 
 
 def train_target_ex(x, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, bagged_p=1.0, mean=True, var=False, weight=False,
@@ -222,10 +222,12 @@ def train_target_ex(x, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, b
 
 def train_target_batch(x, client_begin, seg_begin, seg_len, world, method="MAPOccDep", nb_it=1, bagged_p=1.0, mean=True, var=False, weight=False,
                        reg=(16.0, 16.0, 16.0), alpha_mean=0.75, normalize=False, normalize_mean_only=False, normalize_nb_it=1, device=0,
-                       return_mllr=False):
+                       return_mllr=False, batch_variances=False):
     """TrainTarget for many clients at once (adaptModelBatch): client i owns the segments client_begin[i] .. client_begin[i + 1] of the
     seg_begin / seg_len lists and starts from `world` -> (w [G, C], mean [G, C, D], cov [G, C, D]); row i is what train_target_ex gives
-    for client i when the clients are adapted one after the other in this order (var / normalize: it runs exactly that loop).
+    for client i when the clients are adapted one after the other in this order (var / normalize: it runs exactly that loop, unless
+    batch_variances=True -- MAPCfg::batchVariances -- which keeps those configurations on the device too: second-order statistics per client,
+    the variance branch of computeMAP and normalizeMixture as kernels).
     method="MLLR": one global affine transform of the world means per client (computeMLLR); return_mllr=True appends the last
     iteration's transforms W [G, D, D + 1] to the result."""
     x = np.ascontiguousarray(x, np.float32)
@@ -241,8 +243,8 @@ def train_target_batch(x, client_begin, seg_begin, seg_len, world, method="MAPOc
     wo = np.empty((G, C)); mo = np.empty((G, C, D)); co = np.empty((G, C, D))
     Wm = np.zeros((G, D, D + 1)) if return_mllr else None
     _chk(lib.liagpu_train_target_batch_w(device, x.ctypes.data_as(_fp), ct.c_long(T), D, lp(cb), ct.c_long(G), lp(b), lp(l), C, _d(w), _d(m), _d(c),
-                                         method.encode(), nb_it, ct.c_double(bagged_p), _map_flags(mean, var, weight), _d(r), ct.c_double(alpha_mean), norm,
-                                         _d(wo), _d(mo), _d(co), _d(Wm)))
+                                         method.encode(), nb_it, ct.c_double(bagged_p), _map_flags(mean, var, weight, batch_variances), _d(r),
+                                         ct.c_double(alpha_mean), norm, _d(wo), _d(mo), _d(co), _d(Wm)))
     return (wo, mo, co, Wm) if return_mllr else (wo, mo, co)
 
 
