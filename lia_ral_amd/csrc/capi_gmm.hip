@@ -37,6 +37,134 @@ bool gmmiv_is_device_ptr(const void *p)
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
+// ---- helpers of the entry points below (count_unusable, run_lse, generic_gamma_gemm: declared in capi_gmm_util.h) ----
+static int check_model(gmmiv_ctx *c, const gmmiv_gmm *g)
+{
+    if (!c || !g) { gmmiv_set_error("NULL context or model"); return GMMIV_ERR_ARG; }
+    if (g->ctx != c) { gmmiv_set_error("model belongs to a different context"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    return GMMIV_OK;
+}
+
+// ---- degenerate inputs (include/gmmiv.h) ----
+// Kind (1) frames are not removed from a call: every kernel reads such a value as GMMIV_UNUSABLE_READ_AS (devutil.h, feat_sane), which makes the
+// frame a zero-likelihood frame on the device.  What is left for the host side is the COUNT ("screened_frames"): one pass over x that
+// flags the frames and adds their number to a device counter -- enqueued, never read back here (option "assume_finite" 1 skips it;
+// results do not depend on it).
+int count_unusable(gmmiv_ctx *c, const XView &xv, int dt, int64_t T, int D)
+{
+    if (c->assume_finite || T <= 0) return GMMIV_OK;
+    void *p;
+    int rc;
+    const size_t fbytes = ((size_t)T + 15) / 16 * 16;
+    if ((rc = c->scratch(WS_GFLAG, fbytes + 16, &p))) return rc;
+    unsigned char *flag = (unsigned char *)p;
+    GCHK(hipMemsetAsync(flag, 0, fbytes + 16, c->stream));
+    GCHK(gmmk_flag_frames(c->stream, dt == GMMIV_F64, xv.d, T, xv.ldx, D, flag, (int *)(flag + fbytes)));
+    GCHK(gmmk_count_flags(c->stream, flag, (long)T, c->d_screened));
+    return GMMIV_OK;
+}
+
+// ---- LLK ----
+// zero-likelihood frames of kind (2) among the n frames whose log-sums K1 has just left in `lse` -> the context's device counter
+static int count_dead(gmmiv_ctx *c, const double *lse, int64_t n) { return gmmk_count_dead(c->stream, lse, (long)n, c->d_zero_llk); }
+
+// DETERMINE_TOP_DISTRIBS by the any-shape kernel (k_topc_determine_big), frames in chunks whose logit rows fit 1 GiB of scratch
+static int topc_big(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, int ctop, int complete, double lo, double hi,
+                    int *idx, double *lk, double *nlk, double *nllk, double *nw, double *llk)
+{
+    if (T <= 0) return GMMIV_OK;
+    int64_t per = (int64_t)(((size_t)1 << 30) / ((size_t)g->Cp64 * sizeof(double))) / 4 * 4;
+    if (per < 4) per = 4;
+    if (per > T) per = (T + 3) / 4 * 4;
+    void *zs;
+    int rc = c->scratch(WS_Z, gmmk_topc_big_scratch_doubles((long)per, g->Cp64) * sizeof(double), &zs);
+    if (rc) return rc;
+    for (int64_t c0 = 0; c0 < T; c0 += per) { // one timed launch per chunk, like the other chunked paths (kernel_launches counts them)
+        const int64_t n = T - c0 < per ? T - c0 : per;
+        c->t_begin("k_topc_determine", c0 == 0);
+        int krc = gmmk_topc_determine_big(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), (long)n, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc,
+                                          g->w, ctop, complete, lo, hi, idx ? idx + (size_t)c0 * ctop : nullptr, lk ? lk + (size_t)c0 * ctop : nullptr,
+                                          nlk ? nlk + c0 : nullptr, nllk ? nllk + c0 : nullptr, nw ? nw + c0 : nullptr, llk ? llk + c0 : nullptr,
+                                          (double *)zs);
+        c->t_end();
+        if (krc == -1) { gmmiv_set_error("vectSize %d exceeds the generic kernels' bound", g->D); return GMMIV_ERR_UNSUPPORTED; }
+        if (krc == -2) { gmmiv_set_error("topDistribsCount %d outside 1 .. mixtureDistribCount %d", ctop, g->C); return GMMIV_ERR_ARG; }
+        GCHK(krc);
+    }
+    return GMMIV_OK;
+}
+
+int run_lse(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, double **lse_out)
+{
+    void *lse;
+    int rc = c->scratch(WS_LSE, (size_t)(T > 0 ? T : 1) * sizeof(double), &lse);
+    if (rc) return rc;
+    if (g->KS == GMMK_KS_GENERIC) { // no MFMA instantiation: log sum_c w_c lk_c in the direct form (the top-1 pass of the any-shape kernel, COMPLETE)
+        if ((rc = topc_big(c, g, xv, dt, T, 1, 1, -INFINITY, INFINITY, nullptr, nullptr, nullptr, nullptr, nullptr, (double *)lse))) return rc;
+        GCHK(count_dead(c, (const double *)lse, T));
+        *lse_out = (double *)lse;
+        return GMMIV_OK;
+    }
+    c->t_begin("k_llk_mfma");
+    GCHK(gmmk_llk(c->stream, g->KS, dt == GMMIV_F64, xv.d, T, xv.ldx, g->D, g->Pt, g->nct, (double *)lse, (int)(c->use_glds | (c->dbg << 8)), (int)c->wg_waves));
+    c->t_end();
+    GCHK(count_dead(c, (const double *)lse, T)); // every caller of run_lse is a statistics / likelihood entry point
+    *lse_out = (double *)lse;
+    return GMMIV_OK;
+}
+
+// ---- stored-likelihood path (k_llk_mfma<WZ> + a reader kernel; the scratch: gmmiv_z_reserve) ----
+// frames per chunk that fit the logit scratch budget (multiple of 64), 0 when the path does not apply
+static int64_t z_chunk_frames(gmmiv_ctx *c, const gmmiv_gmm *g)
+{
+    if (!c->stats_z || g->KS > 15 || c->wg_waves != 8) return 0;
+    int64_t tc = gmmiv_z_budget_frames(c, g->nct, 16); // 16 and the rounding below are pinned by results: they fix the summation order
+    // whole rounds of the log-likelihood kernel: 2 resident workgroups per CU x 256 frames
+    const int64_t round = (int64_t)c->n_cu * 2 * 256;
+    tc = tc >= round ? tc / round * round : tc / 64 * 64;
+    return tc >= 4096 ? tc : 0;
+}
+
+// k_llk_mfma<WZ> on frames [c0, c0 + n): their log-sums into lse[0 .. n), the stored likelihoods into z.  Counting the
+// zero-likelihood frames afterwards (count_dead) is the caller's decision.
+static int llk_z_run(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t c0, int64_t n, double *lse, const gmmk_zview &z, bool first)
+{
+    c->t_begin("k_llk_mfma", first);
+    GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, lse,
+                    (int)(c->use_glds | ((c->dbg & 15) << 8)), z));
+    c->t_end();
+    return GMMIV_OK;
+}
+
+// ---- statistics of a model WITHOUT an MFMA instantiation (vectSize > 80): gamma[t][c] = exp(z_tc - lse_t) by the direct-form VALU
+// kernel (k_posteriors), then S[C x NC] (+)= gamma^T [x | 1 | x^2 | 0] on the fp64 GEMM (k_dgemm), frames in chunks whose posterior
+// block fits 512 MiB.  S: sum_t g x | sum_t g | sum_t g x^2.  The same sums as MixtureStat::computeAndAccumulateEM
+// (AccumulateStat.cpp:103-152) / TVAcc::computeAndAccumulateTVStat (AccumulateTVStat.cpp:332-348), any vectSize.
+int generic_gamma_gemm(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t t0, int64_t n, const double *lse, bool sq, int NC,
+                       double *S)
+{
+    int rc;
+    int64_t per = (int64_t)(((size_t)512 << 20) / ((size_t)g->C * sizeof(double)));
+    if (per < 64) per = 64;
+    per = per / 2 * 2; // an even K keeps the aligned GEMM instantiation
+    void *gam, *xa;
+    const int64_t first = n < per ? n : per;
+    if ((rc = c->scratch(WS_Z, (size_t)(first > 0 ? first : 1) * g->C * sizeof(double), &gam))) return rc;
+    if ((rc = c->scratch(WS_INV, (size_t)(first > 0 ? first : 1) * NC * sizeof(double), &xa))) return rc;
+    if (n <= 0) { GCHK(hipMemsetAsync(S, 0, (size_t)g->C * NC * sizeof(double), c->stream)); return GMMIV_OK; }
+    for (int64_t b = 0; b < n; b += per) {
+        const int64_t m = n - b < per ? n - b : per;
+        c->t_begin("k_posteriors", b == 0);
+        GCHK(gmmk_posteriors(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, t0 + b), (long)m, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, lse + t0 + b,
+                             (double *)gam));
+        c->t_end();
+        GCHK(gmmk_build_xa(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, t0 + b), xv.ldx, g->D, (long)m, sq ? 1 : 0, NC, (double *)xa));
+        GCHK(tvk_dgemm(c->stream, true, false, g->C, NC, (int)m, 1.0, (const double *)gam, g->C, 0, (const double *)xa, NC, 0, b == 0 ? 0.0 : 1.0, S, NC, 0, 1));
+    }
+    return GMMIV_OK;
+}
+
 extern "C" {
 
 const char *gmmiv_last_error(void) { return g_err; }
@@ -275,39 +403,6 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g)
     delete g;
 }
 
-// ---- helpers -----------------------------------------------------------------------------
-static size_t esize(int dt) { return dt == GMMIV_F64 ? 8 : 4; }
-
-// ---- degenerate inputs (include/gmmiv.h): frames with a non-finite / absurd feature value never reach the kernels ----------
-// Screening = one HBM pass over x per call (skipped with the option "assume_finite"); in the -- rare -- call that has unusable
-// frames, the usable ones are compacted (k_gather_runs), the entry point runs on them and the per-frame outputs are expanded
-// back with the values the rule gives a zero-likelihood frame.  The hot kernels themselves carry no per-element checks.
-// Kind (1) frames are not removed from a call: every kernel reads such a value as GMMIV_UNUSABLE_READ_AS (devutil.h, feat_sane), which makes the
-// frame a zero-likelihood frame on the device.  What is left for the host side is the COUNT ("screened_frames"): one pass over x that
-// flags the frames and adds their number to a device counter -- enqueued, never read back here (option "assume_finite" 1 skips it;
-// results do not depend on it).
-static int count_unusable(gmmiv_ctx *c, const XView &xv, int dt, int64_t T, int D)
-{
-    if (c->assume_finite || T <= 0) return GMMIV_OK;
-    void *p;
-    int rc;
-    const size_t fbytes = ((size_t)T + 15) / 16 * 16;
-    if ((rc = c->scratch(WS_GFLAG, fbytes + 16, &p))) return rc;
-    unsigned char *flag = (unsigned char *)p;
-    GCHK(hipMemsetAsync(flag, 0, fbytes + 16, c->stream));
-    GCHK(gmmk_flag_frames(c->stream, dt == GMMIV_F64, xv.d, T, xv.ldx, D, flag, (int *)(flag + fbytes)));
-    GCHK(gmmk_count_flags(c->stream, flag, (long)T, c->d_screened));
-    return GMMIV_OK;
-}
-
-static int check_model(gmmiv_ctx *c, const gmmiv_gmm *g)
-{
-    if (!c || !g) { gmmiv_set_error("NULL context or model"); return GMMIV_ERR_ARG; }
-    if (g->ctx != c) { gmmiv_set_error("model belongs to a different context"); return GMMIV_ERR_ARG; }
-    GBIND(c);
-    return GMMIV_OK;
-}
-
 // ---- frame moments -------------------------------------------------------------------------
 int gmmiv_frame_moments(gmmiv_ctx *c, const void *x, int dt, int64_t T, int64_t ldx, int D, double *acc)
 {
@@ -431,55 +526,6 @@ int gmmiv_segment_means(gmmiv_ctx *c, const double *v, int64_t ld, int nrows, co
 }
 
 // ---- LLK ---------------------------------------------------------------------------------
-// zero-likelihood frames of kind (2) among the n frames whose log-sums K1 has just left in `lse` -> the context's device counter
-static int count_dead(gmmiv_ctx *c, const double *lse, int64_t n) { return gmmk_count_dead(c->stream, lse, (long)n, c->d_zero_llk); }
-
-static const void *x_at(const XView &xv, int dt, int64_t frame);
-// DETERMINE_TOP_DISTRIBS by the any-shape kernel (k_topc_determine_big), frames in chunks whose logit rows fit 1 GiB of scratch
-static int topc_big(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, int ctop, int complete, double lo, double hi,
-                    int *idx, double *lk, double *nlk, double *nllk, double *nw, double *llk)
-{
-    if (T <= 0) return GMMIV_OK;
-    int64_t per = (int64_t)(((size_t)1 << 30) / ((size_t)g->Cp64 * sizeof(double))) / 4 * 4;
-    if (per < 4) per = 4;
-    if (per > T) per = (T + 3) / 4 * 4;
-    void *zs;
-    int rc = c->scratch(WS_Z, gmmk_topc_big_scratch_doubles((long)per, g->Cp64) * sizeof(double), &zs);
-    if (rc) return rc;
-    for (int64_t c0 = 0; c0 < T; c0 += per) { // one timed launch per chunk, like the other chunked paths (kernel_launches counts them)
-        const int64_t n = T - c0 < per ? T - c0 : per;
-        c->t_begin("k_topc_determine", c0 == 0);
-        int krc = gmmk_topc_determine_big(c->stream, dt == GMMIV_F64, x_at(xv, dt, c0), (long)n, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc,
-                                          g->w, ctop, complete, lo, hi, idx ? idx + (size_t)c0 * ctop : nullptr, lk ? lk + (size_t)c0 * ctop : nullptr,
-                                          nlk ? nlk + c0 : nullptr, nllk ? nllk + c0 : nullptr, nw ? nw + c0 : nullptr, llk ? llk + c0 : nullptr,
-                                          (double *)zs);
-        c->t_end();
-        if (krc == -1) { gmmiv_set_error("vectSize %d exceeds the generic kernels' bound", g->D); return GMMIV_ERR_UNSUPPORTED; }
-        if (krc == -2) { gmmiv_set_error("topDistribsCount %d outside 1 .. mixtureDistribCount %d", ctop, g->C); return GMMIV_ERR_ARG; }
-        GCHK(krc);
-    }
-    return GMMIV_OK;
-}
-
-static int run_lse(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, double **lse_out)
-{
-    void *lse;
-    int rc = c->scratch(WS_LSE, (size_t)(T > 0 ? T : 1) * sizeof(double), &lse);
-    if (rc) return rc;
-    if (g->KS == GMMK_KS_GENERIC) { // no MFMA instantiation: log sum_c w_c lk_c in the direct form (the top-1 pass of the any-shape kernel, COMPLETE)
-        if ((rc = topc_big(c, g, xv, dt, T, 1, 1, -INFINITY, INFINITY, nullptr, nullptr, nullptr, nullptr, nullptr, (double *)lse))) return rc;
-        GCHK(count_dead(c, (const double *)lse, T));
-        *lse_out = (double *)lse;
-        return GMMIV_OK;
-    }
-    c->t_begin("k_llk_mfma");
-    GCHK(gmmk_llk(c->stream, g->KS, dt == GMMIV_F64, xv.d, T, xv.ldx, g->D, g->Pt, g->nct, (double *)lse, (int)(c->use_glds | (c->dbg << 8)), (int)c->wg_waves));
-    c->t_end();
-    GCHK(count_dead(c, (const double *)lse, T)); // every caller of run_lse is a statistics / likelihood entry point
-    *lse_out = (double *)lse;
-    return GMMIV_OK;
-}
-
 int gmmiv_llk(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int64_t T, int64_t ldx, double min_llk,
               double max_llk, double *llk_out, double *sums)
 {
@@ -502,11 +548,6 @@ int gmmiv_llk(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int64_t T
     if ((rc = o_llk.finish())) return rc;
     return o_sum.finish();
 }
-
-// stored-likelihood helpers (defined with the EM path below)
-static long z_tile_blocks(int64_t n);
-static int64_t z_chunk_frames(gmmiv_ctx *c, const gmmiv_gmm *g);
-static const void *x_at(const XView &xv, int dt, int64_t frame);
 
 int gmmiv_llk_determine_top(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int64_t T, int64_t ldx, int ctop,
                             int mode, double min_llk, double max_llk, int32_t *idx, double *lk, double *nontop_lk,
@@ -562,7 +603,7 @@ int gmmiv_llk_determine_top(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int
             auto run_chunk = [&](int64_t c0, int64_t n) -> int {
                 GCHK(hipMemsetAsync(flg, 0, 64, c->stream));
                 c->t_begin("k_llk_mfma", c0 == 0);
-                krc = gmmk_llk_topc(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (int)c->use_glds,
+                krc = gmmk_llk_topc(c->stream, g->KS, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (int)c->use_glds,
                                     ctop, (double *)cand, (int *)cnt, (double *)th, (double *)sl, efin);
                 c->t_end();
                 if (krc) return GMMIV_OK;
@@ -570,7 +611,7 @@ int gmmiv_llk_determine_top(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int
                 double *olk = o_lk.d ? o_lk.d + (size_t)c0 * ctop : nullptr, *onlk = o_nlk.d ? o_nlk.d + c0 : nullptr;
                 double *onllk = o_nllk.d ? o_nllk.d + c0 : nullptr, *onw = o_nw.d ? o_nw.d + c0 : nullptr, *ollk = o_llk.d ? o_llk.d + c0 : nullptr;
                 c->t_begin("k_topc_rank", c0 == 0);
-                krc = gmmk_topc_rank(c->stream, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->C, (const double *)cand, (const int *)cnt,
+                krc = gmmk_topc_rank(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), n, xv.ldx, g->D, g->C, (const double *)cand, (const int *)cnt,
                                      (const double *)th, (const double *)sl, efin, g->mean, g->iv, g->lwc, g->w, ctop, mode == GMMIV_TOP_COMPLETE,
                                      min_llk, max_llk, oi, olk, onlk, onllk, onw, ollk, (int *)flg, (long *)redo,
                                      stats | (c->topc_rank_direct ? 2 : 0) | (c->topc_rank2 ? 0 : 4), (long *)redo + nalloc);
@@ -591,11 +632,11 @@ int gmmiv_llk_determine_top(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int
                 // (k_topc_determine) on a gathered copy, results scattered back
                 void *gx, *t_idx, *t_d;
                 int rc2;
-                if ((rc2 = c->scratch(WS_PART, (size_t)nr * g->D * esize(dt), &gx))) return rc2;
+                if ((rc2 = c->scratch(WS_PART, (size_t)nr * g->D * gmmiv_esize(dt), &gx))) return rc2;
                 if ((rc2 = c->scratch(WS_T6, (size_t)nr * ctop * sizeof(int), &t_idx))) return rc2;
                 if ((rc2 = c->scratch(WS_T7, (size_t)nr * (ctop + 4) * sizeof(double), &t_d))) return rc2;
                 double *t_lk = (double *)t_d, *t_nlk = t_lk + (size_t)nr * ctop, *t_nllk = t_nlk + nr, *t_nw = t_nllk + nr, *t_llk = t_nw + nr;
-                GCHK(gmmk_gather_frames(c->stream, dt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, g->D, (const long *)redo, nr, gx));
+                GCHK(gmmk_gather_frames(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), xv.ldx, g->D, (const long *)redo, nr, gx));
                 c->t_begin("k_topc_determine", c0 == 0);
                 GCHK(gmmk_topc_determine(c->stream, dt == GMMIV_F64, gx, nr, g->D, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, g->w, ctop,
                                          mode == GMMIV_TOP_COMPLETE, min_llk, max_llk, (int *)t_idx, t_lk, t_nlk, t_nllk, t_nw, t_llk));
@@ -614,28 +655,20 @@ int gmmiv_llk_determine_top(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int
     }
     const int64_t Tc = (!done && c->topc_z) ? z_chunk_frames(c, g) : 0;
     if (Tc > 0 && T > 0 && ctop + 4 <= 64 && gmmk_topc_z_lds(g->nct, g->D)) {
-        const int64_t first = T < Tc ? T : Tc;
-        const long nfb = z_tile_blocks(first);
-        void *zb, *eit, *inv, *lse, *flg;
-        if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
-        if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-        if ((rc = c->scratch(WS_INV, (size_t)first * (sizeof(double) + sizeof(int)), &inv))) return rc;
-        if ((rc = c->scratch(WS_LSE, (size_t)first * sizeof(double), &lse))) return rc;
+        gmmk_zview z;
+        double *lse;
+        void *flg;
+        if ((rc = gmmiv_z_reserve(c, g->nct, T < Tc ? T : Tc, true, &z, &lse))) return rc;
         if ((rc = c->scratch(WS_FLAGS, 64, &flg))) return rc;
-        int *efin = (int *)((double *)inv + first);
         GCHK(hipMemsetAsync(flg, 0, sizeof(int), c->stream));
         for (int64_t c0 = 0; c0 < T; c0 += Tc) {
             const int64_t n = (T - c0) < Tc ? (T - c0) : Tc;
-            c->t_begin("k_llk_mfma", c0 == 0);
-            GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lse,
-                            (int)c->use_glds, (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-            c->t_end();
+            if ((rc = llk_z_run(c, g, xv, dt, c0, n, lse, z, c0 == 0))) return rc; // (this entry point does not count zero-likelihood frames)
             c->t_begin("k_topc_from_z", c0 == 0);
-            GCHK(gmmk_topc_from_z(c->stream, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->C, g->nct, (const double *)zb, nfb,
-                                  (const int *)eit, efin, g->mean, g->iv, g->lwc, g->w, ctop, mode == GMMIV_TOP_COMPLETE, min_llk,
-                                  max_llk, o_idx.d + (size_t)c0 * ctop, o_lk.d ? o_lk.d + (size_t)c0 * ctop : nullptr,
-                                  o_nlk.d ? o_nlk.d + c0 : nullptr, o_nllk.d ? o_nllk.d + c0 : nullptr, o_nw.d ? o_nw.d + c0 : nullptr,
-                                  o_llk.d ? o_llk.d + c0 : nullptr, (int *)flg));
+            GCHK(gmmk_topc_from_z(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), n, xv.ldx, g->D, g->C, g->nct, z, g->mean, g->iv, g->lwc, g->w,
+                                  ctop, mode == GMMIV_TOP_COMPLETE, min_llk, max_llk, o_idx.d + (size_t)c0 * ctop,
+                                  o_lk.d ? o_lk.d + (size_t)c0 * ctop : nullptr, o_nlk.d ? o_nlk.d + c0 : nullptr, o_nllk.d ? o_nllk.d + c0 : nullptr,
+                                  o_nw.d ? o_nw.d + c0 : nullptr, o_llk.d ? o_llk.d + c0 : nullptr, (int *)flg));
             c->t_end();
         }
         int hflag = 0;
@@ -815,24 +848,15 @@ int gmmiv_occ(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int64_t T
     // Fast path: logits on the matrix cores (k_llk_mfma<WZ>), posteriors = the stored scaled likelihoods rescaled and transposed
     const int64_t Tcz = c->topc_z ? z_chunk_frames(c, g) : 0;
     if (Tcz > 0 && T > 0) {
-        const int64_t first = T < Tcz ? T : Tcz;
-        const long nfb = z_tile_blocks(first);
-        void *zb, *eit, *inv, *lz;
-        if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
-        if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-        if ((rc = c->scratch(WS_INV, (size_t)first * (sizeof(double) + sizeof(int)), &inv))) return rc;
-        if ((rc = c->scratch(WS_LSE, (size_t)first * sizeof(double), &lz))) return rc;
-        int *efin = (int *)((double *)inv + first);
+        gmmk_zview z;
+        double *lz;
+        if ((rc = gmmiv_z_reserve(c, g->nct, T < Tcz ? T : Tcz, true, &z, &lz))) return rc;
         for (int64_t c0 = 0; c0 < T; c0 += Tcz) {
             const int64_t n = (T - c0) < Tcz ? (T - c0) : Tcz;
-            c->t_begin("k_llk_mfma", c0 == 0);
-            GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lz,
-                            (int)c->use_glds, (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-            c->t_end();
-            GCHK(count_dead(c, (const double *)lz, n));
+            if ((rc = llk_z_run(c, g, xv, dt, c0, n, lz, z, c0 == 0))) return rc;
+            GCHK(count_dead(c, lz, n));
             c->t_begin("k_post_from_z", c0 == 0);
-            GCHK(gmmk_post_from_z(c->stream, n, g->C, g->nct, (const double *)zb, nfb, (const int *)eit, (const double *)inv, efin,
-                                  o.d + (size_t)c0 * g->C));
+            GCHK(gmmk_post_from_z(c->stream, n, g->C, g->nct, z, o.d + (size_t)c0 * g->C));
             c->t_end();
         }
         return o.finish();
@@ -860,65 +884,6 @@ static int make_chunks(gmmiv_ctx *c, int64_t T, int nseg, long **dev)
     return GMMIV_OK;
 }
 
-// ---- stored-likelihood path (k_llk_mfma<WZ> + k_stats_z) ----------------------------------------
-// Blocks (2 KB) per Gaussian tile of the likelihood scratch for n frames: whole workgroups of the
-// log-likelihood kernel (256 frames), then padded so that the tile stride is an ODD number of 4 KB
-// granules.  A statistics workgroup reads 16 tiles at the same frame position at once; with a stride
-// that is a multiple of the HBM channel interleave (a large power of two) all 16 streams -- and those
-// of every other workgroup of the segment -- would sit on the same channel.
-static long z_tile_blocks(int64_t n)
-{
-    long nfb = 16 * ((n + 255) / 256);
-    if ((nfb / 2) % 2 == 0) nfb += 2;
-    return nfb;
-}
-
-// frames per chunk that fit the logit scratch budget (multiple of 64), 0 when the path does not apply
-static int64_t z_chunk_frames(gmmiv_ctx *c, const gmmiv_gmm *g)
-{
-    if (!c->stats_z || g->KS > 15 || c->wg_waves != 8) return 0;
-    // The chunk length fixes the segment bounds and with them the fp64 summation order of every reduction of this path, so
-    // it depends ONLY on the option and the device's TOTAL memory (the same on every rank of a node), never on what happens
-    // to be free: replicated M-steps stay bit-identical.  If the scratch then does not fit, scratch() fails loudly.
-    size_t budget = (size_t)(c->z_scratch_mb > 0 ? c->z_scratch_mb : 0) << 20;
-    if (c->total_mem && budget > c->total_mem / 4) budget = c->total_mem / 4;
-    const size_t per_frame = (size_t)g->nct * 16 * sizeof(double) + (size_t)g->nct * 2 + 16; // likelihoods + exponents
-    int64_t tc = (int64_t)(budget / per_frame / 1.2); // scratch() over-allocates by 1/8
-    // whole rounds of the log-likelihood kernel: 2 resident workgroups per CU x 256 frames
-    const int64_t round = (int64_t)c->n_cu * 2 * 256;
-    tc = tc >= round ? tc / round * round : tc / 64 * 64;
-    return tc >= 4096 ? tc : 0;
-}
-static const void *x_at(const XView &xv, int dt, int64_t frame) { return (const char *)xv.d + (size_t)frame * xv.ldx * esize(dt); }
-
-// ---- statistics of a model WITHOUT an MFMA instantiation (vectSize > 80): gamma[t][c] = exp(z_tc - lse_t) by the direct-form VALU
-// kernel (k_posteriors), then S[C x NC] (+)= gamma^T [x | 1 | x^2 | 0] on the fp64 GEMM (k_dgemm), frames in chunks whose posterior
-// block fits 512 MiB.  S: sum_t g x | sum_t g | sum_t g x^2.  The same sums as MixtureStat::computeAndAccumulateEM
-// (AccumulateStat.cpp:103-152) / TVAcc::computeAndAccumulateTVStat (AccumulateTVStat.cpp:332-348), any vectSize.
-static int generic_gamma_gemm(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t t0, int64_t n, const double *lse, bool sq, int NC,
-                              double *S)
-{
-    int rc;
-    int64_t per = (int64_t)(((size_t)512 << 20) / ((size_t)g->C * sizeof(double)));
-    if (per < 64) per = 64;
-    per = per / 2 * 2; // an even K keeps the aligned GEMM instantiation
-    void *gam, *xa;
-    const int64_t first = n < per ? n : per;
-    if ((rc = c->scratch(WS_Z, (size_t)(first > 0 ? first : 1) * g->C * sizeof(double), &gam))) return rc;
-    if ((rc = c->scratch(WS_INV, (size_t)(first > 0 ? first : 1) * NC * sizeof(double), &xa))) return rc;
-    if (n <= 0) { GCHK(hipMemsetAsync(S, 0, (size_t)g->C * NC * sizeof(double), c->stream)); return GMMIV_OK; }
-    for (int64_t b = 0; b < n; b += per) {
-        const int64_t m = n - b < per ? n - b : per;
-        c->t_begin("k_posteriors", b == 0);
-        GCHK(gmmk_posteriors(c->stream, dt == GMMIV_F64, x_at(xv, dt, t0 + b), (long)m, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, lse + t0 + b,
-                             (double *)gam));
-        c->t_end();
-        GCHK(gmmk_build_xa(c->stream, dt == GMMIV_F64, x_at(xv, dt, t0 + b), xv.ldx, g->D, (long)m, sq ? 1 : 0, NC, (double *)xa));
-        GCHK(tvk_dgemm(c->stream, true, false, g->C, NC, (int)m, 1.0, (const double *)gam, g->C, 0, (const double *)xa, NC, 0, b == 0 ? 0.0 : 1.0, S, NC, 0, 1));
-    }
-    return GMMIV_OK;
-}
-
 // EM statistics of frames [0, T) into the partial blocks part[nseg] (summed by the caller)
 static int em_stats_z(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, int64_t Tc, double weight,
                       double *lse, int *nseg_out, void **part_out)
@@ -935,7 +900,7 @@ static int em_stats_z(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt,
     const int64_t nchunk = (T + Tc - 1) / Tc;
     // segment bounds relative to the chunk start: one table for full chunks, one for the last chunk
     const int64_t lastn = T - (nchunk - 1) * Tc;
-    void *seg, *zb, *part, *eit, *inv;
+    void *seg, *part;
     if ((rc = c->scratch(WS_SEG, 2 * (size_t)(nseg + 1) * sizeof(long), &seg))) return rc;
     auto fill = [&](long *dst, int64_t n) { // dst[i] = min(i per, n): written on the device, the call does not wait for the stream
         const int64_t per = ((n + nseg - 1) / nseg + 63) / 64 * 64;
@@ -943,25 +908,18 @@ static int em_stats_z(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt,
     };
     GCHK(fill((long *)seg, first));
     GCHK(fill((long *)seg + nseg + 1, lastn));
-    const long nfb = c->dbg & 64 ? 16 * ((first + 255) / 256) : z_tile_blocks(first);
-    if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
-    if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-    if ((rc = c->scratch(WS_INV, (size_t)first * (sizeof(double) + sizeof(int)), &inv))) return rc;
-    int *efin = (int *)((double *)inv + first);
+    gmmk_zview z;
+    if ((rc = gmmiv_z_reserve(c, g->nct, first, !(c->dbg & 64), &z, nullptr))) return rc; // lse: the caller's, T frames
     const int RL = gmmk_rl_for_ks(g->KS);
     const size_t Cp = (size_t)g->nct * 16;
     if ((rc = c->scratch(WS_PART, (size_t)nseg * Cp * 2 * RL * sizeof(double), &part))) return rc;
     for (int64_t k = 0; k < nchunk; ++k) {
         const int64_t c0 = k * Tc, n = (k == nchunk - 1) ? lastn : Tc;
-        c->t_begin("k_llk_mfma", k == 0);
-        GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, lse + c0,
-                        (int)(c->use_glds | ((c->dbg & 15) << 8)), (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-        c->t_end();
+        if ((rc = llk_z_run(c, g, xv, dt, c0, n, lse + c0, z, k == 0))) return rc;
         GCHK(count_dead(c, lse + c0, n));
         c->t_begin("k_stats_z", k == 0);
-        GCHK(gmmk_stats_z(c->stream, g->KS, 1, dt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, (const double *)zb, nfb,
-                          (const int *)eit, (const double *)inv, efin, weight, (const long *)seg + (k == nchunk - 1 ? nseg + 1 : 0), nseg,
-                          (double *)part, nullptr, 0, k > 0, c->prune_thr()));
+        GCHK(gmmk_stats_z(c->stream, g->KS, 1, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, z, weight,
+                          (const long *)seg + (k == nchunk - 1 ? nseg + 1 : 0), nseg, (double *)part, nullptr, 0, k > 0, c->prune_thr()));
         c->t_end();
     }
     *nseg_out = nseg;
@@ -1133,16 +1091,12 @@ int gmmiv_tv_stats(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int6
             std::vector<long> rel;
             for (size_t k = 0; k + 1 < cu.size(); ++k)
                 for (int64_t u = cu[k]; u <= cu[k + 1]; ++u) rel.push_back((long)(utt_begin[u] - utt_begin[cu[k]]));
-            void *zb, *lsew, *eit, *inv;
             if ((rc = c->scratch(WS_SEG, rel.size() * sizeof(long), &seg))) return rc;
             GCHK(hipMemcpyAsync(seg, rel.data(), rel.size() * sizeof(long), hipMemcpyHostToDevice, c->stream));
             GCHK(hipStreamSynchronize(c->stream));
-            const long nfb = z_tile_blocks(maxn);
-            if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
-            if ((rc = c->scratch(WS_LSE, (size_t)(maxn > 0 ? maxn : 1) * sizeof(double), &lsew))) return rc;
-            if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-            if ((rc = c->scratch(WS_INV, (size_t)(maxn > 0 ? maxn : 1) * (sizeof(double) + sizeof(int)), &inv))) return rc;
-            int *efin = (int *)((double *)inv + (maxn > 0 ? maxn : 1));
+            gmmk_zview z;
+            double *lsew;
+            if ((rc = gmmiv_z_reserve(c, g->nct, maxn, true, &z, &lsew))) return rc;
             // A few utterances (on-line extraction: ONE) give the statistics kernel a few workgroups -- 8 per utterance, each walking all
             // its frames: 0.39 ms for 3000 frames.  Up to 16 utterances in one chunk are cut into about 32 pieces of whole 64-frame
             // tiles; the pieces are "utterances" of the kernel, written to scratch rows and summed back in piece order.
@@ -1172,15 +1126,11 @@ int gmmiv_tv_stats(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int6
                     GCHK(hipMemcpyAsync(prb, rbh.data(), rbh.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
                     GCHK(hipStreamSynchronize(c->stream)); // pb / rbh live on this stack frame
                     const int64_t c0 = utt_begin[0], n = utt_begin[U] - c0;
-                    c->t_begin("k_llk_mfma", true);
-                    GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lsew,
-                                    (int)(c->use_glds | ((c->dbg & 15) << 8)), (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-                    c->t_end();
-                    GCHK(count_dead(c, (const double *)lsew, n));
+                    if ((rc = llk_z_run(c, g, xv, dt, c0, n, lsew, z, true))) return rc;
+                    GCHK(count_dead(c, lsew, n));
                     c->t_begin("k_stats_z", true);
-                    GCHK(gmmk_stats_z(c->stream, g->KS, 0, dt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, (const double *)zb, nfb,
-                                      (const int *)eit, (const double *)inv, efin, 1.0, (const long *)pseg, np, (double *)tn, (double *)tf, 1, 0,
-                                      c->prune_thr()));
+                    GCHK(gmmk_stats_z(c->stream, g->KS, 0, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, z, 1.0, (const long *)pseg,
+                                      np, (double *)tn, (double *)tf, 1, 0, c->prune_thr()));
                     GCHK(gmmk_rows_sum_groups(c->stream, g->C, (int)U, (const int *)prb, (const double *)tn, o_n.d));
                     GCHK(gmmk_rows_sum_groups(c->stream, (long)SV, (int)U, (const int *)prb, (const double *)tf, o_f.d));
                     c->t_end();
@@ -1190,15 +1140,11 @@ int gmmiv_tv_stats(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int dt, int6
             }
             for (size_t k = 0; k + 1 < cu.size(); ++k) {
                 const int64_t u0 = cu[k], u1 = cu[k + 1], c0 = utt_begin[u0], n = utt_begin[u1] - c0;
-                c->t_begin("k_llk_mfma", k == 0);
-                GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lsew,
-                                (int)(c->use_glds | ((c->dbg & 15) << 8)), (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-                c->t_end();
-                GCHK(count_dead(c, (const double *)lsew, n));
+                if ((rc = llk_z_run(c, g, xv, dt, c0, n, lsew, z, k == 0))) return rc;
+                GCHK(count_dead(c, lsew, n));
                 c->t_begin("k_stats_z", k == 0);
-                GCHK(gmmk_stats_z(c->stream, g->KS, 0, dt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, (const double *)zb,
-                                  nfb, (const int *)eit, (const double *)inv, efin, 1.0, (const long *)seg + u0 + k, (int)(u1 - u0),
-                                  o_n.d + (size_t)u0 * g->C, o_f.d + (size_t)u0 * SV, 1, 0, c->prune_thr()));
+                GCHK(gmmk_stats_z(c->stream, g->KS, 0, dt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), xv.ldx, g->D, g->C, g->nct, z, 1.0,
+                                  (const long *)seg + u0 + k, (int)(u1 - u0), o_n.d + (size_t)u0 * g->C, o_f.d + (size_t)u0 * SV, 1, 0, c->prune_thr()));
                 c->t_end();
             }
             if ((rc = o_n.finish())) return rc;
@@ -1277,8 +1223,8 @@ static int feat_check(const char *who, const void *x, int xdt, int64_t T, int64_
     if (T < 0 || ldx < D || ldo < D) { gmmiv_set_error("%s: T < 0 or a row stride below vectSize %d", who, D); return GMMIV_ERR_ARG; }
     if (T == 0) return GMMIV_OK;
     if (!x || !out) { gmmiv_set_error("%s: x or out == NULL", who); return GMMIV_ERR_ARG; }
-    const uintptr_t xb = (uintptr_t)x, xe = xb + ((size_t)(T - 1) * ldx + D) * esize(xdt);
-    const uintptr_t ob = (uintptr_t)out, oe = ob + ((size_t)(T - 1) * ldo + D) * esize(odt);
+    const uintptr_t xb = (uintptr_t)x, xe = xb + ((size_t)(T - 1) * ldx + D) * gmmiv_esize(xdt);
+    const uintptr_t ob = (uintptr_t)out, oe = ob + ((size_t)(T - 1) * ldo + D) * gmmiv_esize(odt);
     const bool in_place = x == out && xdt == odt && ldx == ldo;
     if (!in_place && xb < oe && ob < xe) { gmmiv_set_error("%s: out overlaps x (only out == x with the same dtype and stride is allowed)", who); return GMMIV_ERR_ARG; }
     return GMMIV_OK;
@@ -1294,16 +1240,16 @@ struct FeatOut {
     {
         c = ctx; T = T_; D = D_; dt = odt;
         if (T == 0 || gmmiv_is_device_ptr(out)) { d = out; ld = ldo; return GMMIV_OK; }
-        int rc = c->scratch(WS_FEAT_OUT, (size_t)T * D * esize(odt), &d);
+        int rc = c->scratch(WS_FEAT_OUT, (size_t)T * D * gmmiv_esize(odt), &d);
         if (rc) return rc;
         host = out; hld = ldo; ld = D;
         return GMMIV_OK;
     }
-    void *at(int64_t frame) const { return (char *)d + (size_t)frame * ld * esize(dt); }
+    void *at(int64_t frame) const { return (char *)d + (size_t)frame * ld * gmmiv_esize(dt); }
     int finish()
     {
         if (host) {
-            GCHK(hipMemcpy2DAsync(host, hld * esize(dt), d, D * esize(dt), D * esize(dt), T, hipMemcpyDeviceToHost, c->stream));
+            GCHK(hipMemcpy2DAsync(host, hld * gmmiv_esize(dt), d, D * gmmiv_esize(dt), D * gmmiv_esize(dt), T, hipMemcpyDeviceToHost, c->stream));
             GCHK(hipStreamSynchronize(c->stream));
         }
         return GMMIV_OK;
@@ -1331,26 +1277,19 @@ int gmmiv_feat_compensate(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int d
     // contracts the posteriors against the offsets on the matrix cores and writes D values per frame -- no posterior array
     const int64_t Tcz = g->D <= 64 ? z_chunk_frames(c, g) : 0;
     if (Tcz > 0) {
-        const int64_t first = T < Tcz ? T : Tcz;
-        const long nfb = z_tile_blocks(first);
-        void *zb, *eit, *inv, *lz, *offp;
-        if ((rc = c->scratch(WS_Z, (size_t)g->nct * nfb * 2048, &zb))) return rc;
-        if ((rc = c->scratch(WS_EIT, (size_t)(g->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-        if ((rc = c->scratch(WS_INV, (size_t)first * (sizeof(double) + sizeof(int)), &inv))) return rc;
-        if ((rc = c->scratch(WS_LSE, (size_t)first * sizeof(double), &lz))) return rc;
+        gmmk_zview z;
+        double *lz;
+        void *offp;
+        if ((rc = gmmiv_z_reserve(c, g->nct, T < Tcz ? T : Tcz, true, &z, &lz))) return rc;
         if ((rc = c->scratch(WS_FEAT_OFF, gmmk_feat_offset_doubles(g->nct, g->D) * sizeof(double), &offp))) return rc;
-        int *efin = (int *)((double *)inv + first);
         GCHK(gmmk_feat_pack_offset(c->stream, i_off.d, g->C, g->D, g->nct, (double *)offp));
         for (int64_t c0 = 0; c0 < T; c0 += Tcz) {
             const int64_t n = (T - c0) < Tcz ? (T - c0) : Tcz;
-            c->t_begin("k_llk_mfma", c0 == 0);
-            GCHK(gmmk_llk_z(c->stream, g->KS, dt == GMMIV_F64, x_at(xv, dt, c0), n, xv.ldx, g->D, g->Pt, g->nct, (double *)lz,
-                            (int)c->use_glds, (double *)zb, nfb, (int *)eit, (double *)inv, efin));
-            c->t_end();
-            GCHK(count_dead(c, (const double *)lz, n));
+            if ((rc = llk_z_run(c, g, xv, dt, c0, n, lz, z, c0 == 0))) return rc;
+            GCHK(count_dead(c, lz, n));
             c->t_begin("k_feat_comp", c0 == 0);
-            GCHK(gmmk_feat_comp(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, x_at(xv, dt, c0), xv.ldx, n, g->D, g->nct, (const double *)zb, nfb,
-                                (const int *)eit, (const double *)inv, efin, (const double *)offp, o.at(c0), o.ld));
+            GCHK(gmmk_feat_comp(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, gmmiv_x_at(xv, dt, c0), xv.ldx, n, g->D, g->nct, z, (const double *)offp,
+                                o.at(c0), o.ld));
             c->t_end();
         }
         return o.finish();
@@ -1368,12 +1307,12 @@ int gmmiv_feat_compensate(gmmiv_ctx *c, const gmmiv_gmm *g, const void *x, int d
     for (int64_t b = 0; b < T; b += per) {
         const int64_t m = T - b < per ? T - b : per;
         c->t_begin("k_posteriors", b == 0);
-        GCHK(gmmk_posteriors(c->stream, dt == GMMIV_F64, x_at(xv, dt, b), (long)m, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, lse + b,
+        GCHK(gmmk_posteriors(c->stream, dt == GMMIV_F64, gmmiv_x_at(xv, dt, b), (long)m, xv.ldx, g->D, g->C, g->Cp64, g->meanT, g->ivT, g->lwc, lse + b,
                              (double *)gam));
         c->t_end();
         GCHK(tvk_dgemm(c->stream, false, false, (int)m, g->D, g->C, 1.0, (const double *)gam, g->C, 0, i_off.d, g->D, 0, 0.0, (double *)pm, g->D, 0, 1));
         c->t_begin("k_feat_sub", b == 0);
-        GCHK(gmmk_feat_sub(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, x_at(xv, dt, b), xv.ldx, (long)m, g->D, (const double *)pm, lse + b, o.at(b), o.ld));
+        GCHK(gmmk_feat_sub(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, gmmiv_x_at(xv, dt, b), xv.ldx, (long)m, g->D, (const double *)pm, lse + b, o.at(b), o.ld));
         c->t_end();
     }
     return o.finish();
@@ -1457,8 +1396,8 @@ static int norm_check_overlap(const char *who, const void *x, int xdt, int64_t l
 {
     const bool in_place = x == out && xdt == odt && ldx == ldo;
     if (in_place || hi <= lo) return GMMIV_OK;
-    const uintptr_t xb = (uintptr_t)x + (size_t)lo * ldx * esize(xdt), xe = (uintptr_t)x + ((size_t)(hi - 1) * ldx + D) * esize(xdt);
-    const uintptr_t ob = (uintptr_t)out + (size_t)lo * ldo * esize(odt), oe = (uintptr_t)out + ((size_t)(hi - 1) * ldo + D) * esize(odt);
+    const uintptr_t xb = (uintptr_t)x + (size_t)lo * ldx * gmmiv_esize(xdt), xe = (uintptr_t)x + ((size_t)(hi - 1) * ldx + D) * gmmiv_esize(xdt);
+    const uintptr_t ob = (uintptr_t)out + (size_t)lo * ldo * gmmiv_esize(odt), oe = (uintptr_t)out + ((size_t)(hi - 1) * ldo + D) * gmmiv_esize(odt);
     if (xb < oe && ob < xe) { gmmiv_set_error("%s: out overlaps x (only out == x with the same dtype and stride is allowed)", who); return GMMIV_ERR_ARG; }
     return GMMIV_OK;
 }
@@ -1562,7 +1501,7 @@ int gmmiv_feat_norm_online(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int
         void *base = nullptr;
         size_t size = 0;
         if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)x) != hipSuccess) { (void)hipGetLastError(); gmmiv_set_error("feat_norm_online: the allocation of x is unknown to the runtime; pass file_begin as a host array"); return GMMIV_ERR_ARG; }
-        frames = (int64_t)(((uintptr_t)base + size - (uintptr_t)x) / ((size_t)ldx * esize(dt))) + 1;
+        frames = (int64_t)(((uintptr_t)base + size - (uintptr_t)x) / ((size_t)ldx * gmmiv_esize(dt))) + 1;
     }
     const long L = (long)(look_ahead < window ? look_ahead : window);
     const size_t units = gmmk_online_units((long)nfiles, (long)frames);
@@ -1577,15 +1516,6 @@ int gmmiv_feat_norm_online(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int
     c->t_end();
     if (host_tab) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
     return GMMIV_OK;
-}
-
-// ---- helpers shared with capi_models.hip (capi_gmm_util.h) ---------------------------------------------------------------------
-int gmmiv_i_count_unusable(gmmiv_ctx *c, const XView &xv, int dt, int64_t T, int D) { return count_unusable(c, xv, dt, T, D); }
-int gmmiv_i_run_lse(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, double **lse_out) { return run_lse(c, g, xv, dt, T, lse_out); }
-int gmmiv_i_generic_gamma_gemm(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t t0, int64_t n, const double *lse, bool sq, int NC,
-                               double *S)
-{
-    return generic_gamma_gemm(c, g, xv, dt, t0, n, lse, sq, NC, S);
 }
 
 } // extern "C"

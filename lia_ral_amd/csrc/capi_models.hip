@@ -269,24 +269,13 @@ static int models_per_chunk(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
     return n < 1 ? 1 : (n > 0x7fff ? 0x7fff : (int)n);
 }
 
-// frames per chunk of the stored-likelihood path (multiple of 256), 0 when it does not apply.  Like z_chunk_frames of capi_gmm.hip it
-// depends on the option, the model shape and the device's TOTAL memory only; unlike it, it goes down to one tile: a call of short
-// segments is served with any scratch that holds its longest segment
+// frames per chunk of the stored-likelihood path (multiple of 256), 0 when it does not apply.  The budget of z_chunk_frames
+// (capi_gmm.hip); unlike it, it goes down to one tile: a call of short segments is served with any scratch that holds its longest
+// segment.  24 (lse, 1 / S, Efin) and the rounding are pinned by results: they fix the summation order.
 static int64_t models_chunk_frames(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
 {
     if (!c->stats_z || b->KS > 15) return 0;
-    size_t budget = (size_t)(c->z_scratch_mb > 0 ? c->z_scratch_mb : 0) << 20;
-    if (c->total_mem && budget > c->total_mem / 4) budget = c->total_mem / 4;
-    const size_t per_frame = (size_t)b->nct * 16 * sizeof(double) + (size_t)b->nct * 2 + 24; // likelihoods + exponents + lse, 1 / S, Efin
-    const int64_t tc = (int64_t)(budget / per_frame / 1.2); // scratch() over-allocates by 1/8
-    return tc / 256 * 256;
-}
-
-static long model_tile_blocks(int64_t n) // z_tile_blocks of capi_gmm.hip: whole 256-frame tiles, tile stride an odd number of 4 KB granules
-{
-    long nfb = 16 * ((n + 255) / 256);
-    if ((nfb / 2) % 2 == 0) nfb += 2;
-    return nfb;
+    return gmmiv_z_budget_frames(c, b->nct, 24) / 256 * 256;
 }
 
 static int pack_chunk(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const ModelPlan &p, const ModelChunk &ck, double *pt, bool first)
@@ -348,7 +337,7 @@ int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int 
             if (n > 0) {
                 XView sub;
                 sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-                if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+                if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
                 if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
                 c->t_begin("k_llk_mfma", first);
                 first = false;
@@ -372,10 +361,10 @@ int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int 
         if ((rc = om.set(c, b, seg_model[s]))) return rc;
         XView sub;
         sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-        if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+        if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
         double *lse;
         long *sb;
-        if ((rc = gmmiv_i_run_lse(c, om.g, sub, dt, n, &lse))) return rc;
+        if ((rc = run_lse(c, om.g, sub, dt, n, &lse))) return rc;
         if ((rc = segment_table(c, n, &sb))) return rc;
         GCHK(gmmk_llk_seg_finalize(c->stream, lse, sb, 1, min_llk, max_llk, llk ? o_llk.d + f0 : nullptr, seg_sum ? o_sum.d + s : nullptr, nullptr));
     }
@@ -405,15 +394,11 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
     const int64_t Tc = models_chunk_frames(c, b);
     if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
         if ((rc = upload_plan(c, p))) return rc;
-        const long nfb = model_tile_blocks(p.max_span);
-        const size_t span = (size_t)(p.max_span > 0 ? p.max_span : 1);
-        void *pt, *lse, *zb, *eit, *inv;
+        void *pt;
+        gmmk_zview z;
+        double *lse;
         if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
-        if ((rc = c->scratch(WS_LSE, span * sizeof(double), &lse))) return rc;
-        if ((rc = c->scratch(WS_Z, (size_t)b->nct * nfb * 2048, &zb))) return rc;
-        if ((rc = c->scratch(WS_EIT, (size_t)(b->nct / 2) * nfb * 16 * sizeof(int), &eit))) return rc;
-        if ((rc = c->scratch(WS_INV, span * (sizeof(double) + sizeof(int)), &inv))) return rc;
-        int *efin = (int *)((double *)inv + span);
+        if ((rc = gmmiv_z_reserve(c, b->nct, p.max_span, true, &z, &lse))) return rc;
         bool first = true; // the first launch of the call restarts the kernel timers
         for (size_t k = 0; k < p.chunks.size(); ++k) {
             const ModelChunk &ck = p.chunks[k];
@@ -422,30 +407,26 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
             if (n > 0) {
                 XView sub;
                 sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-                if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+                if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
                 if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
                 c->t_begin("k_llk_mfma", first);
                 first = false;
                 GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(), b->nct,
-                                       p.d_tiles + ck.tile_off, (long)ck.ntiles, (double *)lse, (int)(c->use_glds & 1), (double *)zb, nfb, (int *)eit,
-                                       (double *)inv, efin));
+                                       p.d_tiles + ck.tile_off, (long)ck.ntiles, lse, (int)(c->use_glds & 1), z));
                 c->t_end();
-                GCHK(gmmk_count_dead(c->stream, (const double *)lse + (f0 - ck.base), (long)n, c->d_zero_llk));
+                GCHK(gmmk_count_dead(c->stream, lse + (f0 - ck.base), (long)n, c->d_zero_llk));
             }
             // every (segment, c < C) row is written by exactly one wave (zeros for an empty segment, whose likelihood blocks are never read)
             c->t_begin("k_stats_z", k == 0);
             if (second) // the EM shape (x^2 accumulators) with the row epilogue
-                GCHK(gmmk_stats_z_rows(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
-                                       (const double *)inv, efin, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
-                                       o_f.d + (size_t)ck.s0 * SV, o_s.d + (size_t)ck.s0 * SV, c->prune_thr()));
+                GCHK(gmmk_stats_z_rows(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, z, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0),
+                                       o_n.d + (size_t)ck.s0 * b->C, o_f.d + (size_t)ck.s0 * SV, o_s.d + (size_t)ck.s0 * SV, c->prune_thr()));
             else
-                GCHK(gmmk_stats_z(c->stream, b->KS, 0, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, (const double *)zb, nfb, (const int *)eit,
-                                  (const double *)inv, efin, 1.0, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0), o_n.d + (size_t)ck.s0 * b->C,
-                                  o_f.d + (size_t)ck.s0 * SV, 1, 0, c->prune_thr()));
+                GCHK(gmmk_stats_z(c->stream, b->KS, 0, dt == GMMIV_F64, xb, xv.ldx, b->D, b->C, b->nct, z, 1.0, p.d_seg + ck.seg_off, (int)(ck.s1 - ck.s0),
+                                  o_n.d + (size_t)ck.s0 * b->C, o_f.d + (size_t)ck.s0 * SV, 1, 0, c->prune_thr()));
             c->t_end();
             if (seg_llk)
-                GCHK(gmmk_llk_seg_finalize(c->stream, (const double *)lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), 0.0, 0.0, nullptr, nullptr,
-                                           o_l.d + 2 * (size_t)ck.s0));
+                GCHK(gmmk_llk_seg_finalize(c->stream, lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), 0.0, 0.0, nullptr, nullptr, o_l.d + 2 * (size_t)ck.s0));
         }
         return finish();
     }
@@ -469,10 +450,10 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
         const gmmiv_gmm *g = om.g;
         XView sub;
         sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-        if ((rc = gmmiv_i_count_unusable(c, sub, dt, n, b->D))) return rc;
+        if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
         double *lse;
         long *sb;
-        if ((rc = gmmiv_i_run_lse(c, g, sub, dt, n, &lse))) return rc;
+        if ((rc = run_lse(c, g, sub, dt, n, &lse))) return rc;
         if ((rc = segment_table(c, n, &sb))) return rc;
         double *Nrow = o_n.d + (size_t)s * b->C, *Frow = o_f.d + (size_t)s * SV;
         if (second) {
@@ -481,7 +462,7 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
                 const int NC = 2 * g->D + 2; // [x | 1 | x^2 | 0]
                 void *Sg;
                 if ((rc = c->scratch(WS_PART, (size_t)g->C * NC * sizeof(double), &Sg))) return rc;
-                if ((rc = gmmiv_i_generic_gamma_gemm(c, g, sub, dt, 0, n, lse, true, NC, (double *)Sg))) return rc;
+                if ((rc = generic_gamma_gemm(c, g, sub, dt, 0, n, lse, true, NC, (double *)Sg))) return rc;
                 GCHK(gmmk_scatter_em(c->stream, g->C, g->D, NC, (const double *)Sg, 1.0, (double *)accw));
             } else {
                 void *part;
@@ -497,7 +478,7 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
             const int NC = g->D + 2 - (g->D & 1); // [x | 1] padded to an even width
             void *S;
             if ((rc = c->scratch(WS_PART, (size_t)g->C * NC * sizeof(double), &S))) return rc;
-            if ((rc = gmmiv_i_generic_gamma_gemm(c, g, sub, dt, 0, n, lse, false, NC, (double *)S))) return rc;
+            if ((rc = generic_gamma_gemm(c, g, sub, dt, 0, n, lse, false, NC, (double *)S))) return rc;
             GCHK(gmmk_scatter_nf(c->stream, g->C, g->D, NC, (const double *)S, Nrow, Frow));
         } else {
             c->t_begin("k_stats_mfma", s == 0);

@@ -147,9 +147,12 @@ __global__ __launch_bounds__(256, FEAT_FB <= 2 ? 2 : 1) void k_feat_comp(const v
 }
 
 template <int NT>
-static int launch_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const double *zbuf, long nfb,
-                            const int *eit, const double *inv, const int *efin, const double *offP, void *out, long ldo)
+static int launch_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                            const double *offP, void *out, long ldo)
 {
+    const double *zbuf = z.zbuf, *inv = z.inv;
+    const int *eit = z.eit, *efin = z.efin;
+    const long nfb = z.nfb;
     const unsigned grid = (unsigned)((n + 64 * FEAT_FB - 1) / (64 * FEAT_FB));
     if (x_f64 && o_f64) k_feat_comp<NT, double, double><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
     else if (x_f64) k_feat_comp<NT, double, float><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
@@ -175,18 +178,18 @@ int gmmk_feat_pack_offset(hipStream_t st, const double *off, int C, int D, int n
     return (int)hipGetLastError();
 }
 
-int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const double *zbuf, long nfb,
-                   const int *eit, const double *inv, const int *efin, const double *offP, void *out, long ldo)
+int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                   const double *offP, void *out, long ldo)
 {
     if (n <= 0) return 0;
 #ifdef FEAT_VALU
-    if ((D + 15) / 16 == 4) return launch_feat_comp_valu(st, x_f64, o_f64, x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
+    if ((D + 15) / 16 == 4) return launch_feat_comp_valu(st, x_f64, o_f64, x, ldx, n, D, nct, z.zbuf, z.nfb, z.eit, z.inv, z.efin, offP, out, ldo);
 #endif
     switch ((D + 15) / 16) {
-    case 1: return launch_feat_comp<1>(st, x_f64, o_f64, x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    case 2: return launch_feat_comp<2>(st, x_f64, o_f64, x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    case 3: return launch_feat_comp<3>(st, x_f64, o_f64, x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    case 4: return launch_feat_comp<4>(st, x_f64, o_f64, x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
+    case 1: return launch_feat_comp<1>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, out, ldo);
+    case 2: return launch_feat_comp<2>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, out, ldo);
+    case 3: return launch_feat_comp<3>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, out, ldo);
+    case 4: return launch_feat_comp<4>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, out, ldo);
     }
     return -1; // D > 64: the caller takes the generic path
 }

@@ -61,17 +61,27 @@ int gmmk_fill_chunks(hipStream_t st, long *dst, int nseg, long per, long n);
 int gmmk_count_flags(hipStream_t st, const unsigned char *flag, long T, unsigned long long *cnt);
 int gmmk_gather_runs(hipStream_t st, int x_f64, const void *x, long ldx, int D, const long *runs, long nrun, void *out);
 
-// stats_z.hip / k_llk_mfma<WZ>: scaled likelihoods written once by the log-likelihood kernel, statistics from them
+// stats_z.hip / k_llk_mfma<WZ>: scaled likelihoods written once by the log-likelihood kernel, statistics from them.
+// The scratch the kernel leaves them in (reserved by gmmiv_z_reserve, capi_gmm_util.h): zbuf = nct * nfb blocks of 2 KB (16 frames x 16
+// Gaussians), eit = the running exponents, (nct / 2) * nfb * 16 ints, inv / efin = 1 / S_t and Efin of every frame.
+// One other user: gmmk_llk_topc hands k_llk_mfma<TC> its own arrays in the same five kernel arguments (zbuf = candidate records, nfb
+// unused, eit = candidate counts, inv = the slow-path sums, efin = Efin); a change of this struct has to keep that call in step.
+struct gmmk_zview {
+    double *zbuf;
+    long nfb;
+    int *eit;
+    double *inv;
+    int *efin;
+};
 int gmmk_llk_z(hipStream_t st, int KS, int x_f64, const void *x, long T, long ldx, int D, const double *Pt, int nct,
-               double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv, int *efin);
+               double *lse, int use_glds, const gmmk_zview &z);
 // k_llk_mfma<.., MM>: a model per segment (gmmiv_*_models).  tiles: DEVICE array of ntiles entries (gmmiv_plan_model_tiles; frame numbers
 // relative to x / lse / inv / efin / zbuf block 0), Pt: the packed models of the call's chunk, pt_stride doubles apart.  zbuf / eit hold
 // nfb >= ceil(last written frame / 16) blocks per Gaussian tile; only rows inside the tiles' windows are written.  -1: no instantiation
 int gmmk_llk_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
                     const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds);
 int gmmk_llk_z_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
-                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv,
-                      int *efin);
+                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, const gmmk_zview &z);
 // constants of G models in one launch (tables at p + g * stride, stride 0 = shared; a / lwc [G x Cp]); packed operands of the n models
 // ids[0..n) (device array) into Pt + slot * nct (2 KS + 2) 64 in one launch -- the arithmetic of gmmk_pack_model, the same bits
 int gmmk_const_models(hipStream_t st, int G, int C, int Cp, int D, const double *w, long sw, const double *mean, long sm, const double *iv,
@@ -111,30 +121,26 @@ int gmmk_posteriors(hipStream_t st, int x_f64, const void *x, long T, long ldx, 
                     const double *ivT, const double *lwc, const double *lse, double *gamma);
 int gmmk_stats_z_groups(int nct);
 int gmmk_stats_z_wg_per_cu(void);
-int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf,
-                 long nfb, const int *eit, const double *inv, const int *efin, double scale, const long *seg_begin, int nseg,
-                 double *out0, double *out1, int mode, int accum, double prune_thr);
+int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                 double scale, const long *seg_begin, int nseg, double *out0, double *out1, int mode, int accum, double prune_thr);
 // the EM shape with a row epilogue: N [nseg x C], F, X2 [nseg x C*D] = sum_t gamma [1 | x | x^2] of every segment, written directly
-int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
-                      const int *eit, const double *inv, const int *efin, const long *seg_begin, int nseg, double *N, double *F, double *X2,
-                      double prune_thr);
+int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                      const long *seg_begin, int nseg, double *N, double *F, double *X2, double prune_thr);
 size_t gmmk_topc_z_lds(int nct, int D);
-int gmmk_topc_from_z(hipStream_t st, int x_f64, const void *x, long n, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
-                     const int *eit, const int *efin, const double *mean, const double *iv, const double *lwc,
-                     const double *w, int ctop, int complete, double lo, double hi, int *idx, double *lk, double *nlk, double *nllk,
-                     double *nw, double *llk, int *flag);
+int gmmk_topc_from_z(hipStream_t st, int x_f64, const void *x, long n, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                     const double *mean, const double *iv, const double *lwc, const double *w, int ctop, int complete, double lo, double hi,
+                     int *idx, double *lk, double *nlk, double *nllk, double *nw, double *llk, int *flag);
 int gmmk_topc_use16(hipStream_t st, int x_f64, const void *x, long T, long ldx, int D, const double *mean, const double *iv,
                     const double *lwc, int C, int ctop, const int *idx, const double *nllk, int complete, double lo, double hi, double *llk, int four);
 int gmmk_topc_use4_multi(hipStream_t st, int x_f64, const void *x, long T, long ldx, int D, const void *clients, int n_clients, int ctop,
                          const int *idx, const double *nllk, int complete, double lo, double hi, double *llk); // clients: device array of {mean, iv, lwc, (long) C}
-int gmmk_post_from_z(hipStream_t st, long n, int C, int nct, const double *zbuf, long nfb, const int *eit, const double *inv,
-                     const int *efin, double *gamma);
+int gmmk_post_from_z(hipStream_t st, long n, int C, int nct, const gmmk_zview &z, double *gamma);
 
 // feat_comp.hip: frames rewritten from the posteriors (gmmiv_feat_compensate / gmmiv_feat_map / gmmiv_scatter_runs)
 size_t gmmk_feat_offset_doubles(int nct, int D);
 int gmmk_feat_pack_offset(hipStream_t st, const double *off, int C, int D, int nct, double *offP); // MFMA B-operand order, zero padded
-int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const double *zbuf, long nfb,
-                   const int *eit, const double *inv, const int *efin, const double *offP, void *out, long ldo); // -1: D > 64
+int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                   const double *offP, void *out, long ldo); // -1: D > 64
 int gmmk_feat_sub(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, const double *P, const double *lse, void *out,
                   long ldo);
 int gmmk_feat_map(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long T, int D, int C, const int *best, const double *cd_mean,

@@ -1361,47 +1361,43 @@ int gmmk_pack_model(hipStream_t st, int C, int D, int KS, int nct, int Cp64, con
 
 template <int KS, typename XT, int NW, int MODE>
 static int launch_llk(hipStream_t st, const void *x, long T, long ldx, int D, const double *Pt, int nct,
-                      double *lse, int use_glds, double *zbuf = nullptr, long nfb = 0, int *eit = nullptr, double *inv = nullptr,
-                      int *efin = nullptr)
+                      double *lse, int use_glds, const gmmk_zview &z = gmmk_zview{})
 {
     constexpr int NR = 2 * KS + 2;
     const size_t lds = 2 * 2 * NR * 64 * sizeof(double) + GEXP_TAB_N * sizeof(double) + (MODE == 2 ? NW * 32 * sizeof(int) : 0); // two model stages + the exp table (+ TC: candidate counters)
     HIPCHK((gmmiv_lds_attr<k_llk_mfma<KS, XT, NW, MODE>>(lds))); // per (device, kernel): lds_attr.h
     const unsigned grid = (unsigned)((T + NW * 32 - 1) / (NW * 32));
-    k_llk_mfma<KS, XT, NW, MODE><<<grid, NW * 64, lds, st>>>(x, T, ldx, D, Pt, nct, lse, use_glds & 1, use_glds >> 8, zbuf, nfb, eit, inv, efin, nullptr, 0);
+    k_llk_mfma<KS, XT, NW, MODE><<<grid, NW * 64, lds, st>>>(x, T, ldx, D, Pt, nct, lse, use_glds & 1, use_glds >> 8, z.zbuf, z.nfb, z.eit, z.inv, z.efin, nullptr, 0);
     return (int)hipGetLastError();
 }
 
 // a model per segment: one 8-wave workgroup per entry of the tile table (device array); Pt = the chunk's packed models, pt_stride doubles apart
 template <int KS, typename XT, int MODE>
 static int launch_llk_models(hipStream_t st, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct, const gmmiv_model_tile *tiles,
-                             long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv, int *efin)
+                             long ntiles, double *lse, int use_glds, const gmmk_zview &z)
 {
     constexpr int NR = 2 * KS + 2;
     const size_t lds = 2 * 2 * NR * 64 * sizeof(double) + GEXP_TAB_N * sizeof(double);
     HIPCHK((gmmiv_lds_attr<k_llk_mfma<KS, XT, 8, MODE, true>>(lds))); // per (device, kernel): lds_attr.h
-    k_llk_mfma<KS, XT, 8, MODE, true><<<(unsigned)ntiles, 8 * 64, lds, st>>>(x, 0, ldx, D, Pt, nct, lse, use_glds & 1, 0, zbuf, nfb, eit, inv, efin, tiles, pt_stride);
+    k_llk_mfma<KS, XT, 8, MODE, true><<<(unsigned)ntiles, 8 * 64, lds, st>>>(x, 0, ldx, D, Pt, nct, lse, use_glds & 1, 0, z.zbuf, z.nfb, z.eit, z.inv, z.efin, tiles, pt_stride);
     return (int)hipGetLastError();
 }
-#define MM_CASE(K, MODE)                                                                                                                      \
-    case K:                                                                                                                                   \
-        return x_f64 ? launch_llk_models<K, double, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, zbuf, nfb, eit, inv, efin) \
-                     : launch_llk_models<K, float, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, zbuf, nfb, eit, inv, efin);
+#define MM_CASE(K, MODE)                                                                                                  \
+    case K:                                                                                                               \
+        return x_f64 ? launch_llk_models<K, double, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, z) \
+                     : launch_llk_models<K, float, MODE>(st, x, ldx, D, Pt, pt_stride, nct, tiles, ntiles, lse, use_glds, z);
 int gmmk_llk_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
                     const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds)
 {
     if (ntiles <= 0) return 0;
-    double *zbuf = nullptr, *inv = nullptr;
-    int *eit = nullptr, *efin = nullptr;
-    const long nfb = 0;
+    const gmmk_zview z = {}; // MODE 0 stores nothing
     switch (KS) {
         MM_CASE(4, 0) MM_CASE(8, 0) MM_CASE(15, 0)
     }
     return -1;
 }
 int gmmk_llk_z_models(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, const double *Pt, long pt_stride, int nct,
-                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv,
-                      int *efin)
+                      const gmmiv_model_tile *tiles, long ntiles, double *lse, int use_glds, const gmmk_zview &z)
 {
     if (ntiles <= 0) return 0;
     switch (KS) {
@@ -1693,21 +1689,21 @@ int gmmk_llk(hipStream_t st, int KS, int x_f64, const void *x, long T, long ldx,
     return -1;
 }
 
-// the same kernel, additionally leaving the scaled likelihoods of frames [0, T) in zbuf (nct * nfb
-// blocks of 2 KB, nfb = 16 * ceil(T / 256): whole workgroups are written), the running exponents in
-// eit[(nct / 2) * nfb * 16] and 1 / S_t, Efin per frame in inv[T], efin[T]; 8-wave workgroups
+// the same kernel, additionally leaving the scaled likelihoods of frames [0, T) in z.zbuf (nct * z.nfb
+// blocks of 2 KB, nfb >= 16 * ceil(T / 256): whole workgroups are written), the running exponents in
+// z.eit[(nct / 2) * nfb * 16] and 1 / S_t, Efin per frame in z.inv[T], z.efin[T]; 8-wave workgroups
 int gmmk_llk_z(hipStream_t st, int KS, int x_f64, const void *x, long T, long ldx, int D, const double *Pt, int nct,
-               double *lse, int use_glds, double *zbuf, long nfb, int *eit, double *inv, int *efin)
+               double *lse, int use_glds, const gmmk_zview &z)
 {
     if (T <= 0) return 0;
     const bool small = T <= 32768 && gmmiv_kopts_cur().short_calls; // one round of 4-wave workgroups: half the time per stage (see gmmk_llk_topc); same blocks, same values
-#define CASE(K)                                                                                                              \
-    case K:                                                                                                                  \
-        if (small)                                                                                                           \
-            return x_f64 ? launch_llk<K, double, 4, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, zbuf, nfb, eit, inv, efin) \
-                         : launch_llk<K, float, 4, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, zbuf, nfb, eit, inv, efin); \
-        return x_f64 ? launch_llk<K, double, 8, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, zbuf, nfb, eit, inv, efin)   \
-                     : launch_llk<K, float, 8, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, zbuf, nfb, eit, inv, efin);
+#define CASE(K)                                                                                   \
+    case K:                                                                                       \
+        if (small)                                                                                \
+            return x_f64 ? launch_llk<K, double, 4, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, z) \
+                         : launch_llk<K, float, 4, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, z); \
+        return x_f64 ? launch_llk<K, double, 8, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, z)   \
+                     : launch_llk<K, float, 8, 1>(st, x, T, ldx, D, Pt, nct, lse, use_glds, z);
     switch (KS) {
         CASE(4) CASE(8) CASE(15)
     }
@@ -1728,13 +1724,14 @@ int gmmk_llk_topc(hipStream_t st, int KS, int x_f64, const void *x, long T, long
     // workgroups takes 0.65 ms whatever its length -- ComputeTest's segments of a few thousand frames.  Short calls run 4-wave
     // workgroups (128 frames, one wave per SIMD: half the time per stage); per-frame results do not depend on the workgroup shape.
     const bool small = T <= 32768 && gmmiv_kopts_cur().short_calls;
+    const gmmk_zview tc = {cand, 0, cnt, slow, efin}; // this mode's arrays travel in the kernel's five scratch arguments
 #define CASE(K)                                                                                                                    \
     case K:                                                                                                                        \
         if (small)                                                                                                                 \
-            return x_f64 ? launch_llk<K, double, 4, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, cand, 0, cnt, slow, efin)        \
-                         : launch_llk<K, float, 4, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, cand, 0, cnt, slow, efin);        \
-        return x_f64 ? launch_llk<K, double, 8, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, cand, 0, cnt, slow, efin)            \
-                     : launch_llk<K, float, 8, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, cand, 0, cnt, slow, efin);
+            return x_f64 ? launch_llk<K, double, 4, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, tc)        \
+                         : launch_llk<K, float, 4, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, tc);        \
+        return x_f64 ? launch_llk<K, double, 8, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, tc)            \
+                     : launch_llk<K, float, 8, 2>(st, x, T, ldx, D, Pt, nct, theta, use_glds, tc);
     switch (KS) {
         CASE(4) CASE(8) CASE(15)
     }

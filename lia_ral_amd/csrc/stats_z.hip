@@ -365,9 +365,8 @@ int gmmk_stats_z_groups(int nct) { const int tpg = g_stats_z_waves == 4 ? 8 : 16
 int gmmk_stats_z_wg_per_cu(void) { return g_stats_z_waves == 4 ? 2 : 1; }
 
 template <int KS, bool SQ, typename XT, bool PRUNE, int NW, int TPW, int FT, int ZD = 2, bool ROWS = false>
-static int launch_z(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
-                    const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
-                    int mode, int accum, double prune_thr, double *out2)
+static int launch_z(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z, double scale, const long *seg_begin,
+                    int nseg, double *out0, double *out1, int mode, int accum, double prune_thr, double *out2)
 {
     constexpr int RL = ((4 * KS + 2 + 31) / 32) * 32;
     constexpr int PF = TPW > 2 ? TPW / 2 : 1;
@@ -376,16 +375,15 @@ static int launch_z(hipStream_t st, const void *x, long ldx, int D, int C, int n
     const int ngrp = (nct + TPW * NW - 1) / (TPW * NW);
     const unsigned grid = (unsigned)(ngrp * 8 * ((nseg + 7) / 8));
     const unsigned magicD = gmmiv_div_magic(D);
-    k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD, ROWS><<<grid, NW * 64, lds, st>>>(x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg,
-                                                                    ngrp, out0, out1, mode, accum, magicD, prune_thr, out2);
+    k_stats_z<KS, SQ, XT, PRUNE, NW, TPW, FT, ZD, ROWS><<<grid, NW * 64, lds, st>>>(x, ldx, D, C, nct, z.zbuf, z.nfb, z.eit, z.inv, z.efin, scale, seg_begin,
+                                                                    nseg, ngrp, out0, out1, mode, accum, magicD, prune_thr, out2);
     return (int)hipGetLastError();
 }
 
-#define ZARGS st, x, ldx, D, C, nct, zbuf, nfb, eit, inv, efin, scale, seg_begin, nseg, out0, out1, mode, accum, prune_thr, out2
+#define ZARGS st, x, ldx, D, C, nct, z, scale, seg_begin, nseg, out0, out1, mode, accum, prune_thr, out2
 template <int KS, bool SQ, typename XT>
-static int launch_z_p(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
-                      const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
-                      int mode, int accum, double prune_thr, double *out2)
+static int launch_z_p(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z, double scale, const long *seg_begin,
+                      int nseg, double *out0, double *out1, int mode, int accum, double prune_thr, double *out2)
 {
     if (prune_thr > 0.0) return launch_z<KS, SQ, XT, true, 8, 2, 64>(ZARGS);
     if (g_stats_z_waves == 4) return launch_z<KS, SQ, XT, false, 4, 2, 32>(ZARGS);
@@ -401,9 +399,8 @@ static int launch_z_p(hipStream_t st, const void *x, long ldx, int D, int C, int
 }
 // the EM shapes with the row epilogue (N, F, sum g x^2 per segment): the same choice of workgroup shape / stream depth / pruning
 template <int KS, typename XT>
-static int launch_z_rows(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb, const int *eit,
-                         const double *inv, const int *efin, double scale, const long *seg_begin, int nseg, double *out0, double *out1,
-                         int mode, int accum, double prune_thr, double *out2)
+static int launch_z_rows(hipStream_t st, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z, double scale,
+                         const long *seg_begin, int nseg, double *out0, double *out1, int mode, int accum, double prune_thr, double *out2)
 {
     if (prune_thr > 0.0) return launch_z<KS, true, XT, true, 8, 2, 64, 2, true>(ZARGS);
     if (g_stats_z_waves == 4) return launch_z<KS, true, XT, false, 4, 2, 32, 2, true>(ZARGS);
@@ -414,9 +411,8 @@ static int launch_z_rows(hipStream_t st, const void *x, long ldx, int D, int C, 
 
 // scale multiplies every posterior (the EM frame weight); prune_thr > 0: groups of 4 frames x 32
 // Gaussians whose posteriors are all below prune_thr are skipped (opt-in, see ctx.h)
-int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf,
-                 long nfb, const int *eit, const double *inv, const int *efin, double scale, const long *seg_begin, int nseg,
-                 double *out0, double *out1, int mode, int accum, double prune_thr)
+int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                 double scale, const long *seg_begin, int nseg, double *out0, double *out1, int mode, int accum, double prune_thr)
 {
     if (nseg <= 0) return 0;
     double *const out2 = nullptr;
@@ -433,9 +429,8 @@ int gmmk_stats_z(hipStream_t st, int KS, int sq, int x_f64, const void *x, long 
 
 // N [nseg x C], F [nseg x C*D], X2 [nseg x C*D] = sum_t gamma [1 | x | x^2] per segment, rows written directly (every (segment, c < C)
 // row by exactly one wave, in the fixed order of the segment's own blocks: no atomics, no dependence on the other segments)
-int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
-                      const int *eit, const double *inv, const int *efin, const long *seg_begin, int nseg, double *N, double *F, double *X2,
-                      double prune_thr)
+int gmmk_stats_z_rows(hipStream_t st, int KS, int x_f64, const void *x, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                      const long *seg_begin, int nseg, double *N, double *F, double *X2, double prune_thr)
 {
     if (nseg <= 0) return 0;
     const double scale = 1.0;

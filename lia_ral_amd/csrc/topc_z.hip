@@ -221,20 +221,19 @@ __global__ __launch_bounds__(256, 2) void k_topc_from_z(const void *__restrict__
 // 1 when the kernel applies (a lane holds 32 values per frame: at most 128 Gaussian tiles; frame rows of at most 64 dims)
 size_t gmmk_topc_z_lds(int nct, int D) { return (nct <= 128 && D <= 64) ? 1 : 0; }
 
-int gmmk_topc_from_z(hipStream_t st, int x_f64, const void *x, long n, long ldx, int D, int C, int nct, const double *zbuf, long nfb,
-                     const int *eit, const int *efin, const double *mean, const double *iv, const double *lwc,
-                     const double *w, int ctop, int complete, double lo, double hi, int *idx, double *lk, double *nlk, double *nllk,
-                     double *nw, double *llk, int *flag)
+int gmmk_topc_from_z(hipStream_t st, int x_f64, const void *x, long n, long ldx, int D, int C, int nct, const gmmk_zview &z,
+                     const double *mean, const double *iv, const double *lwc, const double *w, int ctop, int complete, double lo, double hi,
+                     int *idx, double *lk, double *nlk, double *nllk, double *nw, double *llk, int *flag)
 {
     if (n <= 0) return 0;
     if (!gmmk_topc_z_lds(nct, D)) return -1;
     const size_t lds = 0;
     const unsigned grid = (unsigned)(2 * ((n + 15) / 16));
     if (x_f64)
-        k_topc_from_z<double><<<grid, 256, lds, st>>>(x, n, ldx, D, C, nct, zbuf, nfb, eit, efin, mean, iv, lwc, w, ctop, complete,
+        k_topc_from_z<double><<<grid, 256, lds, st>>>(x, n, ldx, D, C, nct, z.zbuf, z.nfb, z.eit, z.efin, mean, iv, lwc, w, ctop, complete,
                                                       lo, hi, idx, lk, nlk, nllk, nw, llk, flag);
     else
-        k_topc_from_z<float><<<grid, 256, lds, st>>>(x, n, ldx, D, C, nct, zbuf, nfb, eit, efin, mean, iv, lwc, w, ctop, complete, lo,
+        k_topc_from_z<float><<<grid, 256, lds, st>>>(x, n, ldx, D, C, nct, z.zbuf, z.nfb, z.eit, z.efin, mean, iv, lwc, w, ctop, complete, lo,
                                                      hi, idx, lk, nlk, nllk, nw, llk, flag);
     return (int)hipGetLastError();
 }
@@ -983,11 +982,10 @@ __global__ __launch_bounds__(256) void k_post_from_z(long n, int C, int nct, con
     }
 }
 
-int gmmk_post_from_z(hipStream_t st, long n, int C, int nct, const double *zbuf, long nfb, const int *eit, const double *inv,
-                     const int *efin, double *gamma)
+int gmmk_post_from_z(hipStream_t st, long n, int C, int nct, const gmmk_zview &z, double *gamma)
 {
     if (n <= 0) return 0;
     const unsigned gy = nct >= 32 ? 8 : 1; // 8 tile groups per frame block: enough workgroups for short inputs
-    k_post_from_z<<<dim3((unsigned)((n + 15) / 16), gy), 256, 0, st>>>(n, C, nct, zbuf, nfb, eit, inv, efin, gamma);
+    k_post_from_z<<<dim3((unsigned)((n + 15) / 16), gy), 256, 0, st>>>(n, C, nct, z.zbuf, z.nfb, z.eit, z.inv, z.efin, gamma);
     return (int)hipGetLastError();
 }

@@ -6,9 +6,12 @@ at boundary shapes, as BITS.  A sibling of tools/bitwise_fixture.py, with the sa
 Covered: the EM accumulator at vectSize 1, 13, 33, 60, 64, 80 and frame counts that end inside a 16-frame block, a 64-frame tile
 and a segment, several frame chunks per call (small z_scratch_mb), f32 / f64 / row-strided features, the workgroup shapes and
 stream depths of k_stats_z (z_waves 4 / 16, z_depth_em 4) and posterior pruning; the N / F rows of tv_stats (both N / F shapes);
-the posterior vectors of gmmiv_occ; DETERMINE_TOP through the stored likelihoods (topc_fused 0).
+the posterior vectors of gmmiv_occ; DETERMINE_TOP through the stored likelihoods (topc_fused 0); the compensated frames of
+gmmiv_feat_compensate (one chunk, and a chunk plus a tail); gmmiv_llk_models / _tv_stats_models / _em_stats_models on segments that
+start inside a 16-frame block, are empty, 17 frames long and four tiles long.
 tests/golden/em_readers_bitwise.json was written by the library before the EM statistics kernel read x^2 from LDS and before the
-running exponents were stored four to a 16-byte word (tests/test_gpu_em_readers_bitwise.py)."""
+running exponents were stored four to a 16-byte word (tests/test_gpu_em_readers_bitwise.py); its featcomp_ and models_ entries by the
+library before the likelihood scratch got its one reserve function (gmmiv_z_reserve)."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,6 +97,32 @@ def compute():
         out["topz_idx_" + k], out["topz_llk_" + k] = d["idx"], d["llk"]
         opt("topc_fused", prev)
         g.close()
+
+    # feature compensation through the stored likelihoods: one chunk, and a 4928-frame chunk plus a 1079-frame tail
+    C, D = 128, 60
+    w, mean, iv = make_gmm(C, D, seed=C * 7 + D)
+    g = ctx.gmm(w, mean, iv)
+    offset = np.random.default_rng(5).standard_normal((C, D))
+    out["featcomp_%dx%dx1000" % (C, D)] = g.feat_compensate(make_frames(w, mean, iv, 1000, seed=1000 + D), offset)
+    prev = opt("z_scratch_mb", 6)
+    out["featcomp_chunked_%dx%dx6007" % (C, D)] = g.feat_compensate(make_frames(w, mean, iv, 6007, seed=6007 + D), offset)
+    opt("z_scratch_mb", prev)
+    g.close()
+
+    # a model per segment: a first block that starts inside a 16-frame block, an empty segment, a 17-frame segment and a segment
+    # over four 256-frame tiles
+    G = 3
+    models = [make_gmm(C, D, seed=40 + m) for m in range(G)]
+    b = ctx.gmm_batch(G, C, D).load(*(np.stack([m[i] for m in models]) for i in range(3)))
+    x = make_frames(*models[0], 1400, seed=1400)
+    sb, sm = [5, 305, 305, 322, 1322], [0, 2, 2, 1]
+    llk, seg_sum = b.llk(x, sb, sm)
+    out["models_llk"], out["models_llk_seg_sum"] = llk[sb[0]:sb[-1]], seg_sum  # frames outside the segments are not written
+    for f, v in zip(("N", "F", "seg_llk"), b.tv_stats(x, sb, sm)):
+        out["models_tv_" + f] = v
+    for f, v in zip(("N", "F", "S", "seg_llk"), b.em_stats(x, sb, sm)):
+        out["models_em_" + f] = v
+    b.close()
     ctx.close()
     return {k: np.ascontiguousarray(v) for k, v in out.items()}
 
