@@ -366,7 +366,7 @@ def _launch_dgemm(out, o, ta, tb, grid, M, N, K, lda, sA, ldb, sB, a_off, b_off,
 def plan(ta, tb, M, N, K, lda, ldb, sA=0, sB=0, a_off=0, b_off=0, batch=1, nz=1, epi=0, opts=None, n_cu=256):
     """The k_dgemm launches of gmmiv_dgemm(ta, tb, M, N, K, ...) and whether k_splitk_reduce follows: (launches, reduce).
     a_off / b_off: the operand bases in doubles past a 16-byte boundary (only their parity matters).
-    Mirrors capi_tv.hip gmmiv_dgemm (the choice of path), tv_kernels.hip tvk_dgemm / tvk_dgemm_epi / tvk_dgemm_splitk (grid, the kc
+    Mirrors capi_iv_score.hip gmmiv_dgemm (the choice of path), tv_kernels.hip tvk_dgemm / tvk_dgemm_epi / tvk_dgemm_splitk (grid, the kc
     rounding, the nt80 condition), launch_dgemm (MODE / tile shape / strips) and the krem / nkt lines of k_dgemm."""
     o = dict(DEFAULT_OPTS, **(opts or {}))
     out = []

@@ -1,0 +1,207 @@
+"""The host linear algebra behind the i-vector back end (lia_ral_amd/csrc/host_linalg.cpp: Cholesky upper and lower, SPD inverse,
+triangular inverse and solves, cyclic Jacobi, the host GEMM) in a stand-alone program, tests/host_linalg_main.cpp, built twice:
+plain, and with -fsanitize=address,undefined, whose run must exit 0 with nothing on stderr.  Nothing is loaded into Python.
+
+Orders 1, 2, 33, 64; SPD matrices of spd_ref.spd at condition 1e1, 1e3, 1e6; matrices that are not positive definite must be
+reported; the eigen routine also at rank < n.  Judged by rules the suite already has: factor, inverse and substitutions by
+spd_ref.accept against the 80-bit reference of tests/spd_ref.py with numpy's error on the same matrix as err_oracle; the eigen
+routine by the assertions of test_efr_lda_and_eigen (values descending, reconstruction within 1e-10 val[0], values within 1e-12
+relative of numpy.linalg.eigh)."""
+import os
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import spd_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCES = [os.path.join(ROOT, "tests", "host_linalg_main.cpp"), os.path.join(ROOT, "lia_ral_amd", "csrc", "host_linalg.cpp")]
+ORDERS = (1, 2, 33, 64)
+CONDS = (1e1, 1e3, 1e6)
+BUILDS = {"plain": ["-O3"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+LD = spd_ref.LD
+
+pytestmark = pytest.mark.skipif(not spd_ref.HAVE_LONGDOUBLE, reason=spd_ref.SKIP_MESSAGE)
+
+
+def compiler():
+    """$CXX, else the ROCm clang the library is built with (it links the sanitizer runtime statically), else what the PATH has"""
+    for cxx in (os.environ.get("CXX"), "/opt/rocm/llvm/bin/clang++", "clang++", "g++"):
+        if cxx and shutil.which(cxx):
+            return cxx
+    raise AssertionError("no C++ compiler for the stand-alone program (set CXX)")
+
+
+def cases():
+    """[(name, op, n, rank, A, B)]: every routine on every SPD matrix, the failures, the eigen routine at full and at lower rank"""
+    out = []
+    for n in ORDERS:
+        for cond in CONDS:
+            rng = np.random.default_rng(int(1000 * n + np.log10(cond)))
+            A = spd_ref.spd(n, cond, rng)
+            B = rng.normal(size=(n, n))
+            tag = "n%d_cond%.0e" % (n, cond)
+            out += [("chol_upper_" + tag, 0, n, 0, A, None), ("spd_inverse_" + tag, 1, n, 0, A, None), ("eigen_" + tag, 2, n, n, A, None),
+                    ("chol_lower_" + tag, 3, n, 0, A, None), ("lda_solves_" + tag, 4, n, 0, A, (B + B.T) / 2), ("hmm_" + tag, 5, n, 0, A, B)]
+            if n > 1:
+                out.append(("eigen_lowrank_" + tag, 2, n, n // 2, A, None))
+        bad_last = spd_ref.spd(n, 1e1, np.random.default_rng(n)); bad_last[-1, -1] = -1.0     # fails at the last pivot
+        bad_first = spd_ref.spd(n, 1e1, np.random.default_rng(n)); bad_first[0, 0] = 0.0      # ... at the first: a zero pivot is refused too
+        for name, M in (("last", bad_last), ("first", bad_first)):
+            out += [("notpd_%s_op%d_n%d" % (name, op, n), op, n, 0, M, np.eye(n) if op == 4 else None) for op in (0, 1, 3, 4)]
+    return out
+
+
+def run_program(exe, cs, tmp):
+    """write the cases, run, parse -> ({name: results}, returncode, stderr)"""
+    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<i", len(cs)))
+        for _, op, n, rank, A, B in cs:
+            f.write(struct.pack("<iii", op, n, rank))
+            f.write(np.ascontiguousarray(A, np.float64).tobytes())
+            if B is not None:
+                f.write(np.ascontiguousarray(B, np.float64).tobytes())
+    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
+    res = {}
+    if r.returncode == 0:
+        buf = open(fout, "rb").read()
+        pos = 0
+
+        def take_int():
+            nonlocal pos
+            pos += 4
+            return struct.unpack_from("<i", buf, pos - 4)[0]
+
+        def take(*shape):
+            nonlocal pos
+            cnt = int(np.prod(shape)) if shape else 1
+            a = np.frombuffer(buf, np.float64, cnt, pos).reshape(shape)
+            pos += 8 * cnt
+            return a
+        for name, op, n, rank, _, _ in cs:
+            if op == 0:
+                res[name] = dict(ok=take_int(), ch=take(n, n))
+            elif op == 1:
+                res[name] = dict(ok=take_int(), inv=take(n, n), logdet=float(take()))
+            elif op == 2:
+                res[name] = dict(vect=take(n, rank), val=take(rank))
+            elif op == 3:
+                res[name] = dict(ok=take_int(), dmin=float(take()), dmax=float(take()), L=take(n, n), Li=take(n, n))
+            elif op == 4:
+                res[name] = dict(ok=take_int(), T1=take(n, n), Cm=take(n, n), rows=take(n, n))
+            else:
+                res[name] = dict(prod=take(5, n, n))
+        assert pos == len(buf)
+    return res, r.returncode, r.stderr
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    """both builds of the program, each run once on all cases"""
+    cxx, cs, out = compiler(), cases(), {}
+    for build, flags in BUILDS.items():
+        tmp = str(tmp_path_factory.mktemp(build))
+        exe = os.path.join(tmp, "host_linalg_main")
+        subprocess.run([cxx, "-std=c++17", "-Wall"] + flags + SOURCES + ["-o", exe], check=True, capture_output=True, text=True, timeout=300)
+        out[build] = run_program(exe, cs, tmp)
+    return cs, out
+
+
+@pytest.fixture(scope="module")
+def refs():
+    """80-bit factor of every SPD matrix of the cases, computed once"""
+    memo = {}
+
+    def get(A):
+        key = A.tobytes()
+        if key not in memo:
+            memo[key] = spd_ref.cholesky(A)
+        return memo[key]
+    return get
+
+
+def test_the_sanitized_build_runs_clean(runs):
+    _, out = runs
+    _, rc, err = out["sanitized"]
+    assert rc == 0 and err == "", (rc, err[-2000:])
+    assert out["plain"][1] == 0, out["plain"][2][-2000:]
+
+
+def judged(name, got, ref, oracle):
+    err, err_oracle = spd_ref.forward_error(got, ref), spd_ref.forward_error(oracle, ref)
+    assert spd_ref.accept(err, err_oracle), "%s: error %.3g, numpy's %.3g, bar %.3g" % (name, err, err_oracle, spd_ref.bar(err_oracle))
+
+
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_factor_inverse_and_substitutions_against_the_80_bit_reference(runs, refs, build):
+    cs, out = runs
+    res = out[build][0]
+    seen = 0
+    for name, op, n, rank, A, B in cs:
+        if op in (2, 5) or name.startswith("notpd"):
+            continue
+        r, L80, Lnp = res[name], refs(A), np.linalg.cholesky(A)
+        assert r["ok"] == 1, name
+        seen += 1
+        if op == 0:
+            assert np.all(np.tril(r["ch"], -1) == 0.0)
+            judged(name, r["ch"].T, L80, Lnp)
+        elif op == 1:
+            judged(name, r["inv"], spd_ref.inverse(L80), np.linalg.inv(A))
+            ld80 = 2 * np.sum(np.log(np.diag(L80)))
+            scale = max(1.0, abs(float(ld80)))
+            assert spd_ref.accept(abs(float(r["logdet"] - ld80)) / scale, abs(float(np.linalg.slogdet(A)[1] - ld80)) / scale), name
+        elif op == 3:
+            assert np.all(np.triu(r["L"], 1) == 0.0) and r["dmin"] == np.diag(r["L"]).min() and r["dmax"] == np.diag(r["L"]).max()
+            judged(name, r["L"], L80, Lnp)
+            judged(name + " (inverse)", r["Li"], spd_ref.forward_subst(L80, np.eye(n)), np.linalg.inv(Lnp))
+        else:
+            T80 = spd_ref.forward_subst(L80, B)                         # L^-1 B = U^-T B
+            Tnp = np.linalg.solve(Lnp, B)
+            judged(name + " (U^-T B)", r["T1"], T80, Tnp)
+            judged(name + " (U^-T B U^-1)", r["Cm"], spd_ref.forward_subst(L80, T80.T).T, np.linalg.solve(Lnp, Tnp.T).T)
+            judged(name + " (U^-1 b)", r["rows"].T, spd_ref.backward_subst(L80, B), np.linalg.solve(Lnp.T, B))
+    assert seen == 4 * len(ORDERS) * len(CONDS)
+
+
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_a_matrix_that_is_not_positive_definite_is_reported(runs, build):
+    cs, out = runs
+    res = out[build][0]
+    bad = [name for name, *_ in cs if name.startswith("notpd")]
+    assert len(bad) == 2 * 4 * len(ORDERS) and all(res[name]["ok"] == 0 for name in bad)
+
+
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_the_eigen_routine_at_full_and_lower_rank(runs, build):
+    cs, out = runs
+    res = out[build][0]
+    relerr = lambda a, b: np.max(np.abs(a - b)) / np.max(np.abs(b))
+    for name, op, n, rank, A, _ in cs:
+        if op != 2:
+            continue
+        vect, val = res[name]["vect"], res[name]["val"]
+        assert np.all(np.diff(val) <= 0), name
+        assert relerr(val, np.linalg.eigh(A)[0][::-1][:rank]) < 1e-12, name
+        if rank == n:
+            assert np.allclose(vect @ np.diag(val) @ vect.T, A, atol=1e-10 * val[0]), name
+        else:  # the first `rank` pairs of the full decomposition, unchanged
+            full = res[name.replace("_lowrank", "")]
+            assert np.array_equal(val, full["val"][:rank]) and np.array_equal(vect, full["vect"][:, :rank]), name
+
+
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_the_host_gemm_in_every_transposition(runs, build):
+    cs, out = runs
+    res = out[build][0]
+    for name, op, n, rank, A, B in cs:
+        if op != 5:
+            continue
+        for t in range(4):
+            a, b = (A.T if t & 1 else A), (B.T if t & 2 else B)
+            judged("%s t=%d" % (name, t), res[name]["prod"][t], a.astype(LD) @ b.astype(LD), a @ b)
+        judged(name + " accumulate", res[name]["prod"][4], 2 * (A.astype(LD) @ B.astype(LD)), 2 * (A @ B))

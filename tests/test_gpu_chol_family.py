@@ -5,14 +5,16 @@ the public entry points with selector statistics, so every system of a batch is 
 err_gpu <= 16 max(err_oracle, 64 u)  (spd_ref.accept; err_oracle = the double-precision oracle's measured error on the same system).
 The normwise backward errors eta are printed, not asserted.  Cases and records: tools/chol_family_errors.py.
 
-Which case reaches which kernel (from launch_chol / launch_trinv / launch_uut / tvk_chol_*):
+Which case reaches which kernel.  The entry points decide nothing: SpdBatch (capi_tv_util.h) is the one owner of the choice -- left()
+(even order and chol_gemm 0) takes the left-looking kernels, everything else tvk_unpack_sym + the GEMM-built tvk_chol_batched /
+tvk_spd_inverse_batched -- and launch_chol / launch_trinv / launch_uut (chol_fused.hip) pick the kernel variant under it:
   defaults, even order <= 494      k_chol_left2<1>, k_chol_solve, k_trinv_left<true,1>, k_uut<true,2>
   chol_flow 0                      k_chol_left<true>
   chol_lds 0, and orders 496, 530  k_chol_left<false>, k_trinv_left<false,2>, k_uut<false,2>
   chol_waves 16                    k_trinv_left<true,1,16>, k_uut<true,1,16>
   chol_gemm 1, and orders 33, 131  tvk_chol_batched, tvk_spd_inverse_batched + tvk_pack_sym (GEMM-built)
-  update_t, even R, D <= 64        k_chol_solve_multi;  D = 65 or tv_mstep_solve 0: k_chol_left2 + k_trinv_left + k_uut (full
-                                   inverse) + k_dgemm;  R = 131: tvk_spd_inverse_batched + k_dgemm
+  update_t, even R, D <= 64        SpdBatch::factor + solve_multi: k_chol_solve_multi;  D = 65 or tv_mstep_solve 0: SpdBatch::inverse:
+                                   k_chol_left2 + k_trinv_left + k_uut (full inverse) + k_dgemm;  R = 131: tvk_spd_inverse_batched + k_dgemm
 """
 import functools
 import os
