@@ -1,5 +1,10 @@
 """GPU parity for the i-vector path (TVAcc maths) and i-vector scoring vs the CPU oracle.
-Tolerance: 1e-6 relative on i-vectors (north_star), tighter where conditioning allows."""
+Tolerance: 1e-6 relative on i-vectors (north_star), tighter where conditioning allows.
+
+Every criterion here is max|a - b| / max|b| over a whole array.  The judgement per element, per trial and per utterance, against an
+80-bit reference and a bar of that unit's own operands, is tests/test_gpu_tv_elementwise.py for the E- and M-step and
+tests/test_gpu_backend_elementwise.py for the scores, iv_normalize, the development-set statistics, the JFA steps and the
+approximate extractors."""
 import numpy as np
 import pytest
 
