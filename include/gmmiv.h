@@ -180,6 +180,7 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  *   gmmiv_frame_moments           NOT screened: sums of the raw values, a NaN goes into the sums like in the reference
  *   gmmiv_feat_compensate         the frame is COPIED THROUGH unchanged (converted to out_dtype), either kind, and counted in
  *                                 "zero_llk_frames" (the reference divides 0 by 0 there); kind (1) also in "screened_frames"
+ *   gmmiv_feat_compensate_models  as gmmiv_feat_compensate, under the segment's model; each frame counted once
  *   gmmiv_feat_map                NOT screened: best = 0 on a frame whose every term is 0 (the reference's loop leaves idx = 0), the
  *                                 raw values go through the map of that Gaussian -- a NaN stays a NaN
  *   gmmiv_frame_moments_groups    NOT screened: like gmmiv_frame_moments, a NaN goes into the sums of its group
@@ -465,6 +466,48 @@ typedef struct gmmiv_model_tile {
 } gmmiv_model_tile;
 int64_t gmmiv_plan_model_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int tile_frames,
                                gmmiv_model_tile *tiles, int64_t cap);
+
+/* ---- batched channel compensation: a session model and an offset per segment ------------------------------------------------------
+ * gmmiv_feat_compensate for MANY sessions at once (JFAAcc::normalizeFeatures loops over the sessions, ComputeTestJFA over the ndx
+ * lines, each with its own model m + Vy + Dz + Ux_h and its own offset U x_h).  Segment s = frames [seg_begin[s], seg_begin[s+1]) is
+ * rewritten with the full posterior of model seg_model[s] of the batch and the offset row offset + seg_model[s] * offset_stride
+ * ([C x D] doubles, host or device; offset_stride 0 = one row shared by all models, else >= C * D):
+ *   out[t][i] = x[t][i] - sum_c gamma_tc offset_row[c * D + i].
+ * seg_begin / seg_model are HOST arrays as in gmmiv_llk_models (a device table is GMMIV_ERR_ARG); the call waits once for its table
+ * upload, like the other *_models calls, and otherwise only enqueues when x, offset and out are device arrays.  Frames before
+ * seg_begin[0] and from seg_begin[nseg] on belong to no segment: they are neither read from x nor written to out (a host out is staged
+ * and copied back for the frames of the segments only; padding columns are never written).  Everything gmmiv_feat_compensate promises
+ * carries over: x_dtype / out_dtype independent with fp64 arithmetic; out may be exactly x (same pointer, dtype and stride), any other
+ * overlap is GMMIV_ERR_ARG; every argument error (a batch of another context, seg_model outside [0, G), a decreasing table,
+ * offset == NULL, a bad dtype or stride) is reported before anything is enqueued; T = 0 and nseg = 0 are valid; unusable and
+ * zero-likelihood frames are copied through and counted once in "zero_llk_frames" / "screened_frames".
+ * Work is cut into chunks of whole segments like gmmiv_tv_stats_models (frames that fit "z_scratch_mb", distinct models that fit
+ * "models_scratch_mb"; the packed offsets of a chunk's models take 16 C ceil(D / 16) doubles each on top).  Per chunk: one model
+ * pack, one offset pack, k_llk_mfma<WZ> with a model per tile, k_feat_comp with a segment per wave.  A frame has the bits
+ * gmmiv_feat_compensate gives it on a single-model handle, whatever its row in a 16-frame block, its chunk or its neighbours.  In
+ * place across a chunk boundary is right by construction: the log-likelihood kernel loads the rows outside its chunk's segments as
+ * 0, so a row the previous chunk has rewritten is never evaluated.  Shapes without the stored-likelihood path (vectSize > 60,
+ * "stats_z" 0) and calls with a segment longer than the scratch walk the segments one by one through gmmiv_feat_compensate on a
+ * single-model handle: the same definition, launch-bound.
+ * Kernel timers: "k_gmm_pack", "k_llk_mfma", "k_feat_comp". */
+int gmmiv_feat_compensate_models(gmmiv_ctx *ctx, const gmmiv_gmm_batch *b, const void *x, int x_dtype, int64_t T, int64_t ldx,
+                                 const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, const double *offset,
+                                 int64_t offset_stride, void *out, int out_dtype, int64_t ldo);
+
+/* The work list of the segment-aware k_feat_comp (pure host function, the conventions of gmmiv_plan_model_tiles).  One entry per
+ * wave: the 16-frame blocks [block, block + blocks_per_tile) (block b = frames [16 b, 16 b + 16)) and the frames [lo, hi) of segment
+ * `seg` inside them, 16 block <= lo < hi <= 16 (block + blocks_per_tile), under model `model` = seg_model[seg].  The entries of a
+ * segment start at the block holding its first frame and step by blocks_per_tile; entries are sorted by (seg, block), so the items of
+ * one segment -- which read the same packed offset -- are adjacent; an empty segment has none.  Returns the number of entries
+ * (entries beyond `cap` are counted, not written; tiles may be NULL), or -1 for a decreasing seg_begin, blocks_per_tile < 1 or
+ * nseg < 0. */
+typedef struct gmmiv_feat_tile {
+    int64_t block;
+    int64_t lo, hi;
+    int32_t model, seg;
+} gmmiv_feat_tile;
+int64_t gmmiv_plan_feat_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int blocks_per_tile,
+                              gmmiv_feat_tile *tiles, int64_t cap);
 
 /* ---- A WHOLE LIST OF TRIALS: batched ComputeTest ---------------------------------------------------------------------------------------
  * ComputeTest (ComputeTest.cpp:129-215) scores every line of an ndx -- a test file against its handful of clients out of thousands --

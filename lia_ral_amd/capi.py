@@ -41,6 +41,7 @@ def _load():
     lib.gmmiv_comm_take_bytes.restype = ct.c_double
     lib.gmmiv_ctx_stream.restype = ct.c_void_p
     lib.gmmiv_plan_model_tiles.restype = ct.c_int64
+    lib.gmmiv_plan_feat_tiles.restype = ct.c_int64
     lib.gmmiv_plan_trial_tiles.restype = ct.c_int64
     lib.gmmiv_plan_score_lists.restype = ct.c_int64
     return lib
@@ -1032,6 +1033,31 @@ def plan_model_tiles(seg_begin, seg_model, tile_frames=256):
     return [{k: getattr(buf[i], k) for k, _ in ModelTile._fields_} for i in range(int(n))]
 
 
+class FeatTile(ct.Structure):
+    """gmmiv_feat_tile: one wave of the segment-aware k_feat_comp"""
+    _fields_ = [("block", ct.c_int64), ("lo", ct.c_int64), ("hi", ct.c_int64), ("model", ct.c_int32), ("seg", ct.c_int32)]
+
+
+def plan_feat_tiles(seg_begin, seg_model, blocks_per_tile=2, cap=None, count_only=False):
+    """gmmiv_plan_feat_tiles (host only, needs no GPU) -> list of dicts block / lo / hi / model / seg, sorted by (seg, block); cap: at
+    most that many entries are written (-> (count, the written entries)); count_only: the count alone (tiles = NULL)"""
+    sb = np.ascontiguousarray(seg_begin, np.int64)
+    sm = np.ascontiguousarray(seg_model, np.int32)
+    nseg = len(sb) - 1
+    assert len(sm) == nseg
+    args = (sb.ctypes.data_as(ct.c_void_p), sm.ctypes.data_as(ct.c_void_p), ct.c_int64(nseg), int(blocks_per_tile))
+    n = lib.gmmiv_plan_feat_tiles(*args, ct.c_void_p(0), ct.c_int64(0))
+    if n < 0:
+        raise GmmivError("gmmiv_plan_feat_tiles: bad argument")
+    if count_only:
+        return int(n)
+    room = int(n) if cap is None else int(cap)
+    buf = (FeatTile * max(room, 1))()
+    n2 = lib.gmmiv_plan_feat_tiles(*args, ct.cast(buf, ct.c_void_p), ct.c_int64(room))
+    tiles = [{k: getattr(buf[i], k) for k, _ in FeatTile._fields_} for i in range(min(int(n2), room))]
+    return tiles if cap is None else (int(n2), tiles)
+
+
 TRIAL_PIECE = int(lib.gmmiv_trial_piece(None))  # GMMIV_TRIAL_PIECE, read from the library: frames per work item of gmmiv_llr_trials
 
 
@@ -1157,6 +1183,27 @@ class GmmBatch:
         _chk(lib.gmmiv_em_stats_models(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
                                        sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(N), _ptr(F), _ptr(S), _ptr(seg_llk)))
         return N, F, S, seg_llk
+
+    def feat_compensate(self, x, seg_begin, seg_model, offsets, out=None, out_dtype=None):
+        """gmmiv_feat_compensate_models: segment s of x is rewritten as out[t] = x[t] - sum_c gamma_tc offsets[seg_model[s]][c] with the
+        full posteriors of model seg_model[s].  offsets: [C, D] (shared) or [G, C, D], numpy or torch device.  x, out as in
+        Gmm.feat_compensate (row-strided views allowed, out=x is in place); frames of no segment are not touched: with out=None they
+        are x's own (the fresh output starts as a copy of x in out_dtype)."""
+        x, dt, T, ldx = _feat_view(x)
+        sb, sm = self._segs(seg_begin, seg_model)
+        if out is None:
+            out = _feat_like(x, dt if out_dtype is None else out_dtype)
+            if _is_torch(out):
+                out.copy_(x)
+            else:
+                out[...] = x
+        out, odt, To, ldo = _feat_view(out)
+        assert To == T and out.shape[1] == x.shape[1] == self.D
+        off = offsets if _is_torch(offsets) else np.ascontiguousarray(offsets, np.float64)
+        _chk(lib.gmmiv_feat_compensate_models(self.ctx._h, self._h, _vptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), sb.ctypes.data_as(ct.c_void_p),
+                                              sm.ctypes.data_as(ct.c_void_p), ct.c_int64(len(sm)), _ptr(off),
+                                              ct.c_int64(self._stride(off, self.C * self.D)), _vptr(out), odt, ct.c_int64(ldo)))
+        return out
 
     def llr_trials(self, world, x, seg_begin, trial_seg, trial_model, ctop, complete=True, min_llk=-200.0, max_llk=200.0, llr=None, client_mean=None,
                    world_mean=None):

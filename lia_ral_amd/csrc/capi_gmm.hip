@@ -1230,6 +1230,13 @@ static int feat_check(const char *who, const void *x, int xdt, int64_t T, int64_
     return GMMIV_OK;
 }
 
+// the same two checks for gmmiv_feat_compensate_models (capi_models.hip)
+int gmmiv_feat_check_args(const char *who, const void *x, int xdt, int64_t T, int64_t ldx, const void *out, int odt, int64_t ldo, int D)
+{
+    const int rc = feat_check_dtype(who, xdt, odt);
+    return rc ? rc : feat_check(who, x, xdt, T, ldx, out, odt, ldo, D);
+}
+
 // Device view of the output frames [T x ldo]; a host output is produced compact (ld = D) in WS_FEAT_OUT and copied back by finish().
 struct FeatOut {
     void *d = nullptr, *host = nullptr;

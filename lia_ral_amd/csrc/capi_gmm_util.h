@@ -76,4 +76,6 @@ int count_unusable(gmmiv_ctx *c, const XView &xv, int dt, int64_t T, int D); // 
 int run_lse(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t T, double **lse_out); // WS_LSE; counts zero-likelihood frames
 int generic_gamma_gemm(gmmiv_ctx *c, const gmmiv_gmm *g, const XView &xv, int dt, int64_t t0, int64_t n, const double *lse, bool sq, int NC,
                        double *S);
+// the dtype, stride and overlap rules of gmmiv_feat_compensate / gmmiv_feat_map (GMMIV_ERR_ARG with a message; nothing is enqueued)
+extern "C" int gmmiv_feat_check_args(const char *who, const void *x, int xdt, int64_t T, int64_t ldx, const void *out, int odt, int64_t ldo, int D);
 #pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // capi_models.hip -- C ABI (include/gmmiv.h): a batch of models of one shape, log-likelihood / Baum-Welch statistics with a model per
-// segment, computeMAP for the whole batch.  DESIGN.md section 3.14.
+// segment, channel compensation with a model and an offset per segment, computeMAP for the whole batch.  DESIGN.md sections 3.14, 3.19.
 #include <math.h>
 #include <stdlib.h>
 
@@ -36,6 +36,31 @@ int64_t gmmiv_plan_model_tiles(const int64_t *seg_begin, const int32_t *seg_mode
             // rows of the first / last block that no segment owns: written (as the likelihoods of a zero frame) by the tile next to them
             t.pad_lo = (s == first_ne && f <= b) ? (int32_t)(b - f) : 0;
             t.pad_hi = (s == last_ne && t.hi == e) ? (int32_t)(((e + 15) & ~(int64_t)15) - e) : 0;
+            if (tiles && n < cap) tiles[n] = t;
+            ++n;
+        }
+    }
+    return n;
+}
+
+// the work list of the segment-aware k_feat_comp: per segment, runs of blocks_per_tile 16-frame blocks from the block of its first frame
+int64_t gmmiv_plan_feat_tiles(const int64_t *seg_begin, const int32_t *seg_model, int64_t nseg, int blocks_per_tile, gmmiv_feat_tile *tiles,
+                              int64_t cap)
+{
+    if (!seg_begin || (nseg > 0 && !seg_model) || nseg < 0 || blocks_per_tile < 1 || seg_begin[0] < 0) return -1;
+    for (int64_t s = 0; s < nseg; ++s)
+        if (seg_begin[s + 1] < seg_begin[s]) return -1;
+    int64_t n = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t b = seg_begin[s], e = seg_begin[s + 1];
+        if (e <= b) continue; // an empty segment has no entry
+        for (int64_t blk = b >> 4; blk * 16 < e; blk += blocks_per_tile) {
+            gmmiv_feat_tile t;
+            t.block = blk;
+            t.lo = b > blk * 16 ? b : blk * 16;
+            t.hi = e < (blk + blocks_per_tile) * 16 ? e : (blk + blocks_per_tile) * 16;
+            t.model = seg_model[s];
+            t.seg = (int32_t)s;
             if (tiles && n < cap) tiles[n] = t;
             ++n;
         }
@@ -188,12 +213,16 @@ struct ModelChunk {
     int64_t s0, s1;      // segments [s0, s1)
     int64_t base;        // first frame of the chunk's coordinate system: the 16-frame block holding seg_begin[s0]
     size_t tile_off, ntiles, id_off, nids, seg_off;
+    size_t ftile_off = 0, nftiles = 0; // gmmiv_feat_compensate_models: the chunk's entries of ModelPlan::ftiles
 };
 struct ModelPlan {
     std::vector<ModelChunk> chunks;
     std::vector<gmmiv_model_tile> tiles;
     std::vector<int> ids;
     std::vector<long> segrel;
+    int feat_blocks = 0; // > 0: the work list of the segment-aware k_feat_comp is planned too, with this many blocks per entry
+    std::vector<gmmiv_feat_tile> ftiles;
+    const gmmiv_feat_tile *d_ftiles = nullptr;
     int64_t max_span = 0; // frames from a chunk's base to its end
     int max_models = 0;
     const gmmiv_model_tile *d_tiles = nullptr;
@@ -237,6 +266,18 @@ static bool plan_chunks(const gmmiv_gmm_batch *b, const int64_t *seg_begin, cons
             t.model = slot[t.model];
         }
         ck.ntiles = (size_t)nt;
+        if (p.feat_blocks > 0) { // the same coordinates and model slots for the consumer of the chunk's likelihoods
+            ck.ftile_off = p.ftiles.size();
+            const int64_t nf = gmmiv_plan_feat_tiles(seg_begin + s0, seg_model + s0, s1 - s0, p.feat_blocks, nullptr, 0);
+            p.ftiles.resize(ck.ftile_off + (size_t)nf);
+            gmmiv_plan_feat_tiles(seg_begin + s0, seg_model + s0, s1 - s0, p.feat_blocks, p.ftiles.data() + ck.ftile_off, nf);
+            for (size_t i = ck.ftile_off; i < p.ftiles.size(); ++i) {
+                gmmiv_feat_tile &t = p.ftiles[i];
+                t.block -= ck.base / 16; t.lo -= ck.base; t.hi -= ck.base;
+                t.model = slot[t.model];
+            }
+            ck.nftiles = (size_t)nf;
+        }
         for (size_t i = ck.id_off; i < p.ids.size(); ++i) slot[p.ids[i]] = -1;
         const int64_t span = seg_begin[s1] - ck.base;
         if (span > p.max_span) p.max_span = span;
@@ -257,6 +298,12 @@ static int upload_plan(gmmiv_ctx *c, ModelPlan &p)
     if (!p.tiles.empty()) GCHK(hipMemcpyAsync(dt, p.tiles.data(), p.tiles.size() * sizeof(gmmiv_model_tile), hipMemcpyHostToDevice, c->stream));
     if (!p.ids.empty()) GCHK(hipMemcpyAsync(di, p.ids.data(), p.ids.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     GCHK(hipMemcpyAsync(ds, p.segrel.data(), p.segrel.size() * sizeof(long), hipMemcpyHostToDevice, c->stream));
+    if (!p.ftiles.empty()) {
+        void *df;
+        if ((rc = c->scratch(WS_MB_FTILES, p.ftiles.size() * sizeof(gmmiv_feat_tile), &df))) return rc;
+        GCHK(hipMemcpyAsync(df, p.ftiles.data(), p.ftiles.size() * sizeof(gmmiv_feat_tile), hipMemcpyHostToDevice, c->stream));
+        p.d_ftiles = (const gmmiv_feat_tile *)df;
+    }
     GCHK(hipStreamSynchronize(c->stream)); // the tables live in host vectors
     p.d_tiles = (const gmmiv_model_tile *)dt; p.d_ids = (const int *)di; p.d_seg = (const long *)ds;
     return GMMIV_OK;
@@ -500,6 +547,97 @@ int gmmiv_em_stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x,
                           const int32_t *seg_model, int64_t nseg, double *N, double *F, double *S, double *seg_llk)
 {
     return stats_models(c, b, x, dt, T, ldx, seg_begin, seg_model, nseg, N, F, S, seg_llk, true, "em_stats_models");
+}
+
+// ---- channel compensation with a session model and an offset per segment (include/gmmiv.h) --------------------------------------------
+int gmmiv_feat_compensate_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int dt, int64_t T, int64_t ldx, const int64_t *seg_begin,
+                                 const int32_t *seg_model, int64_t nseg, const double *offset, int64_t offset_stride, void *out, int odt, int64_t ldo)
+{
+    const char *who = "feat_compensate_models";
+    int rc = check_batch(c, b, who);
+    if (rc) return rc;
+    if ((rc = check_segments(b, who, T, seg_begin, seg_model, nseg))) return rc;
+    if (!offset) { gmmiv_set_error("%s: offset == NULL", who); return GMMIV_ERR_ARG; }
+    const size_t CD = (size_t)b->C * b->D;
+    if (offset_stride && offset_stride < (int64_t)CD) { gmmiv_set_error("%s: offset_stride must be 0 (shared) or at least C * D", who); return GMMIV_ERR_ARG; }
+    if ((rc = gmmiv_feat_check_args(who, x, dt, T, ldx, out, odt, ldo, b->D))) return rc;
+    const int64_t F0 = seg_begin[0], F1 = seg_begin[nseg]; // every frame of [F0, F1) belongs to a segment, no other frame does
+    if (T == 0 || nseg == 0 || F1 == F0) return GMMIV_OK;
+    XView xv;
+    if ((rc = xv.init(c, x, dt, T, ldx, b->D))) return rc;
+    // the output as a device view indexed like x; a host output is produced compact for the frames [F0, F1) alone and copied back to
+    // them, so that frames of no segment and padding columns keep what the caller has there
+    char *od = (char *)out;
+    int64_t old = ldo;
+    void *ostage = nullptr;
+    const size_t oes = gmmiv_esize(odt);
+    if (!gmmiv_is_device_ptr(out)) {
+        if ((rc = c->scratch(WS_FEAT_OUT, (size_t)(F1 - F0) * b->D * oes, &ostage))) return rc;
+        old = b->D;
+        od = (char *)ostage - (ptrdiff_t)F0 * old * (ptrdiff_t)oes; // (only frames of [F0, F1) are ever addressed)
+    }
+    auto o_at = [&](int64_t frame) { return (void *)(od + (ptrdiff_t)frame * old * (ptrdiff_t)oes); };
+    auto finish = [&]() -> int {
+        if (ostage) {
+            GCHK(hipMemcpy2DAsync((char *)out + (size_t)F0 * ldo * oes, ldo * oes, ostage, b->D * oes, b->D * oes, (size_t)(F1 - F0), hipMemcpyDeviceToHost, c->stream));
+            GCHK(hipStreamSynchronize(c->stream));
+        }
+        return GMMIV_OK;
+    };
+    DevIn<double> i_off;
+    if ((rc = i_off.init(c, WS_MB_OFFSRC, offset, offset_stride ? (size_t)(b->G - 1) * offset_stride + CD : CD))) return rc;
+    ModelPlan p;
+    p.feat_blocks = gmmk_feat_blocks_per_tile();
+    const int64_t Tc = models_chunk_frames(c, b); // (0 for vectSize > 60: k_feat_comp serves every shape the stored likelihoods exist for)
+    if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
+        if ((rc = upload_plan(c, p))) return rc;
+        const size_t offd = gmmk_feat_offset_doubles(b->nct, b->D);
+        void *pt, *offp;
+        gmmk_zview z;
+        double *lse;
+        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        if ((rc = c->scratch(WS_MB_OFF, (size_t)(p.max_models ? p.max_models : 1) * offd * sizeof(double), &offp))) return rc;
+        if ((rc = gmmiv_z_reserve(c, b->nct, p.max_span, true, &z, &lse))) return rc;
+        bool first = true; // the first launch of the call restarts the kernel timers
+        for (size_t k = 0; k < p.chunks.size(); ++k) {
+            const ModelChunk &ck = p.chunks[k];
+            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
+            if (n <= 0) continue;
+            XView sub;
+            sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+            if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
+            if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
+            c->t_begin("k_gmm_pack", false); // the offsets of the chunk's models, in the order of its model slots
+            GCHK(gmmk_feat_pack_offsets(c->stream, (int)ck.nids, p.d_ids + ck.id_off, i_off.d, (long)offset_stride, b->C, b->D, b->nct, (double *)offp));
+            c->t_end();
+            // In place across a chunk boundary: the log-likelihood kernel loads the rows of its tiles outside their segments as 0, so a
+            // row of a shared 16-frame block that the previous chunk has rewritten is never evaluated; k_feat_comp loads the rows it
+            // writes and no others.
+            const void *xb = gmmiv_x_at(xv, dt, ck.base);
+            c->t_begin("k_llk_mfma", first);
+            GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(), b->nct,
+                                   p.d_tiles + ck.tile_off, (long)ck.ntiles, lse, (int)(c->use_glds & 1), z));
+            c->t_end();
+            GCHK(gmmk_count_dead(c->stream, lse + (f0 - ck.base), (long)n, c->d_zero_llk));
+            c->t_begin("k_feat_comp", first);
+            first = false;
+            GCHK(gmmk_feat_comp_models(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, xb, xv.ldx, (long)(seg_begin[ck.s1] - ck.base), b->D, b->nct, z,
+                                       (const double *)offp, (long)offd, p.d_ftiles + ck.ftile_off, (long)ck.nftiles, o_at(ck.base), old));
+            c->t_end();
+        }
+        return finish();
+    }
+    // launch-bound walk: per segment one model upload and gmmiv_feat_compensate on the single-model handle (device views throughout,
+    // so it stages nothing; it counts its own unusable and zero-likelihood frames)
+    OneModel om;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
+        if (n <= 0) continue;
+        if ((rc = om.set(c, b, seg_model[s]))) return rc;
+        if ((rc = gmmiv_feat_compensate(c, om.g, gmmiv_x_at(xv, dt, f0), dt, n, xv.ldx, i_off.d + (size_t)seg_model[s] * offset_stride, o_at(f0), odt, old)))
+            return rc;
+    }
+    return finish();
 }
 
 // ---- computeMAP for the batch -----------------------------------------------------------------------------------------------------------

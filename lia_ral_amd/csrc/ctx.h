@@ -36,12 +36,13 @@ enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, 
        WS_T9, WS_TIV, WS_LP, WS_AUX, WS_SLAB, WS_SLOTS, WS_FLAGS, WS_Z, WS_EIT, WS_INV,
        WS_GFLAG, WS_NORM, WS_FEAT_OFF, WS_FEAT_OUT, WS_FEAT_IDX, WS_FEAT_M0, WS_FEAT_M1, WS_FEAT_M2, WS_FEAT_M3,
        WS_NORM_OFF, WS_NORM_STATE, WS_NORM_DECAY,
-       WS_MB_PT, WS_MB_TILES, WS_MB_IDS, WS_MB_SEG,
+       WS_MB_PT, WS_MB_TILES, WS_MB_IDS, WS_MB_SEG, WS_MB_OFF, WS_MB_FTILES, WS_MB_OFFSRC,
        WS_TR_IDX, WS_TR_NLLK, WS_TR_LLKW, WS_TR_TILES, WS_TR_TAB, WS_TR_PART, WS_TR_ROW,
        WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask;
                    // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables);
                    // WS_NORM_*: gmmiv_feat_norm_online (chunk offsets of the files, the carried states, the chunks' decay products)
-                   // WS_MB_*: gmmiv_*_models (the packed models of a chunk, the tile tables, the model lists, the segment bounds of all chunks)
+                   // WS_MB_*: gmmiv_*_models (the packed models of a chunk, the tile tables, the model lists, the segment bounds of all chunks;
+                   // gmmiv_feat_compensate_models: the packed offsets of a chunk's models, the k_feat_comp tile tables, staged host offsets)
                    // WS_TR_*: gmmiv_llr_trials (a chunk's world indices / remainders / log-likelihoods, the tile table, the trial and segment
                    // tables, the piece partials of the whole call, one trial's per-frame row on the any-shape path)
 

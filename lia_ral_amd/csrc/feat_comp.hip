@@ -14,10 +14,15 @@ template <> struct feat_store<double> { static __device__ __forceinline__ void p
 // ---- the offset matrix in MFMA B-operand order ----------------------------------------------------------------------------
 // offP[((ct * 4 + s) * NT + nt) * 64 + lane] = offset[16 ct + 4 s + (lane >> 4)][16 nt + (lane & 15)], 0 outside [C x D]: one
 // 512-byte line per (k-step, dimension tile), read by every workgroup in the same order (C x 16 NT doubles, 1 MB at 2048 x 60: it
-// stays in L2 for the whole call).
-__global__ __launch_bounds__(256) void k_feat_pack_offset(const double *__restrict__ off, int C, int D, int nct, int NT, double *__restrict__ offP)
+// stays in L2 for the whole call).  blockIdx.y = slot of a chunk of models (gmmiv_feat_compensate_models): the offsets of model
+// ids[slot], `stride` doubles apart (0 = one row for all), go to the slot's own table -- one launch for all models of the chunk, like
+// k_pack_models.  ids == NULL: the single table of gmmiv_feat_compensate.
+__global__ __launch_bounds__(256) void k_feat_pack_offset(const double *__restrict__ off, long stride, const int *__restrict__ ids, int C, int D, int nct,
+                                                          int NT, double *__restrict__ offP)
 {
     const long tot = (long)nct * 4 * NT * 64;
+    if (ids) off += (size_t)ids[blockIdx.y] * stride;
+    offP += (size_t)blockIdx.y * tot;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < tot; e += (long)gridDim.x * 256) {
         const int lane = (int)(e & 63), nt = (int)((e >> 6) % NT);
         const long cs = (e >> 6) / NT; // ct * 4 + s
@@ -42,23 +47,37 @@ __global__ __launch_bounds__(256) void k_feat_pack_offset(const double *__restri
 #ifndef FEAT_FB // (a second build with -DFEAT_FB=4, loaded through GMMIV_LIB_PATH, prices the other tile shape: DESIGN.md 3.12)
 #define FEAT_FB 2
 #endif
-template <int NT, typename XT, typename OT>
+// SEG (a model per segment, gmmiv_feat_compensate_models): a wave's work item is an entry of `tiles` (gmmiv_plan_feat_tiles,
+// include/gmmiv.h; frames relative to the chunk, n = the chunk's span) instead of the next FB blocks: at most FB consecutive blocks that
+// hold rows [lo, hi) of ONE segment, and the packed offset is the table of the entry's model slot (offP + model * off_stride), so the
+// B registers are still reused over the item's blocks.  A block that several segments share is visited once per segment; every row
+// of it is computed on whatever the scratch holds and only rows of [lo, hi) are loaded from x and written.  The arithmetic of a row is
+// the one above, whatever its row in the block: the bits of the plain kernel under that model.
+template <int NT, typename XT, typename OT, bool SEG = false>
 __global__ __launch_bounds__(256, FEAT_FB <= 2 ? 2 : 1) void k_feat_comp(const void *x, long ldx, long n, int D, int nct,
                                                       const double *__restrict__ zbuf, long nfb, const int *__restrict__ eit,
                                                       const double *__restrict__ inv, const int *__restrict__ efin,
-                                                      const double *__restrict__ offP, void *out, long ldo)
+                                                      const double *__restrict__ offP, void *out, long ldo,
+                                                      const gmmiv_feat_tile *__restrict__ tiles, long ntiles, long off_stride)
 {
     constexpr int FB = FEAT_FB;
     __shared__ double tile[4][FB][16 * 17];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i16 = lane & 15, q = lane >> 4;
-    const long fb0 = ((long)blockIdx.x * 4 + wave) * FB;
-    if (fb0 * 16 >= n) return; // (wave-uniform; the kernel has no workgroup barrier)
+    long fb0 = ((long)blockIdx.x * 4 + wave) * FB;
+    long wlo = 0, whi = n; // the rows written
+    if constexpr (SEG) {
+        if ((long)blockIdx.x * 4 + wave >= ntiles) return; // (wave-uniform)
+        const gmmiv_feat_tile me = tiles[(long)blockIdx.x * 4 + wave];
+        fb0 = me.block; wlo = me.lo; whi = me.hi < n ? me.hi : n;
+        offP += (size_t)me.model * off_stride;
+    }
+    if (fb0 * 16 >= whi) return; // (wave-uniform; the kernel has no workgroup barrier)
     long fbj[FB];
     double fs[FB][4];
     int ef[FB][4];
 #pragma unroll
     for (int j = 0; j < FB; ++j) {
-        fbj[j] = (fb0 + j) * 16 < n ? fb0 + j : fb0; // a block past the end repeats the first one (never written)
+        fbj[j] = (fb0 + j) * 16 < whi ? fb0 + j : fb0; // a block past the end repeats the first one (never written)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const long t = fbj[j] * 16 + q + 4 * r, tc = t < n ? t : n - 1;
@@ -128,11 +147,11 @@ __global__ __launch_bounds__(256, FEAT_FB <= 2 ? 2 : 1) void k_feat_comp(const v
     // lane (i16, q) register r of acc[j][nt]: frame q + 4 r of block j, dimension 16 nt + i16
 #pragma unroll
     for (int j = 0; j < FB; ++j) {
-        if ((fb0 + j) * 16 >= n) continue;
+        if ((fb0 + j) * 16 >= whi) continue;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const long t = (fb0 + j) * 16 + q + 4 * r;
-            if (t >= n) continue;
+            if (t >= whi || (SEG && t < wlo)) continue;
             const bool dead = !(fs[j][r] > 0.0);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -154,10 +173,28 @@ static int launch_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x,
     const int *eit = z.eit, *efin = z.efin;
     const long nfb = z.nfb;
     const unsigned grid = (unsigned)((n + 64 * FEAT_FB - 1) / (64 * FEAT_FB));
-    if (x_f64 && o_f64) k_feat_comp<NT, double, double><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    else if (x_f64) k_feat_comp<NT, double, float><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    else if (o_f64) k_feat_comp<NT, float, double><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
-    else k_feat_comp<NT, float, float><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo);
+    if (x_f64 && o_f64) k_feat_comp<NT, double, double><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo, nullptr, 0, 0);
+    else if (x_f64) k_feat_comp<NT, double, float><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo, nullptr, 0, 0);
+    else if (o_f64) k_feat_comp<NT, float, double><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo, nullptr, 0, 0);
+    else k_feat_comp<NT, float, float><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo, nullptr, 0, 0);
+    return (int)hipGetLastError();
+}
+
+// a model per segment: one wave per entry of the tile table (device array), four entries per workgroup
+template <int NT>
+static int launch_feat_comp_models(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                                   const double *offP, long off_stride, const gmmiv_feat_tile *tiles, long ntiles, void *out, long ldo)
+{
+    const double *zbuf = z.zbuf, *inv = z.inv;
+    const int *eit = z.eit, *efin = z.efin;
+    const long nfb = z.nfb;
+    const unsigned grid = (unsigned)((ntiles + 3) / 4);
+#define FEAT_MM(XT, OT) k_feat_comp<NT, XT, OT, true><<<grid, 256, 0, st>>>(x, ldx, n, D, nct, zbuf, nfb, eit, inv, efin, offP, out, ldo, tiles, ntiles, off_stride)
+    if (x_f64 && o_f64) FEAT_MM(double, double);
+    else if (x_f64) FEAT_MM(double, float);
+    else if (o_f64) FEAT_MM(float, double);
+    else FEAT_MM(float, float);
+#undef FEAT_MM
     return (int)hipGetLastError();
 }
 
@@ -174,7 +211,17 @@ int gmmk_feat_pack_offset(hipStream_t st, const double *off, int C, int D, int n
 #ifdef FEAT_VALU
     if (NT == 4) { k_feat_pack_offset_valu<<<1024, 256, 0, st>>>(off, C, D, nct, offP); return (int)hipGetLastError(); }
 #endif
-    k_feat_pack_offset<<<(unsigned)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024), 256, 0, st>>>(off, C, D, nct, NT, offP);
+    k_feat_pack_offset<<<(unsigned)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024), 256, 0, st>>>(off, 0, nullptr, C, D, nct, NT, offP);
+    return (int)hipGetLastError();
+}
+
+// the offsets of models ids[0 .. n) (device list), `stride` doubles apart, into n tables gmmk_feat_offset_doubles apart: one launch
+int gmmk_feat_pack_offsets(hipStream_t st, int n, const int *ids, const double *off, long stride, int C, int D, int nct, double *offP)
+{
+    if (n <= 0) return 0;
+    const int NT = (D + 15) / 16;
+    const long tot = (long)nct * 4 * NT * 64, nb = (tot + 255) / 256;
+    k_feat_pack_offset<<<dim3((unsigned)(nb < 256 ? nb : 256), (unsigned)n), 256, 0, st>>>(off, stride, ids, C, D, nct, NT, offP);
     return (int)hipGetLastError();
 }
 
@@ -192,6 +239,21 @@ int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx
     case 4: return launch_feat_comp<4>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, out, ldo);
     }
     return -1; // D > 64: the caller takes the generic path
+}
+
+int gmmk_feat_blocks_per_tile(void) { return FEAT_FB; }
+
+int gmmk_feat_comp_models(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                          const double *offP, long off_stride, const gmmiv_feat_tile *tiles, long ntiles, void *out, long ldo)
+{
+    if (n <= 0 || ntiles <= 0) return 0;
+    switch ((D + 15) / 16) {
+    case 1: return launch_feat_comp_models<1>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, off_stride, tiles, ntiles, out, ldo);
+    case 2: return launch_feat_comp_models<2>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, off_stride, tiles, ntiles, out, ldo);
+    case 3: return launch_feat_comp_models<3>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, off_stride, tiles, ntiles, out, ldo);
+    case 4: return launch_feat_comp_models<4>(st, x_f64, o_f64, x, ldx, n, D, nct, z, offP, off_stride, tiles, ntiles, out, ldo);
+    }
+    return -1;
 }
 
 // ---- generic tail: out = x - P, P [n x D] = gamma offset from the fp64 GEMM; a frame whose log-sum is not finite is copied through ----

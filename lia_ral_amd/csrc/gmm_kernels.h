@@ -141,6 +141,12 @@ size_t gmmk_feat_offset_doubles(int nct, int D);
 int gmmk_feat_pack_offset(hipStream_t st, const double *off, int C, int D, int nct, double *offP); // MFMA B-operand order, zero padded
 int gmmk_feat_comp(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
                    const double *offP, void *out, long ldo); // -1: D > 64
+// a model per segment (gmmiv_feat_compensate_models): the offsets of the models ids[0 .. n) of a chunk packed by one launch, and
+// k_feat_comp over a tile table (gmmiv_plan_feat_tiles with gmmk_feat_blocks_per_tile blocks per entry, frames relative to x)
+int gmmk_feat_pack_offsets(hipStream_t st, int n, const int *ids, const double *off, long stride, int C, int D, int nct, double *offP);
+int gmmk_feat_blocks_per_tile(void);
+int gmmk_feat_comp_models(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, int nct, const gmmk_zview &z,
+                          const double *offP, long off_stride, const gmmiv_feat_tile *tiles, long ntiles, void *out, long ldo); // -1: D > 64
 int gmmk_feat_sub(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long n, int D, const double *P, const double *lse, void *out,
                   long ldo);
 int gmmk_feat_map(hipStream_t st, int x_f64, int o_f64, const void *x, long ldx, long T, int D, int C, const int *best, const double *cd_mean,

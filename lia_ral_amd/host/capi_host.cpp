@@ -1110,6 +1110,77 @@ int liagpu_jfa_normalize_features(int device, float *x, long T, int D, long nspk
     })
 }
 
+// The same with the choice of the path: batched = 0 JFAAcc::normalizeFeatures (the per-session loop), 1 JFAAcc::normalizeFeaturesBatch
+int liagpu_jfa_normalize_features_batch(int device, float *x, long T, int D, long nspk, const long *sessPerSpk, const long *clu_off,
+                                        const long *seg_begin, const long *seg_len, int C, const double *w, const double *mean, const double *cov,
+                                        int rankEV, int rankEC, const double *V, const double *U, const double *Dm, const double *Y, const double *X,
+                                        const double *Z, int batched)
+{
+    GUARD({
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD ubm = make_mixture(C, D, w, mean, cov);
+        std::vector<unsigned long> sps(sessPerSpk, sessPerSpk + nspk);
+        JFAAcc jfa(srv, ubm, (unsigned long)rankEV, (unsigned long)rankEC, sps);
+        const size_t SV = (size_t)C * D, nsess = jfa.getNSessions();
+        jfa.loadEV(std::vector<double>(V, V + (size_t)rankEV * SV));
+        jfa.loadEC(std::vector<double>(U, U + (size_t)rankEC * SV));
+        jfa.loadD(std::vector<double>(Dm, Dm + SV));
+        jfa.getY().assign(Y, Y + (size_t)nspk * rankEV);
+        jfa.getX().assign(X, X + nsess * rankEC);
+        jfa.getZ().assign(Z, Z + (size_t)nspk * SV);
+        const std::vector<SegCluster> clusters = clusters_from(clu_off, (long)nsess, seg_begin, seg_len);
+        if (batched) jfa.normalizeFeaturesBatch(fs, clusters);
+        else jfa.normalizeFeatures(fs, clusters);
+        fs.download(x);
+    })
+}
+
+// Timing of the two paths on resident frames (tools/bench_feat_comp_models.py): nsess sessions of frames_per_session frames each, one
+// speaker per session with y = z = 0, session model m + U x_h.  which = 0: normalizeFeaturesBatch, 1: normalizeFeatures (the
+// per-session loop).  ms_out[reps]: host clock around one call with the stream drained before and after (the caller drops warm-ups;
+// every repetition rewrites the frames the previous one left, which changes no amount of work); then one more pass with the kernel
+// timers on: kernel_ms[0..2] = k_gmm_pack, k_llk_mfma, k_feat_comp and kernel_ms[3] = launches of k_feat_comp, all of the LAST library
+// call of the pass (the whole batch for which = 0, the last session alone for which = 1).
+int liagpu_jfa_normalize_features_bench(int device, const float *x, long nsess, long frames_per_session, int D, int C, const double *w,
+                                        const double *mean, const double *cov, int rankEC, const double *U, const double *X, int which, int reps,
+                                        double *ms_out, double *kernel_ms)
+{
+    GUARD({
+        if (which != 0 && which != 1) throw Exception("jfa_normalize_features_bench: which must be 0 (batch) or 1 (per-session loop)");
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)(nsess * frames_per_session), (unsigned long)D);
+        MixtureGD ubm = make_mixture(C, D, w, mean, cov);
+        JFAAcc jfa(srv, ubm, 1, (unsigned long)rankEC, std::vector<unsigned long>((size_t)nsess, 1));
+        jfa.loadEC(std::vector<double>(U, U + (size_t)rankEC * C * D));
+        jfa.getX().assign(X, X + (size_t)nsess * rankEC);
+        std::vector<SegCluster> sel((size_t)nsess);
+        for (long h = 0; h < nsess; ++h) {
+            Seg s;
+            s.begin = (unsigned long)(h * frames_per_session); s.length = (unsigned long)frames_per_session; s.source = 0;
+            sel[(size_t)h].push_back(s);
+        }
+        auto run = [&]() {
+            if (which == 0) jfa.normalizeFeaturesBatch(fs, sel);
+            else jfa.normalizeFeatures(fs, sel);
+            srv.sync();
+        };
+        for (int r = 0; r < reps; ++r) {
+            srv.sync();
+            const auto t0 = std::chrono::steady_clock::now();
+            run();
+            ms_out[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 1);
+        run();
+        kernel_ms[0] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_gmm_pack");
+        kernel_ms[1] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_llk_mfma");
+        kernel_ms[2] = gmmiv_ctx_kernel_ms(srv.ctx(), "k_feat_comp");
+        kernel_ms[3] = (double)gmmiv_ctx_kernel_launches(srv.ctx(), "k_feat_comp");
+        (void)gmmiv_ctx_set_option(srv.ctx(), "timing", 0);
+    })
+}
+
 // liagpu::featureMapping on the frames x [T x D] (rewritten in place) over the cluster (seg_begin, seg_len)[nseg]
 int liagpu_feature_mapping(int device, float *x, long T, int D, const long *seg_begin, const long *seg_len, long nseg, int C, const double *w_cd,
                            const double *mean_cd, const double *cov_cd, const double *w_ci, const double *mean_ci, const double *cov_ci)
@@ -1225,6 +1296,69 @@ static void check_lines(long nlines, const long *line_seg_off, const long *line_
             if (line_clients[k] < 0 || line_clients[k] >= nModels)
                 throw Exception("compute_test_batch: line " + std::to_string(l) + " names client " + std::to_string(line_clients[k]) + " of " + std::to_string(nModels));
     }
+}
+
+// ComputeTestJFA for a whole trial list (computeTestJFABatch): the tables of liagpu_compute_test_batch, every client model of the world's
+// shape, U [rankEC x C*D].  which = 0: computeTestJFABatch; 1: the composition of the existing calls on one accumulator -- the same
+// JFAAcc steps, JFAAcc::normalizeFeatures (the per-session loop) on this call's own copy of the frames, computeTestBatch on the
+// rewritten buffer (the lines' selections must not share frames).  llr_out: one LLR per line and client, line after line; comp_out
+// (nullable) [sum of the selections x D]: the compensated frames, line after line; x_out (nullable) [nlines x rankEC]: the channel factors.
+int liagpu_compute_test_jfa(int device, const float *x, long T, int D, long nlines, const long *line_seg_off, const long *seg_begin, const long *seg_len,
+                            int C, const double *w_world, const double *mean_world, const double *cov_world, int rankEC, const double *U, int nModels,
+                            const double *w_cl, const double *mean_cl, const double *cov_cl, const long *line_cl_off, const long *line_clients,
+                            int topDistribsCount, int complete, double minLLK, double maxLLK, int which, double *llr_out, long max_llr, long *n_llr,
+                            float *comp_out, double *x_out)
+{
+    GUARD({
+        check_lines(nlines, line_seg_off, line_cl_off, line_clients, nModels);
+        if (which != 0 && which != 1) throw Exception("compute_test_jfa: which must be 0 (batch) or 1 (composition of the existing calls)");
+        if (rankEC < 1 || !U || nModels < 1) throw Exception("compute_test_jfa: U with at least one eigenchannel and at least one client model are needed");
+        if (line_cl_off[nlines] > max_llr) throw Exception("compute_test_jfa: llr_out too small");
+        GpuServer srv(device);
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D);
+        MixtureGD world = make_mixture(C, D, w_world, mean_world, cov_world);
+        DeviceMixture dworld(srv, world);
+        const size_t SV = (size_t)C * D;
+        std::vector<MixtureGD> models;
+        for (int g = 0; g < nModels; ++g) models.push_back(make_mixture(C, D, w_cl + (size_t)g * C, mean_cl + g * SV, cov_cl + g * SV));
+        DeviceMixtureBatch batch(srv, models);
+        const std::vector<double> Um(U, U + (size_t)rankEC * SV);
+        std::vector<SegCluster> sel((size_t)nlines);
+        std::vector<std::vector<unsigned long>> cl((size_t)nlines);
+        for (long l = 0; l < nlines; ++l) {
+            sel[(size_t)l] = make_cluster(seg_begin + line_seg_off[l], seg_len + line_seg_off[l], line_seg_off[l + 1] - line_seg_off[l]);
+            cl[(size_t)l].assign(line_clients + line_cl_off[l], line_clients + line_cl_off[l + 1]);
+        }
+        std::vector<std::vector<double>> out;
+        std::vector<float> comp;
+        std::vector<double> xf;
+        if (which == 0)
+            out = computeTestJFABatch(fs, sel, world, Um, (unsigned long)rankEC, dworld, batch, cl, topDistribsCount, complete != 0, minLLK, maxLLK,
+                                      comp_out ? &comp : nullptr, x_out ? &xf : nullptr);
+        else if (nlines > 0) {
+            JFAAcc jfa(srv, world, 1, (unsigned long)rankEC, std::vector<unsigned long>((size_t)nlines, 1));
+            jfa.loadEC(Um);
+            jfa.computeAndAccumulateJFAStat(fs, sel);
+            jfa.estimateUEUT();
+            jfa.estimateAndInverseL_EC();
+            jfa.substractMplusVYplusDZ();
+            jfa.estimateX();
+            xf = jfa.getX();
+            jfa.normalizeFeatures(fs, sel);
+            out = computeTestBatch(fs, sel, dworld, batch, cl, topDistribsCount, complete != 0, minLLK, maxLLK, false);
+            if (comp_out) {
+                std::vector<float> all((size_t)T * D); // the rewritten buffer, its selected rows line after line
+                fs.download(all.data());
+                for (const SegCluster &c : sel)
+                    for (const Seg &s : c) comp.insert(comp.end(), all.begin() + (size_t)s.begin * D, all.begin() + (size_t)(s.begin + s.length) * D);
+            }
+        }
+        long k = 0;
+        for (const auto &o : out) { memcpy(llr_out + k, o.data(), o.size() * sizeof(double)); k += (long)o.size(); }
+        if (n_llr) *n_llr = k;
+        if (comp_out && !comp.empty()) memcpy(comp_out, comp.data(), comp.size() * sizeof(float));
+        if (x_out && !xf.empty()) memcpy(x_out, xf.data(), xf.size() * sizeof(double));
+    })
 }
 
 // models: nModels client models laid out one after the other, model g with model_C[g] Gaussians (model_C == NULL: all have C), covariances

@@ -1729,6 +1729,52 @@ std::vector<double> computeTestLLR(FeatureBuffer &fs, const SegCluster &selected
     return out;
 }
 
+// The tables of a trial list and the scoring of its gathered frames -- what computeTestBatch and computeTestJFABatch share.  The
+// selections of all lines lie one after the other in `all`; a segment of the library call = a selected segment (segmentalMode) or a
+// whole line; every segment of line l is a trial against every client of that line.
+struct LineTrials {
+    SegCluster all;
+    std::vector<int64_t> segBegin;
+    std::vector<int32_t> trialSeg, trialModel;
+    std::vector<size_t> lineSeg;
+    LineTrials(const std::vector<SegCluster> &selectedPerLine, const std::vector<std::vector<unsigned long>> &clientsPerLine, bool segmentalMode)
+        : segBegin(1, 0), lineSeg(selectedPerLine.size() + 1, 0)
+    {
+        for (size_t l = 0; l < selectedPerLine.size(); ++l) {
+            all.insert(all.end(), selectedPerLine[l].begin(), selectedPerLine[l].end());
+            if (segmentalMode)
+                for (const Seg &s : selectedPerLine[l]) segBegin.push_back(segBegin.back() + (int64_t)s.length);
+            else
+                segBegin.push_back(segBegin.back() + (int64_t)totalFrame(selectedPerLine[l]));
+            lineSeg[l + 1] = segBegin.size() - 1;
+            for (size_t s = lineSeg[l]; s < lineSeg[l + 1]; ++s)
+                for (unsigned long g : clientsPerLine[l]) { trialSeg.push_back((int32_t)s); trialModel.push_back((int32_t)g); }
+        }
+    }
+    // x [n x D]: the frames of `all` in its order, on the device (gathered from fs, or a rewritten copy of that gather)
+    std::vector<std::vector<double>> score(FeatureBuffer &fs, const float *x, unsigned long n, DeviceMixture &world, DeviceMixtureBatch &clientModels,
+                                           const std::vector<std::vector<unsigned long>> &clientsPerLine, int topDistribsCount, bool complete, double minLLK,
+                                           double maxLLK) const
+    {
+        GpuServer &srv = fs.server();
+        const size_t L = lineSeg.size() - 1, nseg = segBegin.size() - 1, ntrial = trialSeg.size();
+        topDistribsCount = (int)std::min<unsigned long>((unsigned long)std::max(topDistribsCount, 1), world.getDistribCount());
+        FiniteScope fin(srv, fs);
+        std::vector<double> llr(ntrial, 0.0);
+        srv.check(gmmiv_llr_trials(srv.ctx(), world.handle(), clientModels.handle(), x, GMMIV_F32, (int64_t)n, (int64_t)world.getVectSize(), segBegin.data(),
+                                   (int64_t)nseg, trialSeg.data(), trialModel.data(), (int64_t)ntrial, topDistribsCount,
+                                   complete ? GMMIV_TOP_COMPLETE : GMMIV_TOP_PARTIAL, minLLK, maxLLK, ntrial ? llr.data() : nullptr, nullptr, nullptr));
+        std::vector<std::vector<double>> out(L);
+        size_t k = 0;
+        for (size_t l = 0; l < L; ++l) {
+            const size_t cnt = (lineSeg[l + 1] - lineSeg[l]) * clientsPerLine[l].size();
+            out[l].assign(llr.begin() + k, llr.begin() + k + cnt);
+            k += cnt;
+        }
+        return out;
+    }
+};
+
 std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, DeviceMixture &world,
                                                   const std::vector<MixtureGD> &clientModels,
                                                   const std::vector<std::vector<unsigned long>> &clientsPerLine, int topDistribsCount,
@@ -1808,40 +1854,12 @@ std::vector<std::vector<double>> computeTestBatch(FeatureBuffer &fs, const std::
             if (g >= G) throw Exception("computeTestBatch: client " + std::to_string(g) + " outside the " + std::to_string(G) + " models");
     const unsigned long C = world.getDistribCount(), D = world.getVectSize();
     if (clientModels.getDistribCount() != C || clientModels.getVectSize() != D) throw Exception("computeTestBatch: the batch has another shape than the world model");
-    std::vector<std::vector<double>> out(L);
-    if (L == 0) return out;
-    GpuServer &srv = fs.server();
-    topDistribsCount = (int)std::min<unsigned long>((unsigned long)std::max(topDistribsCount, 1), C);
+    if (L == 0) return std::vector<std::vector<double>>();
     // one gather of all lines' frames, line after line; a segment of the call = a selected segment (segmentalMode) or a whole line
-    SegCluster all;
-    std::vector<int64_t> segBegin(1, 0);
-    std::vector<int32_t> trialSeg, trialModel;
-    std::vector<size_t> lineSeg(L + 1, 0);
-    for (size_t l = 0; l < L; ++l) {
-        all.insert(all.end(), selectedPerLine[l].begin(), selectedPerLine[l].end());
-        if (segmentalMode)
-            for (const Seg &s : selectedPerLine[l]) segBegin.push_back(segBegin.back() + (int64_t)s.length);
-        else
-            segBegin.push_back(segBegin.back() + (int64_t)totalFrame(selectedPerLine[l]));
-        lineSeg[l + 1] = segBegin.size() - 1;
-        for (size_t s = lineSeg[l]; s < lineSeg[l + 1]; ++s)
-            for (unsigned long g : clientsPerLine[l]) { trialSeg.push_back((int32_t)s); trialModel.push_back((int32_t)g); }
-    }
-    const size_t nseg = segBegin.size() - 1, ntrial = trialSeg.size();
+    const LineTrials lt(selectedPerLine, clientsPerLine, segmentalMode);
     unsigned long n = 0;
-    const float *x = fs.select(all, n);
-    FiniteScope fin(srv, fs);
-    std::vector<double> llr(ntrial, 0.0);
-    srv.check(gmmiv_llr_trials(srv.ctx(), world.handle(), clientModels.handle(), x, GMMIV_F32, (int64_t)n, (int64_t)D, segBegin.data(), (int64_t)nseg, trialSeg.data(),
-                               trialModel.data(), (int64_t)ntrial, topDistribsCount, complete ? GMMIV_TOP_COMPLETE : GMMIV_TOP_PARTIAL, minLLK, maxLLK,
-                               ntrial ? llr.data() : nullptr, nullptr, nullptr));
-    size_t k = 0;
-    for (size_t l = 0; l < L; ++l) {
-        const size_t cnt = (lineSeg[l + 1] - lineSeg[l]) * clientsPerLine[l].size();
-        out[l].assign(llr.begin() + k, llr.begin() + k + cnt);
-        k += cnt;
-    }
-    return out;
+    const float *x = fs.select(lt.all, n);
+    return lt.score(fs, x, n, world, clientModels, clientsPerLine, topDistribsCount, complete, minLLK, maxLLK);
 }
 
 WindowLLR::WindowLLR(unsigned long size, unsigned long dec, unsigned long nClient)
@@ -2598,6 +2616,68 @@ void JFAAcc::normalizeFeatures(FeatureBuffer &fs, const std::vector<SegCluster> 
         fs.scatter(segsPerSession[h], x);
     }
 }
+void JFAAcc::compensateSessions(const FeatureBuffer &fs, const float *x, unsigned long n, const std::vector<int64_t> &sessBegin, float *out)
+{
+    if (sessBegin.size() != _n_sessions + 1 || sessBegin.back() != (int64_t)n) throw Exception("compensateSessions: one row range per session expected");
+    if (n == 0) return;
+    // the two products of normalizeFeatures: U x_h and m + V y_s + D z_s + U x_h of ALL sessions
+    DVec ux(_srv), sp(_srv), wts(_srv);
+    std::vector<double> n1(_n_sessions * _n_distrib, -1.0);
+    ux.assign(_n_sessions * _svSize, 0.0);
+    sp.assign(_n_sessions * _svSize, 0.0);
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), ux.dev(), nullptr, (int64_t)_n_sessions,
+                                  nullptr, (int)_rankEC, _matU.cdev(), _matX.cdev(), nullptr, nullptr));
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), sp.dev(), _owner.data(), (int64_t)_n_speakers,
+                                  _ubm_means.cdev(), (int)_rankEV, _V.cdev(), _Y.cdev(), _D.cdev(), _Z.cdev()));
+    _srv.check(gmmiv_jfa_subtract(_srv.ctx(), (int64_t)_n_sessions, (int)_n_distrib, (int)_vectSize, n1.data(), sp.dev(), nullptr, (int64_t)_n_sessions,
+                                  nullptr, (int)_rankEC, _matU.cdev(), _matX.cdev(), nullptr, nullptr));
+    wts.set(_ubm.weights());
+    // the session models as ONE batch from the device rows: weights and variances stay the UBM's (shared rows), the means per session
+    struct Batch {
+        gmmiv_gmm_batch *b = nullptr;
+        ~Batch() { if (b) gmmiv_gmm_batch_destroy(b); }
+    } batch;
+    _srv.check(gmmiv_gmm_batch_create(_srv.ctx(), (int)_n_sessions, (int)_n_distrib, (int)_vectSize, &batch.b));
+    _srv.check(gmmiv_gmm_batch_load(batch.b, wts.cdev(), 0, sp.cdev(), (int64_t)_svSize, _ubm_invvar.cdev(), 0));
+    std::vector<int32_t> model(_n_sessions);
+    for (unsigned long h = 0; h < _n_sessions; ++h) model[h] = (int32_t)h;
+    FiniteScope fin(_srv, fs);
+    _srv.check(gmmiv_feat_compensate_models(_srv.ctx(), batch.b, x, GMMIV_F32, (int64_t)n, (int64_t)_vectSize, sessBegin.data(), model.data(),
+                                            (int64_t)_n_sessions, ux.cdev(), (int64_t)_svSize, out, GMMIV_F32, (int64_t)_vectSize));
+}
+void JFAAcc::normalizeFeaturesBatch(FeatureBuffer &fs, const std::vector<SegCluster> &segsPerSession)
+{
+    if (segsPerSession.size() != _n_sessions) throw Exception("normalizeFeaturesBatch: one SegCluster per session expected");
+    if (fs.getVectSize() != _vectSize) throw Exception("normalizeFeaturesBatch: the features' vectSize differs from the model's");
+    if (&fs.server() != &_srv) throw Exception("normalizeFeaturesBatch: the feature buffer must live on the accumulator's server (the frames are rewritten in stream order)");
+    // Two sessions that share a frame: the per-session loop compensates it twice, the second time as the first has left it -- it depends
+    // on the order, one gather of all sessions does not.  Such a list takes the loop.
+    std::vector<std::pair<std::pair<unsigned long, unsigned long>, unsigned long>> segs; // ((first frame, end frame), session), sorted by frame
+    for (unsigned long h = 0; h < _n_sessions; ++h)
+        for (const Seg &s : segsPerSession[h])
+            if (s.length) {
+                const unsigned long b = s.begin + fs.getFirstFeatureIndexOfASource(s.source);
+                segs.push_back(std::make_pair(std::make_pair(b, b + s.length), h));
+            }
+    std::sort(segs.begin(), segs.end());
+    unsigned long end = 0, owner = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        if (i && segs[i].first.first < end && segs[i].second != owner) { normalizeFeatures(fs, segsPerSession); return; }
+        if (!i || segs[i].first.second > end) { end = segs[i].first.second; owner = segs[i].second; }
+    }
+    // the selections of all sessions gathered once, session after session; one library call; one scatter
+    SegCluster all;
+    std::vector<int64_t> begin(_n_sessions + 1, 0);
+    for (unsigned long h = 0; h < _n_sessions; ++h) {
+        all.insert(all.end(), segsPerSession[h].begin(), segsPerSession[h].end());
+        begin[h + 1] = begin[h] + (int64_t)totalFrame(segsPerSession[h]);
+    }
+    unsigned long n = 0;
+    float *x = fs.selectForUpdate(all, n);
+    if (n == 0) return;
+    compensateSessions(fs, x, n, begin, x);
+    fs.scatter(all, x);
+}
 void featureMapping(MixtureGD &ci, MixtureGD &cd, FeatureBuffer &fs, const SegCluster &selectedSegments)
 {
     if (ci.getDistribCount() != cd.getDistribCount() || ci.getVectSize() != cd.getVectSize() || cd.getVectSize() != fs.getVectSize())
@@ -2611,6 +2691,49 @@ void featureMapping(MixtureGD &ci, MixtureGD &cd, FeatureBuffer &fs, const SegCl
     srv.check(gmmiv_feat_map(srv.ctx(), dcd.handle(), cd.means().data(), cd.covs().data(), ci.means().data(), ci.covs().data(), x, GMMIV_F32, (int64_t)n, D,
                              x, GMMIV_F32, D, nullptr));
     fs.scatter(selectedSegments, x);
+}
+
+std::vector<std::vector<double>> computeTestJFABatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, const MixtureGD &world,
+                                                     const std::vector<double> &U, unsigned long rankEC, DeviceMixture &dworld,
+                                                     DeviceMixtureBatch &clientModels, const std::vector<std::vector<unsigned long>> &clientsPerLine,
+                                                     int topDistribsCount, bool complete, double minLLK, double maxLLK,
+                                                     std::vector<float> *compensated, std::vector<double> *channelFactors)
+{
+    const size_t L = selectedPerLine.size(), G = clientModels.size();
+    if (clientsPerLine.size() != L) throw Exception("computeTestJFABatch: one client list per line is needed");
+    for (const auto &cl : clientsPerLine)
+        for (unsigned long g : cl)
+            if (g >= G) throw Exception("computeTestJFABatch: client " + std::to_string(g) + " outside the " + std::to_string(G) + " models");
+    const unsigned long C = world.getDistribCount(), D = world.getVectSize();
+    if (clientModels.getDistribCount() != C || clientModels.getVectSize() != D || dworld.getDistribCount() != C || dworld.getVectSize() != D ||
+        fs.getVectSize() != D)
+        throw Exception("computeTestJFABatch: the world model, the client batch and the features must have one shape");
+    if (compensated) compensated->clear();
+    if (channelFactors) channelFactors->clear();
+    if (L == 0) return std::vector<std::vector<double>>();
+    GpuServer &srv = fs.server();
+    // every line's test file is one speaker with one session; y = z = 0, so V and D (zero here) play no part
+    JFAAcc jfa(srv, world, 1, rankEC, std::vector<unsigned long>(L, 1));
+    jfa.loadEC(U);
+    jfa.computeAndAccumulateJFAStat(fs, selectedPerLine);
+    jfa.estimateUEUT();
+    jfa.estimateAndInverseL_EC();
+    jfa.substractMplusVYplusDZ();
+    jfa.estimateX();
+    if (channelFactors) *channelFactors = jfa.getX();
+    // the compensation rewrites a COPY of the gathered frames (the reference rewrites a FeatureServer that dies with the line): the
+    // caller's buffer keeps its frames, also when the gather is a view into it
+    const LineTrials lt(selectedPerLine, clientsPerLine, false);
+    unsigned long n = 0;
+    const float *x = fs.select(lt.all, n);
+    float *xc = (float *)srv.workspace(6, (size_t)(n ? n : 1) * D * sizeof(float));
+    jfa.compensateSessions(fs, x, n, lt.segBegin, xc);
+    if (compensated) {
+        compensated->resize((size_t)n * D);
+        srv.sync();
+        if (n) hipcheck(hipMemcpy(compensated->data(), xc, (size_t)n * D * sizeof(float), hipMemcpyDeviceToHost), "computeTestJFABatch: download");
+    }
+    return lt.score(fs, xc, n, dworld, clientModels, clientsPerLine, topDistribsCount, complete, minLLK, maxLLK);
 }
 
 std::vector<double> computeTestDotProduct(GpuServer &srv, JFAAcc &jfaAcc, const std::vector<double> &clientSV, unsigned long nClients)

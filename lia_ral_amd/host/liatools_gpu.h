@@ -661,6 +661,15 @@ class JFAAcc {
     // come from one product each; per session: the session model is set, the cluster's frames are selected, compensated in one call
     // of gmmiv_feat_compensate and scattered back -- one library call per session, not one per label segment.
     void normalizeFeatures(FeatureBuffer &fs, const std::vector<SegCluster> &segsPerSession);
+    // The same for ALL sessions in one device pass (opt-in): the session models as one gmmiv_gmm_batch loaded from the device rows, the
+    // selections of all sessions gathered once, session after session (the way adaptModelBatch / computeTestBatch lay theirs out), one
+    // gmmiv_feat_compensate_models, one scatter.  A frame gets the bits normalizeFeatures gives it.  If the clusters of two sessions
+    // share a frame the per-session loop depends on the order of the sessions and a single gather does not: such a list runs
+    // normalizeFeatures.
+    void normalizeFeaturesBatch(FeatureBuffer &fs, const std::vector<SegCluster> &segsPerSession);
+    // the core of it on frames that are already gathered: rows [sessBegin[h], sessBegin[h + 1]) of x [n x vectSize] (device, float32)
+    // are session h's; out (device) may be x or a matrix that does not overlap it.  fs: the buffer the frames came from (screening).
+    void compensateSessions(const FeatureBuffer &fs, const float *x, unsigned long n, const std::vector<int64_t> &sessBegin, float *out);
     std::vector<double> &getV() { return _V.host(); }
     std::vector<double> &getU() { return _matU.host(); }
     std::vector<double> &getD() { return _D.host(); }
@@ -697,6 +706,18 @@ void estimateDMatrix(JFAAcc &jfaAcc, unsigned long nbIt);                     //
 // ComputeTest in the JFA framework, dot-product scoring (ComputeTest.cpp:303-358): every statistics row of jfaAcc is one test
 // segment (one session, y = z = 0); returns scores[nTest x nClients] = <client supervector, channel-compensated mean statistics>
 std::vector<double> computeTestDotProduct(GpuServer &srv, JFAAcc &jfaAcc, const std::vector<double> &clientSV, unsigned long nClients);
+// ComputeTest in the JFA framework, LLR scoring (ComputeTestJFA, ComputeTest.cpp:376-569) for a WHOLE ndx: per line the channel factor
+// of the test file is estimated (statistics, estimateUEUT, substractMplusVYplusDZ, estimateX -- one speaker with one session per line,
+// y = z = 0, so V and D play no part, as in the reference, where they multiply zero factors), its selected frames are compensated
+// (o_t - sum_c gamma_tc (U x)_c under the model m + U x) and scored like computeTestBatch scores them: worldDecime = 1, one LLR per
+// line and client.  All lines go through one statistics pass, one batched solve, one gmmiv_feat_compensate_models and one
+// gmmiv_llr_trials.  fs is NOT rewritten: the compensation works on a copy of the gathered frames.  U [rankEC x C*D]; compensated
+// (nullable): the compensated frames of all lines, line after line [n x D]; channelFactors (nullable): x of every line [L x rankEC].
+std::vector<std::vector<double>> computeTestJFABatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerLine, const MixtureGD &world,
+                                                     const std::vector<double> &U, unsigned long rankEC, DeviceMixture &dworld,
+                                                     DeviceMixtureBatch &clientModels, const std::vector<std::vector<unsigned long>> &clientsPerLine,
+                                                     int topDistribsCount, bool complete, double minLLK, double maxLLK,
+                                                     std::vector<float> *compensated = nullptr, std::vector<double> *channelFactors = nullptr);
 
 // ---- PldaTools.h: PldaDev, the development set of the i-vector back-end (PldaTools.cpp:274-2005) -------------
 // _data [vectSize x n_sessions] (one i-vector per column), sessions grouped by speaker.

@@ -580,8 +580,21 @@ def _clusters(clusters):
     return off, b, l
 
 
-def jfa_normalize_features(x, sess_per_spk, clusters, ubm, V, U, Dm, Y, X, Z, device=0):
-    """JFAAcc::normalizeFeatures on float32 frames: -> (compensated frames, ux [nsess, SV], session model means [nsess, SV])."""
+def jfa_normalize_features(x, sess_per_spk, clusters, ubm, V, U, Dm, Y, X, Z, device=0, batched=None):
+    """JFAAcc::normalizeFeatures on float32 frames: -> (compensated frames, ux [nsess, SV], session model means [nsess, SV]).
+    batched=True: JFAAcc::normalizeFeaturesBatch (all sessions in one device pass), batched=False: the per-session loop; either
+    returns the compensated frames alone.  None: the loop, with the two tables (the call as it always was)."""
+    if batched is not None:
+        w, mean, cov = [np.ascontiguousarray(a, np.float64) for a in ubm]
+        C, D = mean.shape
+        x = np.array(x, np.float32)
+        sps = np.ascontiguousarray(sess_per_spk, np.int64)
+        off, b, l = _clusters(clusters)
+        V, U, Dm, Y, X, Z = [np.ascontiguousarray(a, np.float64) for a in (V, U, Dm, Y, X, Z)]
+        _chk(lib.liagpu_jfa_normalize_features_batch(device, x.ctypes.data_as(_fp), ct.c_long(x.shape[0]), D, ct.c_long(len(sps)), sps.ctypes.data_as(_lp),
+                                                     off.ctypes.data_as(_lp), b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), C, _d(w), _d(mean), _d(cov),
+                                                     V.shape[0], U.shape[0], _d(V), _d(U), _d(Dm), _d(Y), _d(X), _d(Z), int(bool(batched))))
+        return x
     w, mean, cov = [np.ascontiguousarray(a, np.float64) for a in ubm]
     C, D = mean.shape
     x = np.array(x, np.float32)
@@ -709,6 +722,38 @@ def compute_test_batch(x, seg_begin_per_line, seg_len_per_line, world, models, c
         res.append(out[k:k + a * b].reshape(a, b).copy())
         k += a * b
     return res
+
+
+def compute_test_jfa(x, seg_begin_per_line, seg_len_per_line, world, U, models, clients_per_line, top_c=10, complete=True, min_llk=-200.0,
+                     max_llk=200.0, compose=False, device=0):
+    """ComputeTestJFA for a whole trial list (liagpu::computeTestJFABatch): per line the channel factor of the test file from its
+    selected frames, those frames compensated, then the LLR of every client of the line (one per line and client, worldDecime 1).
+    world = (w, mean, cov); U [rankEC, C*D]; models: (w, mean, cov) of the world's shape.  compose=True: the same through the existing
+    calls (JFAAcc steps, the normalizeFeatures loop on a copy of x, computeTestBatch).  x is not rewritten.
+    -> (list of LLR[n_clients], compensated frames [sum of the selections, D] float32 line after line, channel factors [nlines, rankEC])."""
+    x = np.ascontiguousarray(x, np.float32)
+    T, D = x.shape
+    ww, mw, cw = [np.ascontiguousarray(a, np.float64) for a in world]
+    U = np.ascontiguousarray(U, np.float64)
+    so, sb, sl, co, cl = _lines(seg_begin_per_line, seg_len_per_line, clients_per_line, len(models))
+    for m in models:
+        if np.shape(m[1]) != mw.shape:
+            raise HostError("compute_test_jfa: every client model must have the world's shape")
+    if U.ndim != 2 or U.shape[1] != mw.size:
+        raise HostError("compute_test_jfa: U must be [rankEC, C*D]")
+    cat = lambda k: np.ascontiguousarray(np.concatenate([np.asarray(m[k], np.float64).ravel() for m in models]) if models else np.zeros(0))
+    wc, mc, cc = cat(0), cat(1), cat(2)
+    nl = len(so) - 1
+    out = np.empty(max(1, int(co[-1])))
+    comp = np.empty((int(sl.sum()), D), np.float32)
+    xf = np.zeros((nl, U.shape[0]))
+    n = ct.c_long(0)
+    p = lambda a: a.ctypes.data_as(_lp)
+    _chk(lib.liagpu_compute_test_jfa(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(nl), p(so), p(sb), p(sl), len(ww), _d(ww), _d(mw), _d(cw),
+                                     U.shape[0], _d(U), len(models), _d(wc), _d(mc), _d(cc), p(co), p(cl), int(top_c), int(complete),
+                                     ct.c_double(min_llk), ct.c_double(max_llk), int(bool(compose)), _d(out), ct.c_long(len(out)), ct.byref(n),
+                                     comp.ctypes.data_as(_fp), _d(xf)))
+    return [out[int(co[l]):int(co[l + 1])].copy() for l in range(nl)], comp, xf
 
 
 def compute_test_ndx(world_path, ndx_path, model_path, feature_path, label_path, model_ext=".gmm", feature_ext=".prm", label_ext=".lbl", mask="",
