@@ -452,15 +452,18 @@ class Context:
         _chk(lib.gmmiv_dev_cov_mat(self._h, dim, n, xp, k, sp, _ptr(S), _ptr(W), _ptr(B)))
         return S, W, B
 
-    def dev_wccn_chol(self, X, sps):
+    def dev_wccn_chol(self, X, sps, out=None):
+        """out (here and in the estimation calls below): a numpy array or a device tensor of the result's shape, written in place"""
         dim, n, xp, k, sp, keep = self._dev_args(X, sps)
-        out = np.empty((dim, dim))
+        if out is None:
+            out = np.empty((dim, dim))
         _chk(lib.gmmiv_dev_wccn_chol(self._h, dim, n, xp, k, sp, _ptr(out)))
         return out
 
-    def dev_mahalanobis(self, X, sps):
+    def dev_mahalanobis(self, X, sps, out=None):
         dim, n, xp, k, sp, keep = self._dev_args(X, sps)
-        out = np.empty((dim, dim))
+        if out is None:
+            out = np.empty((dim, dim))
         _chk(lib.gmmiv_dev_mahalanobis(self._h, dim, n, xp, k, sp, _ptr(out)))
         return out
 
@@ -470,40 +473,45 @@ class Context:
         _chk(lib.gmmiv_dev_scatter_mat(self._h, dim, n, xp, k, sp, _ptr(SB), _ptr(SW)))
         return SB, SW
 
-    def sym_eigen(self, A, rank=None):
+    def sym_eigen(self, A, rank=None, out=None):
+        """out: (vect [n x rank], val [rank])"""
         n = A.shape[0]; rank = n if rank is None else rank
-        vect = np.empty((n, rank)); val = np.empty(rank)
+        vect, val = (np.empty((n, rank)), np.empty(rank)) if out is None else out
         _chk(lib.gmmiv_sym_eigen(self._h, n, _ptr(_f64(A)), rank, _ptr(vect), _ptr(val)))
         return vect, val
 
-    def dev_efr_matrix(self, Cov):
-        out = np.empty_like(Cov)
+    def dev_efr_matrix(self, Cov, out=None):
+        if out is None:
+            out = np.empty((Cov.shape[0], Cov.shape[0]))
         _chk(lib.gmmiv_dev_efr_matrix(self._h, Cov.shape[0], _ptr(_f64(Cov)), _ptr(out)))
         return out
 
-    def dev_lda(self, W, B, rank):
+    def dev_lda(self, W, B, rank, out=None):
+        """out: (ldaMat [rank x dim], eigval [rank])"""
         dim = W.shape[0]
-        out = np.empty((rank, dim)); val = np.empty(rank)
+        out, val = (np.empty((rank, dim)), np.empty(rank)) if out is None else out
         _chk(lib.gmmiv_dev_lda(self._h, dim, _ptr(_f64(W)), _ptr(_f64(B)), rank, _ptr(out), _ptr(val)))
         return out, val
 
     def plda_em_iteration(self, X, sps, F, G, Sigma, Delta):
-        """One PldaModel::em_iteration, in place on X (centred by Delta), F, G, Sigma, Delta (numpy float64 arrays)."""
+        """One PldaModel::em_iteration, in place on X (centred by Delta), F, G, Sigma, Delta: float64 numpy arrays or device
+        tensors, each on its own (the five ARE the outputs: there is no out=)."""
         dim, n, xp, k, sp, keep = self._dev_args(X, sps)
         _chk(lib.gmmiv_plda_em_iteration(self._h, dim, n, xp, k, sp, F.shape[1], G.shape[1], _ptr(F), _ptr(G), _ptr(Sigma), _ptr(Delta)))
         return X, F, G, Sigma, Delta
 
-    def twocov_model(self, W, B):
+    def twocov_model(self, W, B, out=None):
+        """out: (G, H)"""
         dim = W.shape[0]
-        G = np.empty((dim, dim)); H = np.empty((dim, dim))
+        G, H = (np.empty((dim, dim)), np.empty((dim, dim))) if out is None else out
         _chk(lib.gmmiv_twocov_model(self._h, dim, _ptr(_f64(W)), _ptr(_f64(B)), _ptr(G), _ptr(H)))
         return G, H
 
-    def plda_precompute(self, F, G, Sigma):
-        """-> (FTJ [rf x dim], FTJF [rf x rf]); G may be None."""
+    def plda_precompute(self, F, G, Sigma, out=None):
+        """-> (FTJ [rf x dim], FTJF [rf x rf]); G may be None; out: (FTJ, FTJF)."""
         dim, rf = F.shape
         rg = 0 if G is None else G.shape[1]
-        FTJ = np.empty((rf, dim)); FTJF = np.empty((rf, rf))
+        FTJ, FTJF = (np.empty((rf, dim)), np.empty((rf, rf))) if out is None else out
         _chk(lib.gmmiv_plda_precompute(self._h, dim, rf, rg, _ptr(_f64(F)), _ptr(_f64(G)), _ptr(_f64(Sigma)), _ptr(FTJ), _ptr(FTJF)))
         return FTJ, FTJF
 
@@ -542,6 +550,7 @@ class Context:
         return means, Tm
 
     def tv_orthonormalize_t(self, Tm):
+        """in place on Tm [R x SV], a numpy array or a device tensor (Tm IS the output: there is no out=)"""
         R, SV = Tm.shape
         _chk(lib.gmmiv_tv_orthonormalize_t(self._h, R, ct.c_int64(SV), _ptr(Tm)))
         return Tm

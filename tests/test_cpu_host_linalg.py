@@ -6,7 +6,8 @@ Orders 1, 2, 33, 64; SPD matrices of spd_ref.spd at condition 1e1, 1e3, 1e6; mat
 reported; the eigen routine also at rank < n.  Judged by rules the suite already has: factor, inverse and substitutions by
 spd_ref.accept against the 80-bit reference of tests/spd_ref.py with numpy's error on the same matrix as err_oracle; the eigen
 routine by the assertions of test_efr_lda_and_eigen (values descending, reconstruction within 1e-10 val[0], values within 1e-12
-relative of numpy.linalg.eigh)."""
+relative of numpy.linalg.eigh) and, per pair, per value and per row of V^T V - I, by the bars of tests/estimation_ref.py (the same
+matrices are its "spd" eigen cases)."""
 import os
 import shutil
 import struct
@@ -15,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import estimation_ref as er
 import spd_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,6 +194,11 @@ def test_the_eigen_routine_at_full_and_lower_rank(runs, build):
         else:  # the first `rank` pairs of the full decomposition, unchanged
             full = res[name.replace("_lowrank", "")]
             assert np.array_equal(val, full["val"][:rank]) and np.array_equal(vect, full["vect"][:, :rank]), name
+        # per pair ||A v - l v|| / ||A||_2, per value, per row of V^T V - I, against the 80-bit Jacobi: 16 max(err_double, 64 u)
+        mkey = ("spd", n, [c for c in CONDS if name.endswith("cond%.0e" % c)][0])
+        assert np.array_equal(A, er.eigen_matrix(mkey)), name
+        for kind, r in er.judge("sym_eigen", (mkey, rank), (vect, val)).items():
+            assert np.max(r, initial=0.0) <= 1.0, "%s %s: unit %d at %.3g of its bar" % (name, kind, int(np.argmax(r)), float(np.max(r)))
 
 
 @pytest.mark.parametrize("build", list(BUILDS))

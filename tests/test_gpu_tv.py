@@ -4,7 +4,8 @@ Tolerance: 1e-6 relative on i-vectors (north_star), tighter where conditioning a
 Every criterion here is max|a - b| / max|b| over a whole array.  The judgement per element, per trial and per utterance, against an
 80-bit reference and a bar of that unit's own operands, is tests/test_gpu_tv_elementwise.py for the E- and M-step and
 tests/test_gpu_backend_elementwise.py for the scores, iv_normalize, the development-set statistics, the JFA steps and the
-approximate extractors."""
+approximate extractors, tests/test_gpu_estimation_elementwise.py for the back-end estimation (inverses, eigen problems, PLDA EM,
+tv_orthonormalize_t)."""
 import numpy as np
 import pytest
 
@@ -224,7 +225,7 @@ def test_approximate_extractors_match_oracle(ctx, U, C, D, R):
     assert relerr(ctx.tv_estimate_w_eigen(N, Fn, Tn, Do, Q, C, D, out=acc) - 1.0, w2) < 1e-9
 
 
-@pytest.mark.parametrize("dim,rf,rg", [(40, 10, 6), (200, 50, 0), (400, 100, 80)])
+@pytest.mark.parametrize("dim,rf,rg", [(40, 10, 6), (200, 50, 0), (400, 100, 80), (33, 7, 3)])   # 33: an odd order through SpdBatch::inverse_of
 def test_plda_precompute_and_native_scoring(ctx, dim, rf, rg):
     """PldaModel::preComputation + FTJ / FTJF (PldaTools.cpp:2950-2972, 4494-4496), then the native scoring chain
     rotateLeft(FTJ) -> pldaScoring against the oracle."""
@@ -252,7 +253,7 @@ def _dev_set(dim, sps, seed):
     return X
 
 
-@pytest.mark.parametrize("dim,nspk,seed", [(10, 6, 1), (64, 40, 2), (400, 300, 3)])
+@pytest.mark.parametrize("dim,nspk,seed", [(10, 6, 1), (64, 40, 2), (400, 300, 3), (33, 20, 4)])   # 33: an odd order through SpdBatch::inverse
 def test_backend_estimation_matches_oracle(ctx, dim, nspk, seed):
     """PldaDev::computeAll / computeCovMat / computeWccnChol / computeMahalanobis / computeScatterMat
     (PldaTools.cpp:353-387, 527-566, 1124-1176, 1366-1378, 1610-1644) on the device against the oracle."""
