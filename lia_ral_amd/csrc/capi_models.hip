@@ -317,7 +317,7 @@ static int models_per_chunk(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
 }
 
 // frames per chunk of the stored-likelihood path (multiple of 256), 0 when it does not apply.  The budget of z_chunk_frames
-// (capi_gmm.hip); unlike it, it goes down to one tile: a call of short segments is served with any scratch that holds its longest
+// (capi_gmm_util.h); unlike it, it goes down to one tile: a call of short segments is served with any scratch that holds its longest
 // segment.  24 (lse, 1 / S, Efin) and the rounding are pinned by results: they fix the summation order.
 static int64_t models_chunk_frames(const gmmiv_ctx *c, const gmmiv_gmm_batch *b)
 {
@@ -330,6 +330,41 @@ static int pack_chunk(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const ModelPlan &p
     c->t_begin("k_gmm_pack", first);
     GCHK(gmmk_pack_models(c->stream, (int)ck.nids, p.d_ids + ck.id_off, b->C, b->Cpa, b->D, b->KS, b->nct, b->mean, b->sm, b->iv, b->si, b->a, pt));
     c->t_end();
+    return GMMIV_OK;
+}
+
+// the packed models of the largest chunk of a plan
+static int reserve_packed(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const ModelPlan &p, double **pt)
+{
+    void *q;
+    const int rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &q);
+    *pt = (double *)q;
+    return rc;
+}
+
+// The likelihood stage of one (non-empty) chunk, the same for every batched entry point: the unusable frames of its segments counted, its
+// models packed into pt, k_llk_mfma over its tiles -- the log-sums into lse, indexed from ck.base; with a scratch view z the stored
+// likelihoods too -- and the zero-likelihood frames of its segments counted.  first: this is the first chunk the call launches (the
+// kernel timers restart); the flag is the caller's, which clears it after its own first launch.
+static int llk_chunk(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const XView &xv, int dt, const int64_t *seg_begin, const ModelPlan &p, const ModelChunk &ck,
+                     double *pt, double *lse, const gmmk_zview *z, bool first)
+{
+    const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
+    int rc;
+    XView sub;
+    sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
+    if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
+    if ((rc = pack_chunk(c, b, p, ck, pt, first))) return rc;
+    const void *xb = gmmiv_x_at(xv, dt, ck.base);
+    c->t_begin("k_llk_mfma", first);
+    if (z)
+        GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, pt, (long)b->packed_doubles(), b->nct, p.d_tiles + ck.tile_off,
+                               (long)ck.ntiles, lse, (int)(c->use_glds & 1), *z));
+    else
+        GCHK(gmmk_llk_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, pt, (long)b->packed_doubles(), b->nct, p.d_tiles + ck.tile_off,
+                             (long)ck.ntiles, lse, (int)(c->use_glds & 1)));
+    c->t_end();
+    GCHK(gmmk_count_dead(c->stream, lse + (f0 - ck.base), (long)n, c->d_zero_llk));
     return GMMIV_OK;
 }
 
@@ -348,11 +383,19 @@ struct OneModel {
     }
 };
 
-static int segment_table(gmmiv_ctx *c, int64_t n, long **sb)
+// The head of the walk for segment [f0, f0 + n) of xv under model m: the handle switched to the model, the segment as a view of its
+// own with its unusable frames counted, its log-sums by the single-model kernel (run_lse: WS_LSE, zero-likelihood frames counted) and
+// the one-segment table {0, n}.
+static int walk_segment(gmmiv_ctx *c, const gmmiv_gmm_batch *b, OneModel &om, int m, const XView &xv, int dt, int64_t f0, int64_t n, XView *sub,
+                        double **lse, long **sb)
 {
+    int rc;
+    if ((rc = om.set(c, b, m))) return rc;
+    sub->d = gmmiv_x_at(xv, dt, f0); sub->ldx = xv.ldx;
+    if ((rc = count_unusable(c, *sub, dt, n, b->D))) return rc;
+    if ((rc = run_lse(c, om.g, *sub, dt, n, lse))) return rc;
     void *p;
-    int rc = c->scratch(WS_MB_SEG, 2 * sizeof(long), &p);
-    if (rc) return rc;
+    if ((rc = c->scratch(WS_MB_SEG, 2 * sizeof(long), &p))) return rc;
     GCHK(gmmk_fill_chunks(c->stream, (long *)p, 1, (long)n, (long)n)); // {0, n}, written on the device
     *sb = (long *)p;
     return GMMIV_OK;
@@ -374,24 +417,16 @@ int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int 
     // the plain log-likelihood needs one double of scratch per frame: chunks by models, and by 16 M frames
     if (b->KS <= 15 && plan_chunks(b, seg_begin, seg_model, nseg, (int64_t)1 << 24, models_per_chunk(c, b), p)) {
         if ((rc = upload_plan(c, p))) return rc;
-        void *pt, *lse;
-        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        double *pt;
+        void *lse;
+        if ((rc = reserve_packed(c, b, p, &pt))) return rc;
         if ((rc = c->scratch(WS_LSE, (size_t)(p.max_span > 0 ? p.max_span : 1) * sizeof(double), &lse))) return rc;
         bool first = true; // the first launch of the call restarts the kernel timers
         for (size_t k = 0; k < p.chunks.size(); ++k) {
             const ModelChunk &ck = p.chunks[k];
-            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
-            if (n > 0) {
-                XView sub;
-                sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-                if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
-                if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
-                c->t_begin("k_llk_mfma", first);
+            if (seg_begin[ck.s1] > seg_begin[ck.s0]) {
+                if ((rc = llk_chunk(c, b, xv, dt, seg_begin, p, ck, pt, (double *)lse, nullptr, first))) return rc;
                 first = false;
-                GCHK(gmmk_llk_models(c->stream, b->KS, dt == GMMIV_F64, gmmiv_x_at(xv, dt, ck.base), xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(),
-                                     b->nct, p.d_tiles + ck.tile_off, (long)ck.ntiles, (double *)lse, (int)(c->use_glds & 1)));
-                c->t_end();
-                GCHK(gmmk_count_dead(c->stream, (const double *)lse + (f0 - ck.base), (long)n, c->d_zero_llk));
             }
             GCHK(gmmk_llk_seg_finalize(c->stream, (const double *)lse, p.d_seg + ck.seg_off, (long)(ck.s1 - ck.s0), min_llk, max_llk,
                                        llk ? o_llk.d + ck.base : nullptr, seg_sum ? o_sum.d + ck.s0 : nullptr, nullptr));
@@ -405,14 +440,10 @@ int gmmiv_llk_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, int 
     for (int64_t s = 0; s < nseg; ++s) {
         const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
         if (n <= 0) continue;
-        if ((rc = om.set(c, b, seg_model[s]))) return rc;
         XView sub;
-        sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-        if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
         double *lse;
         long *sb;
-        if ((rc = run_lse(c, om.g, sub, dt, n, &lse))) return rc;
-        if ((rc = segment_table(c, n, &sb))) return rc;
+        if ((rc = walk_segment(c, b, om, seg_model[s], xv, dt, f0, n, &sub, &lse, &sb))) return rc;
         GCHK(gmmk_llk_seg_finalize(c->stream, lse, sb, 1, min_llk, max_llk, llk ? o_llk.d + f0 : nullptr, seg_sum ? o_sum.d + s : nullptr, nullptr));
     }
     if ((rc = o_llk.finish())) return rc;
@@ -441,27 +472,17 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
     const int64_t Tc = models_chunk_frames(c, b);
     if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
         if ((rc = upload_plan(c, p))) return rc;
-        void *pt;
         gmmk_zview z;
-        double *lse;
-        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        double *pt, *lse;
+        if ((rc = reserve_packed(c, b, p, &pt))) return rc;
         if ((rc = gmmiv_z_reserve(c, b->nct, p.max_span, true, &z, &lse))) return rc;
         bool first = true; // the first launch of the call restarts the kernel timers
         for (size_t k = 0; k < p.chunks.size(); ++k) {
             const ModelChunk &ck = p.chunks[k];
-            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
             const void *xb = gmmiv_x_at(xv, dt, ck.base);
-            if (n > 0) {
-                XView sub;
-                sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-                if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
-                if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
-                c->t_begin("k_llk_mfma", first);
+            if (seg_begin[ck.s1] > seg_begin[ck.s0]) {
+                if ((rc = llk_chunk(c, b, xv, dt, seg_begin, p, ck, pt, lse, &z, first))) return rc;
                 first = false;
-                GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(), b->nct,
-                                       p.d_tiles + ck.tile_off, (long)ck.ntiles, lse, (int)(c->use_glds & 1), z));
-                c->t_end();
-                GCHK(gmmk_count_dead(c->stream, lse + (f0 - ck.base), (long)n, c->d_zero_llk));
             }
             // every (segment, c < C) row is written by exactly one wave (zeros for an empty segment, whose likelihood blocks are never read)
             c->t_begin("k_stats_z", k == 0);
@@ -493,15 +514,11 @@ static int stats_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const void *x, i
     for (int64_t s = 0; s < nseg; ++s) {
         const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
         if (n <= 0) continue;
-        if ((rc = om.set(c, b, seg_model[s]))) return rc;
-        const gmmiv_gmm *g = om.g;
         XView sub;
-        sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-        if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
         double *lse;
         long *sb;
-        if ((rc = run_lse(c, g, sub, dt, n, &lse))) return rc;
-        if ((rc = segment_table(c, n, &sb))) return rc;
+        if ((rc = walk_segment(c, b, om, seg_model[s], xv, dt, f0, n, &sub, &lse, &sb))) return rc;
+        const gmmiv_gmm *g = om.g;
         double *Nrow = o_n.d + (size_t)s * b->C, *Frow = o_f.d + (size_t)s * SV;
         if (second) {
             GCHK(hipMemsetAsync(accw, 0, nacc * sizeof(double), c->stream));
@@ -565,25 +582,10 @@ int gmmiv_feat_compensate_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const v
     if (T == 0 || nseg == 0 || F1 == F0) return GMMIV_OK;
     XView xv;
     if ((rc = xv.init(c, x, dt, T, ldx, b->D))) return rc;
-    // the output as a device view indexed like x; a host output is produced compact for the frames [F0, F1) alone and copied back to
-    // them, so that frames of no segment and padding columns keep what the caller has there
-    char *od = (char *)out;
-    int64_t old = ldo;
-    void *ostage = nullptr;
-    const size_t oes = gmmiv_esize(odt);
-    if (!gmmiv_is_device_ptr(out)) {
-        if ((rc = c->scratch(WS_FEAT_OUT, (size_t)(F1 - F0) * b->D * oes, &ostage))) return rc;
-        old = b->D;
-        od = (char *)ostage - (ptrdiff_t)F0 * old * (ptrdiff_t)oes; // (only frames of [F0, F1) are ever addressed)
-    }
-    auto o_at = [&](int64_t frame) { return (void *)(od + (ptrdiff_t)frame * old * (ptrdiff_t)oes); };
-    auto finish = [&]() -> int {
-        if (ostage) {
-            GCHK(hipMemcpy2DAsync((char *)out + (size_t)F0 * ldo * oes, ldo * oes, ostage, b->D * oes, b->D * oes, (size_t)(F1 - F0), hipMemcpyDeviceToHost, c->stream));
-            GCHK(hipStreamSynchronize(c->stream));
-        }
-        return GMMIV_OK;
-    };
+    // the output as a device view indexed like x: a host output is staged for the frames [F0, F1) alone, so that frames of no segment
+    // and padding columns keep what the caller has there
+    FeatOut o;
+    if ((rc = o.init(c, out, odt, F0, F1, ldo, b->D))) return rc;
     DevIn<double> i_off;
     if ((rc = i_off.init(c, WS_MB_OFFSRC, offset, offset_stride ? (size_t)(b->G - 1) * offset_stride + CD : CD))) return rc;
     ModelPlan p;
@@ -592,40 +594,30 @@ int gmmiv_feat_compensate_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const v
     if (Tc > 0 && plan_chunks(b, seg_begin, seg_model, nseg, Tc, models_per_chunk(c, b), p)) {
         if ((rc = upload_plan(c, p))) return rc;
         const size_t offd = gmmk_feat_offset_doubles(b->nct, b->D);
-        void *pt, *offp;
+        void *offp;
         gmmk_zview z;
-        double *lse;
-        if ((rc = c->scratch(WS_MB_PT, (size_t)(p.max_models ? p.max_models : 1) * b->packed_doubles() * sizeof(double), &pt))) return rc;
+        double *pt, *lse;
+        if ((rc = reserve_packed(c, b, p, &pt))) return rc;
         if ((rc = c->scratch(WS_MB_OFF, (size_t)(p.max_models ? p.max_models : 1) * offd * sizeof(double), &offp))) return rc;
         if ((rc = gmmiv_z_reserve(c, b->nct, p.max_span, true, &z, &lse))) return rc;
         bool first = true; // the first launch of the call restarts the kernel timers
         for (size_t k = 0; k < p.chunks.size(); ++k) {
             const ModelChunk &ck = p.chunks[k];
-            const int64_t f0 = seg_begin[ck.s0], n = seg_begin[ck.s1] - f0;
-            if (n <= 0) continue;
-            XView sub;
-            sub.d = gmmiv_x_at(xv, dt, f0); sub.ldx = xv.ldx;
-            if ((rc = count_unusable(c, sub, dt, n, b->D))) return rc;
-            if ((rc = pack_chunk(c, b, p, ck, (double *)pt, first))) return rc;
-            c->t_begin("k_gmm_pack", false); // the offsets of the chunk's models, in the order of its model slots
-            GCHK(gmmk_feat_pack_offsets(c->stream, (int)ck.nids, p.d_ids + ck.id_off, i_off.d, (long)offset_stride, b->C, b->D, b->nct, (double *)offp));
-            c->t_end();
+            if (seg_begin[ck.s1] <= seg_begin[ck.s0]) continue;
             // In place across a chunk boundary: the log-likelihood kernel loads the rows of its tiles outside their segments as 0, so a
             // row of a shared 16-frame block that the previous chunk has rewritten is never evaluated; k_feat_comp loads the rows it
             // writes and no others.
-            const void *xb = gmmiv_x_at(xv, dt, ck.base);
-            c->t_begin("k_llk_mfma", first);
-            GCHK(gmmk_llk_z_models(c->stream, b->KS, dt == GMMIV_F64, xb, xv.ldx, b->D, (const double *)pt, (long)b->packed_doubles(), b->nct,
-                                   p.d_tiles + ck.tile_off, (long)ck.ntiles, lse, (int)(c->use_glds & 1), z));
+            if ((rc = llk_chunk(c, b, xv, dt, seg_begin, p, ck, pt, lse, &z, first))) return rc;
+            c->t_begin("k_gmm_pack", false); // the offsets of the chunk's models, in the order of its model slots
+            GCHK(gmmk_feat_pack_offsets(c->stream, (int)ck.nids, p.d_ids + ck.id_off, i_off.d, (long)offset_stride, b->C, b->D, b->nct, (double *)offp));
             c->t_end();
-            GCHK(gmmk_count_dead(c->stream, lse + (f0 - ck.base), (long)n, c->d_zero_llk));
             c->t_begin("k_feat_comp", first);
             first = false;
-            GCHK(gmmk_feat_comp_models(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, xb, xv.ldx, (long)(seg_begin[ck.s1] - ck.base), b->D, b->nct, z,
-                                       (const double *)offp, (long)offd, p.d_ftiles + ck.ftile_off, (long)ck.nftiles, o_at(ck.base), old));
+            GCHK(gmmk_feat_comp_models(c->stream, dt == GMMIV_F64, odt == GMMIV_F64, gmmiv_x_at(xv, dt, ck.base), xv.ldx, (long)(seg_begin[ck.s1] - ck.base), b->D,
+                                       b->nct, z, (const double *)offp, (long)offd, p.d_ftiles + ck.ftile_off, (long)ck.nftiles, o.at(ck.base), o.ld));
             c->t_end();
         }
-        return finish();
+        return o.finish();
     }
     // launch-bound walk: per segment one model upload and gmmiv_feat_compensate on the single-model handle (device views throughout,
     // so it stages nothing; it counts its own unusable and zero-likelihood frames)
@@ -634,10 +626,10 @@ int gmmiv_feat_compensate_models(gmmiv_ctx *c, const gmmiv_gmm_batch *b, const v
         const int64_t f0 = seg_begin[s], n = seg_begin[s + 1] - f0;
         if (n <= 0) continue;
         if ((rc = om.set(c, b, seg_model[s]))) return rc;
-        if ((rc = gmmiv_feat_compensate(c, om.g, gmmiv_x_at(xv, dt, f0), dt, n, xv.ldx, i_off.d + (size_t)seg_model[s] * offset_stride, o_at(f0), odt, old)))
+        if ((rc = gmmiv_feat_compensate(c, om.g, gmmiv_x_at(xv, dt, f0), dt, n, xv.ldx, i_off.d + (size_t)seg_model[s] * offset_stride, o.at(f0), odt, o.ld)))
             return rc;
     }
-    return finish();
+    return o.finish();
 }
 
 // ---- computeMAP for the batch -----------------------------------------------------------------------------------------------------------

@@ -1343,7 +1343,7 @@ int gmmk_ks_for_dim(int D)
     if (D <= 32) return 8;
     if (D <= 60) return 15;
     if (D <= 80) return 20;
-    return D <= GMMK_MAX_DIM ? GMMK_KS_GENERIC : 0; // no MFMA instantiation: the generic (VALU logits + fp64 GEMM statistics) paths of capi_gmm.hip
+    return D <= GMMK_MAX_DIM ? GMMK_KS_GENERIC : 0; // no MFMA instantiation: the generic (VALU logits + fp64 GEMM statistics) paths of capi_gmm.hip / capi_feat.hip
 }
 int gmmk_rl_for_ks(int KS) { return ((4 * KS + 2 + 31) / 32) * 32; }
 

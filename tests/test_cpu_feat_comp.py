@@ -44,7 +44,7 @@ def test_dtype_errors_come_first_and_argument_checks_precede_any_enqueue():
         assert lib.gmmiv_feat_map(null, null, buf, buf, buf, buf, buf, xdt, i64(1), i64(4), buf, odt, i64(4), null) == -1
         assert b"must be GMMIV_F32 or GMMIV_F64" in lib.gmmiv_last_error()
     assert lib.gmmiv_scatter_runs(null, buf, 5, i64(4), 4, null, i64(0), buf) == -1
-    src = open(os.path.join(CSRC, "capi_gmm.hip")).read()
+    src = open(os.path.join(CSRC, "capi_feat.hip")).read()
     for fn in ("gmmiv_feat_compensate", "gmmiv_feat_map"):
         body = src[src.index("int %s(" % fn):]
         body = body[:body.index("\n}\n")]

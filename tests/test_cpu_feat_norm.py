@@ -69,7 +69,7 @@ def test_dtype_errors_come_first_and_argument_checks_precede_any_enqueue():
     assert lib.gmmiv_feat_norm_apply(null, buf, 1, i64(3), 4, runs, i64(2), i64(2), buf, buf, buf, 1, i64(4)) == -1 and b"bad argument" in lib.gmmiv_last_error()
     assert lib.gmmiv_feat_norm_online(null, buf, 1, i64(4), 4, fb, i64(2), i64(0), i64(0), buf, 1, i64(4)) == -1 and b"bad argument" in lib.gmmiv_last_error()
     assert lib.gmmiv_feat_norm_online(null, buf, 1, i64(4), 4, fb, i64(2), i64(300), i64(-1), buf, 1, i64(4)) == -1 and b"bad argument" in lib.gmmiv_last_error()
-    src = open(os.path.join(CSRC, "capi_gmm.hip")).read()
+    src = open(os.path.join(CSRC, "capi_feat.hip")).read()
     for fn, table in (("gmmiv_feat_norm_apply", "norm_check_runs("), ("gmmiv_feat_norm_online", "file_begin[f + 1] < file_begin[f]")):
         body = src[src.index("int %s(" % fn):]
         body = body[:body.index("\n}\n")]

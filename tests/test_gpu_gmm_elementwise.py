@@ -269,7 +269,7 @@ def test_paths_documented_as_bitwise_equal_are(ctx, case):
 
 
 def chunk_plan(C):
-    """-> (z_scratch_mb, T): the smallest scratch whose chunk (z_chunk_frames, capi_gmm.hip: at least 4096 frames, a multiple of 64)
+    """-> (z_scratch_mb, T): the smallest scratch whose chunk (z_chunk_frames, capi_gmm_util.h: at least 4096 frames, a multiple of 64)
     the library accepts, and a frame count one ragged piece beyond it"""
     nct = ((C + 15) // 16 + 1) // 2 * 2
     per_frame = nct * 16 * 8 + nct * 2 + 16
