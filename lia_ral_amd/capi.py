@@ -192,6 +192,10 @@ class Context:
     def set_option(self, key, value):
         return lib.gmmiv_ctx_set_option(self._h, key.encode(), ct.c_long(value))
 
+    def trial_piece(self):
+        """gmmiv_trial_piece: the frames per work item gmmiv_llr_trials uses on this context ("trials_piece" if set and valid, else TRIAL_PIECE)"""
+        return int(lib.gmmiv_trial_piece(self._h))
+
     def set_hook(self, point, fn):
         """gmmiv_ctx_set_hook: `fn()` is called on the host at `point` ("tv_a_ready": inside tv_estimate_a_and_c once A is
         complete and before the Cmx GEMM is enqueued; "md_factored": inside tv_min_divergence after R is factored, before T is

@@ -426,10 +426,18 @@ __device__ __forceinline__ void topc_rank_frame(const long t, const void *__rest
     srel += wave_sum_f64_dpp((cd && !sel) ? gexp(zc - M) : 0.0);
     const double st = wave_sum_f64_dpp(sel ? gexp(zc - M) : 0.0);
     const bool dead = !(M > GMMIV_ZERO_LLK); // zero-likelihood frame (include/gmmiv.h): the lowest indices, likelihoods 0, llk = lo
-    if (sel) {
-        idx_out[t * ctop + rank] = dead ? rank : ci;
-        if (lk_out) lk_out[t * ctop + rank] = dead ? 0.0 : exp(zc);
-        ord[wave][rank] = dead ? rank : ci;
+    if (dead) {
+        // every rank, not only those a survivor holds: on a frame read as 1e10 the padded Gaussians (constant GMMIV_PAD_LOGIT) outrank
+        // every real one, fill the survivor list and select nothing -- fewer than ctop ranks were written, the rest kept stale values
+        if (lane < ctop) {
+            idx_out[t * ctop + lane] = lane;
+            if (lk_out) lk_out[t * ctop + lane] = 0.0;
+            ord[wave][lane] = lane;
+        }
+    } else if (sel) {
+        idx_out[t * ctop + rank] = ci;
+        if (lk_out) lk_out[t * ctop + rank] = exp(zc);
+        ord[wave][rank] = ci;
     }
     if (lane == 0) {
         const double rest_llk = (srel > 0.0 && !dead) ? M + log(srel) : NINF;
@@ -677,10 +685,16 @@ __global__ __launch_bounds__(256) void k_topc_rank2(const void *__restrict__ x, 
     srel += half_sum_f64_dpp((cd && !sel) ? gexp(zc - M) : 0.0, hi2);
     const double st = half_sum_f64_dpp(sel ? gexp(zc - M) : 0.0, hi2);
     const bool dead = !(M > GMMIV_ZERO_LLK); // zero-likelihood frame (include/gmmiv.h): the lowest indices, likelihoods 0, llk = lo
-    if (sel && alive) {
-        idx_out[t * ctop + rank] = dead ? rank : ci;
-        if (lk_out) lk_out[t * ctop + rank] = dead ? 0.0 : exp(zc);
-        ord[f][32 + rank] = dead ? rank : ci; // the upper half of the row is free (survivors use 0..31)
+    if (dead && alive) { // every rank (k_topc_rank has the reason); ctop <= 16 lanes of the half
+        if (l32 < ctop) {
+            idx_out[t * ctop + l32] = l32;
+            if (lk_out) lk_out[t * ctop + l32] = 0.0;
+            ord[f][32 + l32] = l32;
+        }
+    } else if (sel && alive) {
+        idx_out[t * ctop + rank] = ci;
+        if (lk_out) lk_out[t * ctop + rank] = exp(zc);
+        ord[f][32 + rank] = ci; // the upper half of the row is free (survivors use 0..31)
     }
     if (l32 == 0 && alive) {
         const double rest_llk = (srel > 0.0 && !dead) ? M + log(srel) : NINF;

@@ -19,6 +19,11 @@ bound        derived from what the kernels do, per pair (t, c), u = 2^-53.  The 
                  |d| <= |s| sum_t [gamma_tc (rho_tc + B_t + 8u) + phi] |v_t| + (n + 8) u |s| sum_t gamma_tc |v_t|.
              The direct-form kernels (top-C family, vectSize > 80) are inside the same expression: 1/2 sum (x - mu)^2 iv <= 2 S.
              The linear likelihood w_c lk_c of a selected Gaussian gets rho_tc relative.
+             The top-C chain in both modes (top_llk, use_top): a log-sum over a SUBSET of the logits -- the selected ones, and in
+             COMPLETE mode the world's remainder -- carries the share-weighted rho of the terms in the sum + 4u |llk| + 4u, the
+             form of B_t; PARTIAL is that expression without the remainder term.  clamp() is 1-Lipschitz and keeps a bar; a
+             value that is NaN (a NaN feature) or -inf (every term 0) becomes exactly lo with bar 0, and a zero-likelihood frame
+             (dead(): largest logit not above log 2^-1075) is lo, remainder -inf, selection 0 .. ctop - 1 by definition.
              Derived, not tuned: a float64 numpy restatement of the expanded form (restate) sits well below 1 on every case,
              a dropped term or an fp32 table is orders beyond (tests/test_cpu_gmm_ref.py).
 cases        (C, D, T, spread): the smallest shapes at which the structure of the kernels changes -- the KS instantiations 4 / 8 /
@@ -40,6 +45,8 @@ U = 2.0 ** -53
 PHI = 2.0 ** -960
 FLOOR_ONLY = 2.0 ** -900          # a pair whose reference posterior is below this is judged by phi alone
 LOG_2PI = float(np.log(2.0 * np.pi))
+ZERO_LLK = -745.1332191019412     # log 2^-1075 (GMMIV_ZERO_LLK): a frame whose largest logit is not above it has likelihood 0 in fp64
+UNUSABLE, READ_AS = 1e18, 1e10    # a feature that is NaN, infinite or beyond 1e18 in magnitude is read as 1e10 (feat_sane, devutil.h)
 
 CASES = ((1, 1, 17, 2.0), (2, 1, 65, 2.0), (17, 2, 129, 2.0), (16, 13, 16, 2.0), (33, 16, 257, 2.0), (37, 17, 300, 2.0),
          (64, 32, 255, 2.0), (65, 33, 64, 2.0), (129, 60, 256, 2.0), (300, 60, 130, 2.0), (530, 60, 70, 2.0), (2048, 60, 40, 2.0),
@@ -185,25 +192,72 @@ class Reference:
         order = np.lexsort((np.broadcast_to(np.arange(self.C), self.z.shape), -self.z), axis=1)
         return order[:, :ctop]
 
-    def nontop(self, idx):
-        """log of sum_{c not in idx[t]} exp(z_tc) (-inf when nothing is left) and the share-weighted rho of that sum"""
+    def nontop(self, idx, dead=None):
+        """log of sum_{c not in idx[t]} exp(z_tc) (-inf when nothing is left) and the share-weighted rho of that sum; dead [T]: the
+        zero-likelihood frames (self.dead()), whose remainder is -inf by definition (include/gmmiv.h, "DEGENERATE INPUTS")"""
         mask = np.ones((self.T, self.C), bool)
         np.put_along_axis(mask, idx, False, axis=1)
-        with np.errstate(divide="ignore"):
+        if dead is not None:
+            mask &= ~dead[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
             ln = np.log(np.where(mask, self.gamma, LD(0)).sum(1)) + self.llk
+        if dead is not None:
+            ln = np.where(dead, LD(-np.inf), ln)
         return ln, mask
 
+    def dead(self):
+        """the zero-likelihood frames of include/gmmiv.h: a NaN feature, or the largest logit not above log 2^-1075"""
+        with np.errstate(invalid="ignore"):
+            return ~(self.z.max(1) > LD(ZERO_LLK)) if self.C else np.ones(self.T, bool)
 
-def use_top(client, idx, world_nontop_log, world, mask):
-    """USE_TOP_DISTRIBS, COMPLETE: llk_t = log(sum_{c in idx[t]} exp(z^client_tc) + nontop^world_t) in long double, and its bar:
+    def top_llk(self, idx, complete=True):
+        """DETERMINE_TOP_DISTRIBS' per-frame value before the clamp and its bar.  COMPLETE: the full log-likelihood, bar B_t.
+        PARTIAL: log sum_{c in idx[t]} exp(z_tc), bar = the share-weighted rho of the selected logits + 4u |llk| + 4u."""
+        if complete:
+            return self.llk, self.B
+        z = np.take_along_axis(self.z, idx, axis=1)
+        llk = log_sum_exp(z)
+        with np.errstate(invalid="ignore"):
+            share = np.exp(z - llk[:, None]).astype(np.float64)
+            return llk, (share * np.take_along_axis(self.rho, idx, axis=1)).sum(1) + 4 * U * np.abs(llk.astype(np.float64)) + 4 * U
+
+
+def log_sum_exp(z):
+    """log sum_j exp(z[t, j]) in long double; a row of -inf gives -inf, a row with a NaN gives NaN"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = z.max(1, keepdims=True)
+        m = np.where(np.isfinite(m), m, LD(0))
+        return m[:, 0] + np.log(np.exp(z - m).sum(1))
+
+
+def clamp(v, lo, hi, bar=None):
+    """fmin(fmax(v, lo), hi) on long double: NaN and -inf give lo.  Clamping is 1-Lipschitz, so a frame's bar does not change under
+    it -- except where the value is NaN (a NaN feature) or -inf (every term 0): there the result is lo by definition, bar 0.
+    -> clamped values, or (clamped values, bars) when `bar` is given"""
+    v = np.asarray(v, LD)
+    none = np.isnan(v) | (v == -np.inf)
+    with np.errstate(invalid="ignore"):
+        c = np.where(none, LD(lo), np.minimum(np.maximum(v, LD(lo)), LD(hi)))
+    return c if bar is None else (c, np.where(none, 0.0, np.asarray(bar, np.float64)))
+
+
+def use_top(client, idx, world_nontop_log, world, mask, complete=True):
+    """USE_TOP_DISTRIBS.  COMPLETE: llk_t = log(sum_{c in idx[t]} exp(z^client_tc) + nontop^world_t) in long double, and its bar:
     the share-weighted logit errors of the terms (the client's for the selected Gaussians, the world's for the remainder, which
-    also goes through a log and an exp: 4u |log nontop| more) + 4u |llk| + 4u, as B_t"""
+    also goes through a log and an exp: 4u |log nontop| more) + 4u |llk| + 4u, as B_t.  PARTIAL (complete=False): the same
+    expression without the remainder term, log sum_{c in idx[t]} exp(z^client_tc) and the share-weighted rho of the selected
+    logits + 4u |llk| + 4u.  Before the clamp; a frame with a NaN feature comes back NaN (clamp() makes it lo, bar 0)."""
     zc = np.take_along_axis(client.z, idx, axis=1)
     rc = np.take_along_axis(client.rho, idx, axis=1)
+    if not complete:
+        llk = log_sum_exp(zc)
+        with np.errstate(invalid="ignore"):
+            share = np.exp(zc - llk[:, None]).astype(np.float64)
+            return llk, (share * rc).sum(1) + 4 * U * np.abs(llk.astype(np.float64)) + 4 * U
     allz = np.concatenate([zc, world_nontop_log[:, None]], axis=1)
-    m = allz.max(1, keepdims=True)
-    llk = m[:, 0] + np.log(np.exp(allz - m).sum(1))
-    share = np.exp(allz - llk[:, None]).astype(np.float64)
+    llk = log_sum_exp(allz)
+    with np.errstate(invalid="ignore"):
+        share = np.exp(allz - llk[:, None]).astype(np.float64)
     tot = np.where(mask, world.g64, 0.0).sum(1)
     with np.errstate(invalid="ignore", divide="ignore"):
         rn = np.where(tot > 0, (np.where(mask, world.g64 * world.rho, 0.0).sum(1)) / np.where(tot > 0, tot, 1.0), 0.0)
@@ -243,7 +297,51 @@ def restate(w, mean, iv, x, defect=None):
     gamma = np.exp(z - llk[:, None])
     if isinstance(defect, tuple) and defect[0] == "gamma":
         gamma = defect[1](gamma)
-    return {"llk": llk, "gamma": gamma, "occ": gamma.sum(0), "sx": gamma.T @ x, "sxx": gamma.T @ (x * x)}
+    return {"llk": llk, "gamma": gamma, "occ": gamma.sum(0), "sx": gamma.T @ x, "sxx": gamma.T @ (x * x), "z": z}
+
+
+def restate_top(world, clients, x, idx, complete=True, lo=-1e9, hi=1e9, defect=None):
+    """The top-C chain in float64 numpy, as the kernels evaluate it: the world's logits in the expanded form (restate), its log-sum
+    relative to the largest logit over the selected Gaussians plus -- COMPLETE -- the remainder; the clients' selected logits in
+    the direct form lwc - 1/2 sum (x - mu)^2 iv, their log-sum with the world's remainder (COMPLETE) or alone (PARTIAL); an
+    unusable feature read as 1e10, a frame whose largest world logit is not above log 2^-1075 given lo and remainder -inf; the
+    clamp as fmin(fmax(., lo), hi).  clients: a list of (w, mean, iv).  -> (world llk [T], client llk [G, T]).
+    defect (tests/test_cpu_trials.py): "drop_small_remainder" leaves the remainder out of a COMPLETE frame where its share is
+    below 1e-10; "partial_with_remainder" adds it in PARTIAL mode."""
+    x = x.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        x = np.where(np.abs(x) <= UNUSABLE, x, READ_AS)
+    z = restate(*world, x)["z"]
+    T, C = z.shape
+    M = z.max(1)
+    dead = ~(M > ZERO_LLK)
+    sel = np.zeros((T, C), bool)
+    np.put_along_axis(sel, idx, True, axis=1)
+    rest = complete or defect == "partial_with_remainder"
+    drop = defect == "drop_small_remainder"
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        e = np.exp(z - M[:, None])
+        st, srel = np.where(sel, e, 0.0).sum(1), np.where(sel, 0.0, e).sum(1)
+        tot = st + srel if rest else st
+        if drop:
+            tot = np.where(srel < 1e-10 * tot, st, tot)
+        wl = np.where(dead, lo, np.fmin(np.fmax(M + np.log(tot), lo), hi))
+        nontop = np.where((srel > 0) & ~dead, M + np.log(srel), -np.inf)
+        out = []
+        for w, mean, iv in clients:
+            w, mean, iv = (np.asarray(a, np.float64) for a in (w, mean, iv))
+            D = mean.shape[1]
+            lwc = np.log(w) - 0.5 * D * 1.8378770664093454836 + 0.5 * np.log(iv).sum(1)
+            d = x[:, None, :] - mean[idx]
+            zc = lwc[idx] - 0.5 * (d * d * iv[idx]).sum(2)
+            allz = np.concatenate([zc, nontop[:, None]], axis=1) if rest else zc
+            Mc = allz.max(1)
+            ec = np.exp(allz - Mc[:, None])
+            s = ec.sum(1)
+            if drop and rest:
+                s = np.where(ec[:, -1] < 1e-10 * s, ec[:, :-1].sum(1), s)
+            out.append(np.fmin(np.fmax(Mc + np.log(s), lo), hi))
+    return wl, np.stack(out)
 
 
 def judge(ref, got, s=1.0):

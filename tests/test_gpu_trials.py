@@ -3,6 +3,9 @@ per-frame entry points bit for bit, against the composition it replaces, and the
 
 Tolerances: per-frame values of these kernels agree with the oracle to 1e-9 absolute (test_gpu_gmm.py), so do means of them; an LLR is
 the difference of two.  Two summation orders of the same n values of magnitude <= L differ by at most 2 n 2^-53 L in the mean.
+
+These thresholds see neither the order of the sums nor an error below 1e-9: tests/test_gpu_trials_elementwise.py holds the results
+to the bits of the documented summation order and judges every trial, segment and frame against long double under its own bar.
 """
 import ctypes as ct
 import os
