@@ -187,6 +187,12 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  *   gmmiv_feat_norm_apply         NOT screened: (x - mean) / std of the raw value; std = 0 gives Inf / NaN like computeZeroOne
  *   gmmiv_feat_norm_online        NOT screened: a NaN / Inf frame poisons the running mean and std of its file from there on, like
  *                                 the tool's (1 - B) * f[i]; a running std of 0 gives Inf / NaN
+ *   gmmiv_energy_train            globalCov NOT screened (FrameAccGD: a NaN / Inf energy makes it NaN, and a comparison with NaN is false: no
+ *                                 floor, no ceiling); the EM statistics read the column through feat_sane: a frame of either kind adds nothing
+ *                                 and is not counted; when EVERY frame is one, count = 0: weights 0 / 0 = NaN, means and covariances kept,
+ *                                 status GMMIV_ENERGY_NONFINITE.  Neither counter ("screened_frames", "zero_llk_frames") is bumped.
+ *   gmmiv_energy_select           NOT screened: a frame is in when x > threshold (strict): NaN is out, +Inf and 1e30 are in; a NaN threshold
+ *                                 (an empty file) selects nothing
  * Frames of kind (1) are handled ON THE DEVICE, inside the kernels: every kernel that reads features reads an unusable value as 1e10
  * (csrc/devutil.h, feat_sane: one compare + select where the value is loaded -- in the MFMA log-likelihood kernel once per frame and
  * workgroup, outside its loop).  The value is finite, so no 0 x NaN reaches a statistic, and it puts every logit of the frame near
@@ -281,6 +287,54 @@ int gmmiv_feat_norm_apply(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ld
                           const double *mean /* nullable */, const double *std /* nullable */, void *out, int out_dtype, int64_t ldo);
 int gmmiv_feat_norm_online(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, int D, const int64_t *file_begin, int64_t nfiles,
                            int64_t window, int64_t look_ahead, void *out, int out_dtype, int64_t ldo);
+
+/* ---- EnergyDetector on resident frames (LIA_SpkDet/EnergyDetector/src/EnergyDetector.cpp:118-279, thresholdMode meanStd) for a whole
+ * list of files: gmmiv_energy_train keeps every file's EM chain inside one workgroup of ONE launch, gmmiv_energy_select is selectFrames
+ * as a parallel pass.  x is a DEVICE array and points at the ENERGY COLUMN (a column slice is a pointer offset, as with
+ * gmmiv_feat_norm_apply: x + 16 with ldx = 34); frame t is x[t * ldx], GMMIV_F32 or GMMIV_F64.  Every other array is host or device,
+ * and with device pointers throughout both calls only enqueue on the context's stream.  nfiles = 0, nrun = 0 and files without frames
+ * are valid.
+ *
+ * RUN TABLE: that of the NormFeat calls, runs[3 r + 0 .. 2] = (first frame, length, file); file ids non-decreasing and in [0, nfiles),
+ * a file may have no run; a HOST table that breaks this is GMMIV_ERR_ARG before anything is enqueued, a DEVICE table is not checked.  A
+ * run here is ONE INPUT LABEL SEGMENT of any length -- never cut it: selectFrames' end-of-segment rule depends on where it ends.  A
+ * file's selection is its runs' frames in table order (wherever they lie in the buffer), x_0 .. x_(n-1).
+ *
+ * gmmiv_energy_train, per file, fp64 throughout, a model of C in 1 .. 8 one-dimensional Gaussians:
+ *   globalCov = ss / n - (s / n)^2  (FrameAccGD's biased covariance, the rule of gmmiv_frame_moments; not screened);
+ *   init (:173-193): mean_c = -2 + c 4 / (C - 1) (-2 for C = 1), cov 1, weights 1 / C;
+ *   nb_train_it x ( full-posterior EM statistics occ, sum g x, sum g x^2, count under the zero-likelihood rule of "DEGENERATE INPUTS";
+ *                   gmmiv_em_get's formula: w = occ / count, mean = sum g x / occ, cov = sum g x^2 / occ - mean^2, occ == 0 keeps the previous
+ *                   mean and covariance with weight 0;  gmmiv_variance_control against globalCov: floor test first, then ceiling );
+ *   threshold = mean[higher] - alpha sqrt(cov[higher]), higher = the first index of the largest mean (strict >, findMaxEnergyDistrib).
+ * nb_train_it = 0 is valid (the threshold of the init model).  Outputs: model [nfiles x 3 C] = (w | mean | cov) per file, threshold
+ * [nfiles], status [nfiles] (int32 bit set): GMMIV_ENERGY_EMPTY -- no frame: the model as initialised, threshold NaN, no other bit;
+ * GMMIV_ENERGY_NONFINITE -- the threshold or a model value is not finite; GMMIV_ENERGY_FLOORED / _CEILED -- an entry was floored /
+ * ceiled in the LAST iteration.  No atomics: every sum is 512 strided per-lane partials (lane j adds frames j, j + 512, ... in order),
+ * a wave reduction, the 8 waves added in order -- a function of the file's selection alone, so a file's bits never depend on its
+ * neighbours, its place in the list or the rest of the call.  A selection of at most gmmiv_energy_stage_frames(x_dtype) frames is
+ * staged in LDS once, a longer one is streamed per iteration (same order, same bits).  C outside 1 .. 8 is GMMIV_ERR_ARG.
+ *
+ * gmmiv_energy_select, per file: frame i of the selection is IN when x_i > threshold[f] (strict).  Output segments never cross an input
+ * run; begin and length count frames of the SELECTION (the reference's `ind`); a run of frames that ends inside its input segment has
+ * length = its frame count, one that reaches the input segment's end is one frame longer (:144 against :151, as written).
+ * n_above [nfiles] (nullable) = frames in; seg_count [nfiles] (nullable) = output segments; seg_begin / seg_len (both or neither) =
+ * the segments of file f at [seg_off[f], seg_off[f + 1]) -- CSR, seg_off [nfiles + 1] from a first call with seg_begin = seg_len = NULL
+ * (counts only; seg_off is then not read).  Segments beyond a file's CSR room are not written.  Worst case of a file: one segment per
+ * two frames plus one per input run.
+ * Kernel timers: "k_energy_em", "k_energy_select". */
+#define GMMIV_ENERGY_EMPTY 1
+#define GMMIV_ENERGY_NONFINITE 2
+#define GMMIV_ENERGY_FLOORED 4
+#define GMMIV_ENERGY_CEILED 8
+#define GMMIV_ENERGY_MAX_C 8
+int64_t gmmiv_energy_stage_frames(int x_dtype); /* the longest selection gmmiv_energy_train stages in LDS (0 for an unknown dtype) */
+int gmmiv_energy_train(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, const int64_t *runs, int64_t nrun, int64_t nfiles, int C,
+                       int nb_train_it, double variance_flooring, double variance_ceiling, double alpha, double *model, double *threshold,
+                       int32_t *status);
+int gmmiv_energy_select(gmmiv_ctx *ctx, const void *x, int x_dtype, int64_t ldx, const int64_t *runs, int64_t nrun, int64_t nfiles,
+                        const double *threshold, int64_t *n_above /* nullable */, int64_t *seg_count /* nullable */,
+                        const int64_t *seg_off /* with seg_begin */, int64_t *seg_begin /* nullable */, int64_t *seg_len /* nullable */);
 
 /* ---- segment means of per-frame values (ComputeTest's score per segment, ComputeTest.cpp:181-199) ------
  * out[r * nseg + s] = mean of v[r * ld + t], t in [seg_begin[s], seg_begin[s+1])  (0 for an empty segment).

@@ -44,6 +44,7 @@ def _load():
     lib.gmmiv_plan_feat_tiles.restype = ct.c_int64
     lib.gmmiv_plan_trial_tiles.restype = ct.c_int64
     lib.gmmiv_plan_score_lists.restype = ct.c_int64
+    lib.gmmiv_energy_stage_frames.restype = ct.c_int64
     return lib
 
 
@@ -327,6 +328,51 @@ class Context:
         _chk(lib.gmmiv_feat_norm_online(self._h, _vptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(fb), ct.c_int64(fb.shape[0] - 1), ct.c_int64(window),
                                         ct.c_int64(look_ahead), _vptr(out), odt, ct.c_int64(ldo)))
         return out
+
+    # ---- EnergyDetector on resident frames: x is the ENERGY COLUMN, a torch device view [T, 1] (x[:, 16:17] of a wider matrix keeps its stride)
+    def energy_train(self, x, runs, nfiles, C=3, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.0, model=None, threshold=None,
+                     status=None):
+        """gmmiv_energy_train: runs [nrun, 3] int64 (first frame, length, file), host or device -> (model [nfiles, 3 C] = w | mean | cov,
+        threshold [nfiles], status [nfiles] int32); outputs numpy unless torch device arrays are passed (then the call only enqueues)."""
+        x, dt, T, ldx = _feat_view(x)
+        assert x.shape[1] == 1, "energy_train: x is one column"
+        r = self._tab(runs)
+        if model is None:
+            model = np.zeros((nfiles, 3 * C))
+        if threshold is None:
+            threshold = np.zeros(nfiles)
+        if status is None:
+            status = np.zeros(nfiles, np.int32)
+        _chk(lib.gmmiv_energy_train(self._h, _vptr(x), dt, ct.c_int64(ldx), _ptr(r), ct.c_int64(0 if r is None else r.shape[0]), ct.c_int64(nfiles), int(C),
+                                    int(nb_train_it), ct.c_double(variance_flooring), ct.c_double(variance_ceiling), ct.c_double(alpha), _ptr(model),
+                                    _ptr(threshold), _ptr(status)))
+        return model, threshold, status
+
+    def energy_select(self, x, runs, nfiles, threshold, seg_off=None, seg_begin=None, seg_len=None, n_above=None, seg_count=None):
+        """gmmiv_energy_select.  seg_begin is None: the counting call -> (n_above [nfiles], seg_count [nfiles]); with seg_off [nfiles + 1],
+        seg_begin, seg_len: the fill call -> (n_above, seg_count, seg_begin, seg_len).  Arrays numpy or torch device."""
+        x, dt, T, ldx = _feat_view(x)
+        assert x.shape[1] == 1, "energy_select: x is one column"
+        r = self._tab(runs)
+        th = threshold if _is_torch(threshold) else np.ascontiguousarray(threshold, np.float64)
+        if n_above is None:
+            n_above = np.zeros(nfiles, np.int64)
+        if seg_count is None:
+            seg_count = np.zeros(nfiles, np.int64)
+        so = self._tab(seg_off)
+        _chk(lib.gmmiv_energy_select(self._h, _vptr(x), dt, ct.c_int64(ldx), _ptr(r), ct.c_int64(0 if r is None else r.shape[0]), ct.c_int64(nfiles), _ptr(th),
+                                     _ptr(n_above), _ptr(seg_count), _ptr(so), _ptr(seg_begin), _ptr(seg_len)))
+        return (n_above, seg_count) if seg_begin is None else (n_above, seg_count, seg_begin, seg_len)
+
+    def energy_detect(self, x, runs, nfiles, **kw):
+        """train + count + fill with host outputs -> dict(model, threshold, status, n_above, seg_off [nfiles + 1], seg_begin, seg_len)"""
+        model, th, st = self.energy_train(x, runs, nfiles, **kw)
+        above, cnt = self.energy_select(x, runs, nfiles, th)
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        sb, sl = np.zeros(int(off[-1]), np.int64), np.zeros(int(off[-1]), np.int64)
+        if off[-1] > 0:
+            self.energy_select(x, runs, nfiles, th, seg_off=off, seg_begin=sb, seg_len=sl)
+        return dict(model=model, threshold=th, status=st, n_above=above, seg_off=off, seg_begin=sb, seg_len=sl)
 
     def segment_means(self, v, seg_begin, out=None):
         """v: torch CUDA float64 [nrows, ld] (or 1-D); seg_begin: nseg + 1 host offsets -> out [nrows, nseg]."""
@@ -731,6 +777,14 @@ SCORE_LIST_CLASSES = 7     # GMMIV_SCORE_LIST_CLASSES
 def list_scratch_bytes(ndist):
     """GMMIV_SCORE_LIST_SCRATCH_BYTES(ndist): the device scratch of score_list_stats"""
     return 12 * int(ndist) + 8
+
+
+ENERGY_EMPTY, ENERGY_NONFINITE, ENERGY_FLOORED, ENERGY_CEILED, ENERGY_MAX_C = 1, 2, 4, 8, 8   # GMMIV_ENERGY_*
+
+
+def energy_stage_frames(dtype_code=F32):
+    """gmmiv_energy_stage_frames: the longest selection gmmiv_energy_train stages in LDS; one frame more is streamed per iteration"""
+    return int(lib.gmmiv_energy_stage_frames(int(dtype_code)))
 
 
 def score_list_class(n, streaming):

@@ -3,6 +3,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "ctx.h"
 #include "gmm_kernels.h"
 #include "tv_kernels.h"
@@ -417,6 +419,95 @@ int gmmiv_feat_norm_online(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, int
                                (long *)off, (double *)state, (double *)decay, out, ldo));
     c->t_end();
     if (host_tab) GCHK(hipStreamSynchronize(c->stream)); // the host table may be freed
+    return GMMIV_OK;
+}
+
+// ---- EnergyDetector on resident frames: a model, a threshold and the output segments per file (energy_det.hip) ------------------------
+static int energy_check(const char *who, gmmiv_ctx *c, const void *x, int dt, int64_t ldx, const int64_t *runs, int64_t nrun, int64_t nfiles, bool *host_runs)
+{
+    if (dt != GMMIV_F32 && dt != GMMIV_F64) { gmmiv_set_error("%s: x_dtype must be GMMIV_F32 or GMMIV_F64", who); return GMMIV_ERR_ARG; }
+    if (nrun < 0 || nfiles < 0 || ldx < 1 || (!runs && nrun > 0)) { gmmiv_set_error("%s: bad argument (nrun, nfiles < 0, ldx < 1 or runs == NULL)", who); return GMMIV_ERR_ARG; }
+    *host_runs = nrun > 0 && !gmmiv_is_device_ptr(runs);
+    int rc;
+    if (*host_runs && (rc = norm_check_runs(who, runs, nrun, nfiles, nullptr, nullptr))) return rc;
+    if (!c) { gmmiv_set_error("%s: NULL context", who); return GMMIV_ERR_ARG; }
+    if (nrun > 0 && (!x || !gmmiv_is_device_ptr(x))) { gmmiv_set_error("%s: x must be a device array", who); return GMMIV_ERR_ARG; }
+    return GMMIV_OK;
+}
+
+int64_t gmmiv_energy_stage_frames(int x_dtype) { return x_dtype == GMMIV_F32 || x_dtype == GMMIV_F64 ? (int64_t)gmmk_energy_stage_frames(x_dtype == GMMIV_F64) : 0; }
+
+int gmmiv_energy_train(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, const int64_t *runs, int64_t nrun, int64_t nfiles, int C, int nb_train_it,
+                       double flooring, double ceiling, double alpha, double *model, double *threshold, int32_t *status)
+{
+    if (C < 1 || C > GMMIV_ENERGY_MAX_C) { gmmiv_set_error("energy_train: C = %d outside 1 .. %d", C, GMMIV_ENERGY_MAX_C); return GMMIV_ERR_ARG; }
+    if (nb_train_it < 0) { gmmiv_set_error("energy_train: nb_train_it < 0"); return GMMIV_ERR_ARG; }
+    bool host_runs;
+    int rc = energy_check("energy_train", c, x, dt, ldx, runs, nrun, nfiles, &host_runs);
+    if (rc) return rc;
+    if (nfiles == 0) return GMMIV_OK;
+    if (!model || !threshold || !status) { gmmiv_set_error("energy_train: model, threshold or status == NULL"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    // the host plan: the files longest first (a workgroup is a file), and the longest selection sizes the LDS of the launch.  With a
+    // device table neither is known: table order, the whole staging budget.  Neither changes a bit of any file's result.
+    std::vector<long> order;
+    long max_frames = -1;
+    if (host_runs || nrun == 0) {
+        std::vector<int64_t> n((size_t)nfiles, 0);
+        for (int64_t r = 0; r < nrun; ++r) n[(size_t)runs[3 * r + 2]] += runs[3 * r + 1];
+        order.resize((size_t)nfiles);
+        for (int64_t f = 0; f < nfiles; ++f) order[(size_t)f] = (long)f;
+        std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return n[(size_t)a] > n[(size_t)b]; });
+        max_frames = (long)n[(size_t)order[0]];
+    }
+    DevIn<int64_t> i_runs;
+    if ((rc = i_runs.init(c, WS_T0, runs, (size_t)nrun * 3))) return rc;
+    DevIn<long> i_order;
+    if ((rc = i_order.init(c, WS_T1, order.empty() ? nullptr : order.data(), order.size()))) return rc;
+    DevOut<double> o_model, o_th;
+    DevOut<int32_t> o_st;
+    if ((rc = o_model.init(c, WS_T2, model, (size_t)nfiles * 3 * C, false)) || (rc = o_th.init(c, WS_T3, threshold, (size_t)nfiles, false)) ||
+        (rc = o_st.init(c, WS_T4, status, (size_t)nfiles, false))) return rc;
+    c->t_begin("k_energy_em");
+    GCHK(gmmk_energy_em(c->stream, dt == GMMIV_F64, x, ldx, (const long *)i_runs.d, nrun, nfiles, i_order.d, max_frames, C, nb_train_it, flooring, ceiling, alpha,
+                        o_model.d, o_th.d, (int *)o_st.d));
+    c->t_end();
+    if ((rc = o_model.finish()) || (rc = o_th.finish()) || (rc = o_st.finish())) return rc;
+    if (!order.empty() || host_runs) GCHK(hipStreamSynchronize(c->stream)); // the host tables may be freed
+    return GMMIV_OK;
+}
+
+int gmmiv_energy_select(gmmiv_ctx *c, const void *x, int dt, int64_t ldx, const int64_t *runs, int64_t nrun, int64_t nfiles, const double *threshold,
+                        int64_t *n_above, int64_t *seg_count, const int64_t *seg_off, int64_t *seg_begin, int64_t *seg_len)
+{
+    bool host_runs;
+    int rc = energy_check("energy_select", c, x, dt, ldx, runs, nrun, nfiles, &host_runs);
+    if (rc) return rc;
+    if ((seg_begin == nullptr) != (seg_len == nullptr)) { gmmiv_set_error("energy_select: seg_begin and seg_len go together"); return GMMIV_ERR_ARG; }
+    if (nfiles == 0) return GMMIV_OK;
+    if (!threshold) { gmmiv_set_error("energy_select: threshold == NULL"); return GMMIV_ERR_ARG; }
+    if (seg_begin && !seg_off) { gmmiv_set_error("energy_select: seg_off == NULL with seg_begin"); return GMMIV_ERR_ARG; }
+    const bool host_off = seg_begin && !gmmiv_is_device_ptr(seg_off);
+    size_t room = 0;
+    if (host_off) {
+        for (int64_t f = 0; f < nfiles; ++f)
+            if (seg_off[f] < 0 || seg_off[f + 1] < seg_off[f]) { gmmiv_set_error("energy_select: seg_off must be non-negative and non-decreasing (file %ld)", (long)f); return GMMIV_ERR_ARG; }
+        room = (size_t)seg_off[nfiles];
+    } else if (seg_begin && (!gmmiv_is_device_ptr(seg_begin) || !gmmiv_is_device_ptr(seg_len))) { gmmiv_set_error("energy_select: host seg_begin / seg_len need a host seg_off"); return GMMIV_ERR_ARG; }
+    GBIND(c);
+    DevIn<int64_t> i_runs, i_off;
+    DevIn<double> i_th;
+    if ((rc = i_runs.init(c, WS_T0, runs, (size_t)nrun * 3)) || (rc = i_th.init(c, WS_T3, threshold, (size_t)nfiles)) ||
+        (rc = i_off.init(c, WS_T7, seg_begin ? seg_off : nullptr, (size_t)nfiles + 1))) return rc;
+    DevOut<int64_t> o_above, o_cnt, o_beg, o_len;
+    if ((rc = o_above.init(c, WS_T5, n_above, (size_t)nfiles, false)) || (rc = o_cnt.init(c, WS_T6, seg_count, (size_t)nfiles, false)) ||
+        (rc = o_beg.init(c, WS_T8, seg_begin, room, false)) || (rc = o_len.init(c, WS_T9, seg_len, room, false))) return rc;
+    c->t_begin("k_energy_select");
+    GCHK(gmmk_energy_select(c->stream, dt == GMMIV_F64, x, ldx, (const long *)i_runs.d, nrun, nfiles, i_th.d, (long *)o_above.d, (long *)o_cnt.d, (const long *)i_off.d,
+                            (long *)o_beg.d, (long *)o_len.d));
+    c->t_end();
+    if ((rc = o_above.finish()) || (rc = o_cnt.finish()) || (rc = o_beg.finish()) || (rc = o_len.finish())) return rc;
+    if (host_runs || host_off || !gmmiv_is_device_ptr(threshold)) GCHK(hipStreamSynchronize(c->stream)); // host arrays may be freed
     return GMMIV_OK;
 }
 

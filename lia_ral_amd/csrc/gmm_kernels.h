@@ -163,3 +163,9 @@ size_t gmmk_online_units(long nfiles, long frames); // upper bound of the chunks
 long gmmk_online_chunk(void);
 int gmmk_feat_norm_online(hipStream_t st, int n_cu, int x_f64, int o_f64, const void *x, long ldx, int D, const long *file_begin, long nfiles,
                           long W, long L, long max_units, long *chunk_off, double *state, double *decay, void *out, long ldo);
+// energy_det.hip: EnergyDetector per file (order nullable: the file of each workgroup; max_frames < 0: the longest selection is unknown)
+long gmmk_energy_stage_frames(int x_f64);
+int gmmk_energy_em(hipStream_t st, int x_f64, const void *x, long ldx, const long *runs, long nrun, long nfiles, const long *order, long max_frames,
+                   int C, int nb_it, double flooring, double ceiling, double alpha, double *model, double *threshold, int *status);
+int gmmk_energy_select(hipStream_t st, int x_f64, const void *x, long ldx, const long *runs, long nrun, long nfiles, const double *threshold,
+                       long *n_above, long *seg_count, const long *seg_off, long *seg_begin, long *seg_len);

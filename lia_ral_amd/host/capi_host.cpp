@@ -1604,6 +1604,75 @@ int liagpu_energy_detector(int device, const float *energy, long T, const long *
     })
 }
 
+// liagpu::energyDetectorBatch on nfiles energy columns laid end to end: energy [T] float32, file f = frames [file_begin[f], file_begin[f + 1]),
+// its input segments seg_begin / seg_len [seg_off[f], seg_off[f + 1]) (frames of the FILE).  out_off [nfiles + 1], out_begin / out_len
+// [max_out] <- the output segments in CSR form (frames of each file's SELECTION); model_out [nfiles x 3 C] (w | mean | cov), threshold_out
+// [nfiles], status_out [nfiles] (all nullable).
+int liagpu_energy_detector_batch(int device, const float *energy, long T, const long *file_begin, long nfiles, const long *seg_off, const long *seg_begin,
+                                 const long *seg_len, int C, int nbTrainIt, double varianceFlooring, double varianceCeiling, double alpha, long *out_off,
+                                 long *out_begin, long *out_len, long max_out, double *model_out, double *threshold_out, int *status_out)
+{
+    GUARD({
+        GpuServer srv(device);
+        if (nfiles < 0 || (nfiles > 0 && (file_begin[0] != 0 || file_begin[nfiles] != T))) throw Exception("file_begin must run from 0 to T");
+        std::vector<unsigned long> first((size_t)(nfiles > 0 ? nfiles : 1), 0);
+        for (long f = 0; f < nfiles; ++f) first[(size_t)f] = (unsigned long)file_begin[f];
+        FeatureBuffer fs(srv, energy, (unsigned long)T, 1, first);
+        std::vector<SegCluster> sel((size_t)nfiles);
+        for (long f = 0; f < nfiles; ++f) sel[(size_t)f] = make_cluster(seg_begin + seg_off[f], seg_len + seg_off[f], seg_off[f + 1] - seg_off[f]);
+        if (nfiles == 0) sel.resize(fs.getSourceCount());
+        EnergyDetectorCfg cfg;
+        cfg.nbTrainIt = (unsigned long)nbTrainIt; cfg.mixtureDistribCount = (unsigned long)C;
+        cfg.varianceFlooring = varianceFlooring; cfg.varianceCeiling = varianceCeiling; cfg.alpha = alpha;
+        std::vector<MixtureGD> models;
+        std::vector<double> th;
+        std::vector<int> st;
+        std::vector<SegCluster> out = energyDetectorBatch(fs, sel, cfg, &models, &th, &st);
+        long k = 0;
+        for (long f = 0; f < nfiles; ++f) {
+            out_off[f] = k;
+            for (const Seg &g : out[(size_t)f]) {
+                if (k >= max_out) throw Exception("out_begin too small");
+                out_begin[k] = (long)g.begin; out_len[k] = (long)g.length; ++k;
+            }
+            if (model_out)
+                for (int c = 0; c < C; ++c) {
+                    model_out[f * 3 * C + c] = models[(size_t)f].weight(c); model_out[f * 3 * C + C + c] = models[(size_t)f].getMean(c, 0);
+                    model_out[f * 3 * C + 2 * C + c] = models[(size_t)f].getCov(c, 0);
+                }
+            if (threshold_out) threshold_out[f] = th[(size_t)f];
+            if (status_out) status_out[f] = st[(size_t)f];
+        }
+        out_off[nfiles > 0 ? nfiles : 0] = k;
+    })
+}
+
+// liagpu::energyDetectorFiles: names [n] are joined with the paths / extensions; threshold_out / status_out [n] (nullable)
+int liagpu_energy_detector_files(int device, int n, const char **names, const char *feature_path, const char *load_ext, const char *label_path,
+                                 const char *label_ext, const char *label, const char *save_path, const char *save_ext, const char *label_out,
+                                 const char *mask, double frameLength, int C, int nbTrainIt, double varianceFlooring, double varianceCeiling, double alpha,
+                                 double *threshold_out, int *status_out)
+{
+    GUARD({
+        GpuServer srv(device);
+        EnergyDetectorFilesCfg cfg;
+        cfg.energy.nbTrainIt = (unsigned long)nbTrainIt; cfg.energy.mixtureDistribCount = (unsigned long)C;
+        cfg.energy.varianceFlooring = varianceFlooring; cfg.energy.varianceCeiling = varianceCeiling; cfg.energy.alpha = alpha;
+        cfg.featureFilesPath = feature_path ? feature_path : ""; cfg.loadFeatureFileExtension = load_ext ? load_ext : "";
+        cfg.labelFilesPath = label_path ? label_path : ""; cfg.labelFilesExtension = label_ext ? label_ext : "";
+        cfg.labelSelectedFrames = label ? label : ""; cfg.saveLabelFilePath = save_path ? save_path : "";
+        cfg.saveLabelFileExtension = save_ext ? save_ext : ""; cfg.labelOutputFrames = label_out ? label_out : "";
+        cfg.featureServerMask = mask ? mask : ""; cfg.frameLength = frameLength;
+        std::vector<double> th;
+        std::vector<int> st;
+        energyDetectorFiles(srv, std::vector<std::string>(names, names + n), cfg, &th, &st);
+        for (int k = 0; k < n; ++k) {
+            if (threshold_out) threshold_out[k] = th[(size_t)k];
+            if (status_out) status_out[k] = st[(size_t)k];
+        }
+    })
+}
+
 // selectFrames alone (EnergyDetector.cpp:118-157; host only, no GPU): energy [T], threshold, selected segments -> output segments
 int liagpu_select_frames(const float *energy, long T, double threshold, const long *seg_begin, const long *seg_len, long nseg, long *out_begin,
                          long *out_len, long max_out, long *n_out, long *count_out)

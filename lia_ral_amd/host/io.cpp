@@ -677,4 +677,45 @@ void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const 
     }
 }
 
+void energyDetectorFiles(GpuServer &srv, const std::vector<std::string> &names, const EnergyDetectorFilesCfg &cfg, std::vector<double> *thresholds,
+                         std::vector<int> *status)
+{
+    if (thresholds) thresholds->clear();
+    if (status) status->clear();
+    if (names.empty()) return;
+    std::vector<unsigned long> first;
+    std::vector<SegCluster> clusters;
+    std::vector<float> all;
+    unsigned long total = 0, dim = 0;
+    for (size_t k = 0; k < names.size(); ++k) {
+        const FeatureFile f = readFeatureFile(cfg.featureFilesPath + names[k] + cfg.loadFeatureFileExtension, cfg.featureServerMask);
+        if (f.nFrames) {
+            if (dim && f.vectSize != dim) throw Exception("energyDetectorFiles: [" + names[k] + "] has another dimension than the files before it");
+            dim = f.vectSize;
+        }
+        first.push_back(total);
+        total += f.nFrames;
+        all.insert(all.end(), f.data.begin(), f.data.end());
+        SegCluster c;
+        if (cfg.labelFilesExtension.empty()) { Seg s; s.begin = 0; s.length = f.nFrames; s.source = k; if (f.nFrames) c.push_back(s); }
+        else c = selectSegments(readLabelFile(cfg.labelFilesPath + names[k] + cfg.labelFilesExtension), cfg.labelSelectedFrames, cfg.frameLength, k);
+        for (const Seg &g : c)
+            if (g.begin + g.length > f.nFrames) throw Exception("energyDetectorFiles: a segment of [" + names[k] + "] ends after the last frame of the file");
+        clusters.push_back(c);
+    }
+    if (!dim) throw Exception("energyDetectorFiles: no frames");
+    std::vector<SegCluster> out;
+    {
+        FeatureBuffer fs(srv, all.data(), total, dim, first);
+        out = energyDetectorBatch(fs, clusters, cfg.energy, nullptr, thresholds, status);
+    }
+    for (size_t k = 0; k < names.size(); ++k) {
+        const std::string path = (cfg.saveLabelFilePath.empty() ? cfg.labelFilesPath : cfg.saveLabelFilePath) + names[k] + cfg.saveLabelFileExtension;
+        std::ofstream o(path.c_str(), std::ios::out | std::ios::trunc);
+        if (!o.good()) throw Exception("Can't create label file [" + path + "]");
+        for (const Seg &g : out[k])
+            o << frameIdxToTime(g.begin, cfg.frameLength) << " " << frameIdxToTime(g.begin + g.length - 1, cfg.frameLength) << " " << cfg.labelOutputFrames << std::endl;
+    }
+}
+
 } // namespace liagpu

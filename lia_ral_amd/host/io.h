@@ -140,4 +140,19 @@ struct NormFeatFilesCfg {
 };
 void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const NormFeatFilesCfg &cfg);
 
+// EnergyDetector driven by files (EnergyDetectorMain.cpp:104-131, EnergyDetector.cpp:200-279): every feature file
+// <featureFilesPath><name><loadFeatureFileExtension> of the list is loaded through featureServerMask -- which picks the energy column --
+// into ONE resident buffer, the input clusters come from <labelFilesPath><name><labelFilesExtension> (labelFilesExtension "": every frame
+// of the file), liagpu::energyDetectorBatch runs once on the whole list, and <saveLabelFilePath><name><saveLabelFileExtension> receives one
+// line "begin_s end_s labelOutputFrames" per output segment (outputLabelFile, SegTools.cpp:106-118: frameIdxToTime of begin and of
+// begin + length - 1).  thresholds / status (optional): one entry per name.
+struct EnergyDetectorFilesCfg {
+    EnergyDetectorCfg energy;
+    std::string featureFilesPath, loadFeatureFileExtension = ".prm", labelFilesPath, labelFilesExtension = ".lbl", labelSelectedFrames = "speech";
+    std::string saveLabelFilePath, saveLabelFileExtension = ".enr.lbl", labelOutputFrames = "speech", featureServerMask;
+    double frameLength = 0.01;
+};
+void energyDetectorFiles(GpuServer &srv, const std::vector<std::string> &names, const EnergyDetectorFilesCfg &cfg, std::vector<double> *thresholds = nullptr,
+                         std::vector<int> *status = nullptr);
+
 } // namespace liagpu

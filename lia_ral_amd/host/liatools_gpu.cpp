@@ -1139,6 +1139,88 @@ SegCluster energyDetector(FeatureBuffer &fs, const SegCluster &selectedSegments,
     return outputSeg;
 }
 
+std::vector<SegCluster> energyDetectorBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerFile, const EnergyDetectorCfg &cfg,
+                                            std::vector<MixtureGD> *modelsOut, std::vector<double> *thresholdsOut, std::vector<int> *statusOut)
+{
+    if (cfg.thresholdMode != "meanStd")
+        throw Exception("energyDetectorBatch: thresholdMode [" + cfg.thresholdMode + "] needs alize-core's Histo, only meanStd is available");
+    const size_t nf = selectedPerFile.size();
+    if (nf != fs.getSourceCount()) throw Exception("energyDetectorBatch: one SegCluster per source of the feature buffer expected");
+    const int C = (int)cfg.mixtureDistribCount;
+    if (cfg.mixtureDistribCount < 1) throw Exception("energyDetectorBatch: mixtureDistribCount < 1");
+    for (size_t s = 0; s < nf; ++s)
+        for (const Seg &g : selectedPerFile[s])
+            if (g.begin + g.length > fs.getFeatureCountOfASource(s)) throw Exception("energyDetectorBatch: a segment ends after the last frame of its source");
+    std::vector<SegCluster> out(nf);
+    if (modelsOut) modelsOut->assign(nf, MixtureGD(cfg.mixtureDistribCount, fs.getVectSize()));
+    if (thresholdsOut) thresholdsOut->assign(nf, 0.0);
+    if (statusOut) statusOut->assign(nf, 0);
+    if (nf == 0) return out;
+    GpuServer &srv = fs.server();
+    if (fs.getVectSize() > 1 || cfg.mixtureDistribCount > GMMIV_ENERGY_MAX_C) {
+        // the per-file tool on absolute frame indices (source 0 of the buffer starts at frame 0)
+        for (size_t s = 0; s < nf; ++s) {
+            SegCluster abs = selectedPerFile[s];
+            for (Seg &g : abs) { g.begin += fs.getFirstFeatureIndexOfASource(s); g.source = 0; }
+            MixtureGD model(cfg.mixtureDistribCount, fs.getVectSize());
+            double th = 0.0;
+            if (totalFrame(abs) == 0) { energyMixtureInit(model); th = NAN; }
+            else out[s] = energyDetector(fs, abs, cfg, &model, &th);
+            for (Seg &g : out[s]) g.source = s;
+            bool fin = std::isfinite(th);
+            for (unsigned long c = 0; c < cfg.mixtureDistribCount; ++c) fin = fin && std::isfinite(model.weight(c)) && std::isfinite(model.getMean(c, 0)) && std::isfinite(model.getCov(c, 0));
+            if (modelsOut) (*modelsOut)[s] = model;
+            if (thresholdsOut) (*thresholdsOut)[s] = th;
+            if (statusOut) (*statusOut)[s] = totalFrame(abs) == 0 ? GMMIV_ENERGY_EMPTY : fin ? 0 : GMMIV_ENERGY_NONFINITE;
+        }
+        return out;
+    }
+    // the run table of the NormFeat calls: one run per input label segment, never cut (selectFrames' end-of-segment rule)
+    std::vector<int64_t> runs;
+    for (size_t s = 0; s < nf; ++s)
+        for (const Seg &g : selectedPerFile[s]) {
+            if (g.length == 0) continue;
+            runs.push_back((int64_t)(fs.getFirstFeatureIndexOfASource(s) + g.begin)); runs.push_back((int64_t)g.length); runs.push_back((int64_t)s);
+        }
+    const int64_t nrun = (int64_t)(runs.size() / 3);
+    // one device block: model [nf x 3 C] | threshold [nf] (doubles), n_above [nf] | seg_count [nf] (int64), status [nf] (int32)
+    const size_t nd = nf * 3 * C + nf, bytes = nd * sizeof(double) + 2 * nf * sizeof(int64_t) + nf * sizeof(int32_t);
+    struct Block { void *p = nullptr; ~Block() { if (p) (void)hipFree(p); } } blk;
+    hipcheck(hipMalloc(&blk.p, bytes), "energyDetectorBatch: hipMalloc");
+    double *dModel = (double *)blk.p, *dTh = dModel + nf * 3 * C;
+    int64_t *dAbove = (int64_t *)(dTh + nf), *dCount = dAbove + nf;
+    int32_t *dStatus = (int32_t *)(dCount + nf);
+    const float *x = fs.device();
+    srv.check(gmmiv_energy_train(srv.ctx(), x, GMMIV_F32, 1, runs.data(), nrun, (int64_t)nf, C, (int)cfg.nbTrainIt, cfg.varianceFlooring, cfg.varianceCeiling,
+                                 cfg.alpha, dModel, dTh, dStatus));
+    srv.check(gmmiv_energy_select(srv.ctx(), x, GMMIV_F32, 1, runs.data(), nrun, (int64_t)nf, dTh, dAbove, dCount, nullptr, nullptr, nullptr));
+    std::vector<unsigned char> host(bytes);
+    hipcheck(hipMemcpyAsync(host.data(), blk.p, bytes, hipMemcpyDeviceToHost, (hipStream_t)srv.stream()), "energyDetectorBatch: download");
+    srv.sync();
+    const double *hModel = (const double *)host.data(), *hTh = hModel + nf * 3 * C;
+    const int64_t *hCount = (const int64_t *)(hTh + nf) + nf;
+    const int32_t *hStatus = (const int32_t *)(hCount + nf);
+    std::vector<int64_t> off(nf + 1, 0);
+    for (size_t s = 0; s < nf; ++s) off[s + 1] = off[s] + hCount[s];
+    std::vector<int64_t> sb((size_t)off[nf]), sl((size_t)off[nf]);
+    if (off[nf] > 0)
+        srv.check(gmmiv_energy_select(srv.ctx(), x, GMMIV_F32, 1, runs.data(), nrun, (int64_t)nf, dTh, nullptr, nullptr, off.data(), sb.data(), sl.data()));
+    for (size_t s = 0; s < nf; ++s) {
+        for (int64_t k = off[s]; k < off[s + 1]; ++k) {
+            Seg g; g.begin = (unsigned long)sb[(size_t)k]; g.length = (unsigned long)sl[(size_t)k]; g.source = s;
+            out[s].push_back(g);
+        }
+        if (modelsOut) {
+            MixtureGD &m = (*modelsOut)[s];
+            for (int c = 0; c < C; ++c) { m.weight(c) = hModel[s * 3 * C + c]; m.setMean(c, hModel[s * 3 * C + C + c], 0); m.setCov(c, hModel[s * 3 * C + 2 * C + c], 0); }
+            m.computeAll();
+        }
+        if (thresholdsOut) (*thresholdsOut)[s] = hTh[s];
+        if (statusOut) (*statusOut)[s] = (int)hStatus[s];
+    }
+    return out;
+}
+
 // ---- GmmTokenizer -------------------------------------------------------------------------------------
 // the sorted top list of every selected frame, [n x ctop] (DETERMINE_TOP_DISTRIBS + getTopDistribIndexVector, GmmTokenizer.cpp:71-72, :100-101)
 static std::vector<int32_t> topListOfSelection(const SegCluster &selectedSegments, FeatureBuffer &fs, DeviceMixture &world, int ctop,

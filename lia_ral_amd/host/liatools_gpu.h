@@ -506,6 +506,16 @@ unsigned long selectFrames(const std::vector<float> &energy, double threshold, c
 SegCluster energyDetector(FeatureBuffer &fs, const SegCluster &selectedSegments, const EnergyDetectorCfg &cfg, MixtureGD *energyModel = nullptr,
                           double *threshold = nullptr);
 
+// The same for ALL sources of the buffer in one device pass (gmmiv_energy_train + gmmiv_energy_select): selectedPerFile[s] is the cluster
+// of input label segments of source s (Seg::begin counts from the source's first frame; Seg::source is ignored), the result [s] the output
+// segments of source s (begin / length count frames of ITS selection, Seg::source = s).  One train call, a counting and a filling select
+// call, and two downloads (the per-file results and counts; the segments) whatever the number of files.  models / thresholds / status
+// (optional, one entry per source) receive the trained models, the thresholds and the GMMIV_ENERGY_* bit sets.  A buffer of vectSize > 1
+// or a model of more than GMMIV_ENERGY_MAX_C Gaussians runs energyDetector per file; thresholdMode "weight" is the Exception it is there.
+std::vector<SegCluster> energyDetectorBatch(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerFile, const EnergyDetectorCfg &cfg,
+                                            std::vector<MixtureGD> *models = nullptr, std::vector<double> *thresholds = nullptr,
+                                            std::vector<int> *status = nullptr);
+
 // ---- NormFeat (LIA_SpkDet/NormFeat/src/NormFeat.cpp:231-518), the default mode: mean / std of the selected frames per segment
 // (segmentalMode, :340-370) and / or per file (fileMode, :448-464; the mode when neither is set, :243), then computeZeroOne
 // (GeneralTools.cpp:670-682) on those frames, in place in the resident buffer.  Both set: segmental first, then file (:272).

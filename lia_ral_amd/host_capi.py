@@ -804,6 +804,47 @@ def energy_detector(energy, seg_begin, seg_len, C=2, nb_train_it=10, variance_fl
                 threshold=th.value)
 
 
+def energy_detector_batch(energies, segments, C=2, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.25, device=0):
+    """EnergyDetector (meanStd mode) on a LIST of energy columns in one device pass (liagpu::energyDetectorBatch): energies[f] a float32
+    column, segments[f] = (seg_begin, seg_len) of its input label segments -> one dict(begin, length, w, mean, cov, threshold, status) per
+    file.  The output arrays are sized from the frame counts: a file has at most one segment per two frames plus one per input segment."""
+    es = [np.ascontiguousarray(e, np.float32).reshape(-1) for e in energies]
+    nf = len(es)
+    fb = np.zeros(nf + 1, np.int64)
+    fb[1:] = np.cumsum([len(e) for e in es])
+    x = np.concatenate(es) if nf and fb[-1] else np.zeros(0, np.float32)
+    sb = [np.ascontiguousarray(s[0], np.int64).reshape(-1) for s in segments]
+    sl = [np.ascontiguousarray(s[1], np.int64).reshape(-1) for s in segments]
+    assert len(sb) == nf
+    so = np.zeros(nf + 1, np.int64)
+    so[1:] = np.cumsum([len(b) for b in sb])
+    sbc = np.concatenate(sb + [np.zeros(1, np.int64)]); slc = np.concatenate(sl + [np.zeros(1, np.int64)])
+    room = int(sum(int(l.sum()) // 2 + 1 + len(l) for l in sl)) + 1
+    oo = np.zeros(nf + 1, np.int64); ob = np.zeros(room, np.int64); ol = np.zeros(room, np.int64)
+    model = np.zeros((max(nf, 1), 3 * C)); th = np.zeros(max(nf, 1)); st = np.zeros(max(nf, 1), np.int32)
+    _chk(lib.liagpu_energy_detector_batch(device, x.ctypes.data_as(_fp), ct.c_long(len(x)), fb.ctypes.data_as(_lp), ct.c_long(nf), so.ctypes.data_as(_lp),
+                                          sbc.ctypes.data_as(_lp), slc.ctypes.data_as(_lp), int(C), int(nb_train_it), ct.c_double(variance_flooring),
+                                          ct.c_double(variance_ceiling), ct.c_double(alpha), oo.ctypes.data_as(_lp), ob.ctypes.data_as(_lp),
+                                          ol.ctypes.data_as(_lp), ct.c_long(room), _d(model), _d(th), st.ctypes.data_as(ct.POINTER(ct.c_int))))
+    return [dict(begin=ob[oo[f]:oo[f + 1]].copy(), length=ol[oo[f]:oo[f + 1]].copy(), w=model[f, :C].copy(), mean=model[f, C:2 * C].copy(),
+                 cov=model[f, 2 * C:].copy(), threshold=float(th[f]), status=int(st[f])) for f in range(nf)]
+
+
+def energy_detector_files(names, feature_path="", load_ext=".prm", label_path="", label_ext=".lbl", label="speech", save_path="", save_ext=".enr.lbl",
+                          label_out="speech", mask="", frame_length=0.01, C=2, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.25,
+                          device=0):
+    """liagpu::energyDetectorFiles: the list's feature files (mask picks the energy column) and label files in one batch; one output label
+    file <save_path><name><save_ext> per name -> (thresholds [n], status [n])."""
+    names = list(names)
+    arr = (ct.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    th = np.zeros(max(len(names), 1)); st = np.zeros(max(len(names), 1), np.int32)
+    _chk(lib.liagpu_energy_detector_files(device, len(names), arr, feature_path.encode(), load_ext.encode(), label_path.encode(), label_ext.encode(),
+                                          label.encode(), save_path.encode(), save_ext.encode(), label_out.encode(), mask.encode(), ct.c_double(frame_length),
+                                          int(C), int(nb_train_it), ct.c_double(variance_flooring), ct.c_double(variance_ceiling), ct.c_double(alpha), _d(th),
+                                          st.ctypes.data_as(ct.POINTER(ct.c_int))))
+    return th[:len(names)].copy(), st[:len(names)].copy()
+
+
 def select_frames(energy, threshold, seg_begin, seg_len):
     """selectFrames (EnergyDetector.cpp:118-157) on the host: -> (begin[], length[], frames above the threshold)."""
     e = np.ascontiguousarray(energy, np.float32)
