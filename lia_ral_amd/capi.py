@@ -246,6 +246,13 @@ class Context:
         _chk(lib.gmmiv_frame_moments(self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), D, _ptr(acc)))
         return acc
 
+    def count_unusable_frames(self, x):
+        """gmmiv_count_unusable_frames: the frames with a NaN, infinite or absurd (|x| > 1e18) feature value; waits for the stream"""
+        x, dt, T, ldx = _feat(x)
+        n = ct.c_int64(0)
+        _chk(lib.gmmiv_count_unusable_frames(self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), x.shape[1], ct.byref(n)))
+        return int(n.value)
+
     # ---- frame selection on the device (x, out: torch CUDA tensors)
     def gather_frames(self, x, frame_idx, out):
         x, dt, T, ldx = _feat(x)
@@ -962,6 +969,18 @@ class Gmm:
                                          ct.c_double(max_llk), _ptr(idx), _ptr(lk), _ptr(nlk), _ptr(nllk), _ptr(nw),
                                          _ptr(out)))
         return dict(idx=idx, lk=lk, nontop_lk=nlk, nontop_llk=nllk, nontop_w=nw, llk=out)
+
+    def topgauss_compute(self, x, cap, top_gauss, complete=True, min_llk=-200.0, max_llk=200.0):
+        """gmmiv_topgauss_compute (TopGauss::compute): top_gauss >= 1 a fixed count, < 1 a share of the frame's likelihood -> dict(idx
+        [T, cap] with -1 behind the selection, count [T], snsw, snsl, llk [T], n_capped)"""
+        x, dt, T, ldx = _feat(x)
+        idx = np.empty((T, cap), np.int32); count = np.empty(T, np.int32)
+        snsw = np.empty(T); snsl = np.empty(T); out = np.empty(T)
+        n_capped = ct.c_int64(0)
+        _chk(lib.gmmiv_topgauss_compute(self.ctx._h, self._h, _ptr(x), dt, ct.c_int64(T), ct.c_int64(ldx), int(cap), ct.c_double(top_gauss),
+                                        TOP_COMPLETE if complete else TOP_PARTIAL, ct.c_double(min_llk), ct.c_double(max_llk), _ptr(idx),
+                                        _ptr(count), _ptr(snsw), _ptr(snsl), _ptr(out), ct.byref(n_capped)))
+        return dict(idx=idx, count=count, snsw=snsw, snsl=snsl, llk=out, n_capped=int(n_capped.value))
 
     def llk_use_top(self, x, idx, nontop_llk, complete=True, min_llk=-200.0, max_llk=200.0):
         x, dt, T, ldx = _feat(x)

@@ -1,12 +1,13 @@
 """What the per-element GPU files share (test_gpu_tv_elementwise.py, test_gpu_backend_elementwise.py,
-test_gpu_estimation_elementwise.py, test_gpu_trials_elementwise.py): the option bracket, the
+test_gpu_estimation_elementwise.py, test_gpu_trials_elementwise.py, test_gpu_ws_history.py / ws_history.py): the option bracket, the
 collector of ratios to a bar and the device buffer between two guard bands.  No test lives here."""
 import contextlib
 
 import numpy as np
 
 DEFAULTS = {"tv_batch": 1024, "tv_acc_mb": 8192, "gemm_nt80": 1, "tv_tett_direct": 1, "tv_mstep_solve": 1, "tv_md_device": 1, "chol_gemm": 0,
-            "trials_piece": 0, "trials_scratch_mb": 2048, "topc_use_lanes": 4, "topc_z": 1, "topc_fused": 1, "glds": 1}
+            "trials_piece": 0, "trials_scratch_mb": 2048, "topc_use_lanes": 4, "topc_z": 1, "topc_fused": 1, "glds": 1,
+            "stats_z": 1, "z_scratch_mb": 16384, "models_scratch_mb": 2048, "wg_waves": 8, "z_waves": 8, "short_calls": 1, "timing": 0}
 GUARD = 64                    # doubles on either side of a device result (a multiple of 2: the result keeps its 16-byte alignment)
 SENTINEL = -1.2345678e300
 

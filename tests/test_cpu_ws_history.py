@@ -1,0 +1,207 @@
+"""What tests/test_gpu_ws_history.py relies on, checked without a GPU: the large cases dominate the judged ones in every quantity
+that sizes a workspace and do not align with them; the degenerate frames are where the table says; and the programme reaches
+every function of include/gmmiv.h that takes a context, model or batch handle -- or names it in EXEMPT with a reason -- so a new
+ABI function with neither fails here."""
+import ast
+import inspect
+import os
+import re
+
+import numpy as np
+
+import ws_history as wh
+from conftest import ROOT
+
+
+def test_every_judged_case_is_dominated_by_a_large_case_that_does_not_align_with_it():
+    for small in wh.SMALL:
+        s = wh.sizes(small)
+        found = []
+        for large in wh.LARGE:
+            l = wh.sizes(large)
+            if all(l[k] >= s[k] for k in s):
+                Cs, Ds, Ts, _ = small["gcase"]
+                Cl, Dl, Tl, _ = large["gcase"]
+                if Cl % Cs or Dl % Ds or Tl % Ts:
+                    found.append(large["name"])
+        assert found, "no large case dominates %s: %s" % (small["name"], s)
+    # the segment, trial and file tables, which size the WS_MB_* / WS_TR_* / WS_NORM_* slots, and the energy / score inputs
+    for small in wh.SMALL:
+        for large in wh.LARGE:
+            assert len(wh.seg_table(large)[1]) >= len(wh.seg_table(small)[1]) and len(wh.trial_table(large)[0]) >= len(wh.trial_table(small)[0])
+            assert max(np.diff(wh.file_table(large))) >= max(np.diff(wh.file_table(small)))
+            assert sum(large["energy"]) >= sum(small["energy"]) and sum(large["lists"]) >= sum(small["lists"])
+    assert max(c["gcase"][2] for c in wh.LARGE) > 4096 and wh.Z_MB_530 >= 1              # more than one chunk of the smallest scratch
+    assert max(np.diff(wh.file_table(wh.LARGE[0]))) >= 2500 > 2 * 1024                     # the online scan: more than two chunks
+    assert all(c["cohort"] == 100003 for c in wh.LARGE)
+    # the online scan with a device table is sized by the allocation that holds x (ws_history.s_norm_online)
+    most = max(wh.TORCH_SMALL_BLOCK // (4 * c["gcase"][1]) + 1 for c in wh.SMALL)
+    assert all(c["online_rows"] >= most and c["online_rows"] * c["gcase"][1] * 4 > wh.TORCH_SMALL_BLOCK for c in wh.LARGE)
+    assert max(c["online_rows"] * c["gcase"][1] for c in wh.LARGE) >= max((wh.TORCH_SMALL_BLOCK // (4 * c["gcase"][1]) + 2048) * c["gcase"][1] for c in wh.SMALL)
+    assert {c["gcase"][:3] for c in wh.SMALL} == {(37, 13, 65), (129, 60, 257), (40, 97, 66)}
+    assert 70 in wh.CASES["s129x60x257"]["ctops"] and {10, 17} <= set(wh.SMALL[0]["ctops"])
+
+
+def test_tables_are_valid_and_have_an_empty_segment():
+    for case in wh.SMALL + wh.LARGE:
+        T = case["gcase"][2]
+        sb, sm = wh.seg_table(case)
+        assert len(sb) == case["nseg"] + 1 and sb[0] >= 0 and sb[-1] <= T and np.all(np.diff(sb) >= 0) and (np.diff(sb) == 0).sum() == 1
+        assert sm.min() >= 0 and sm.max() < case["G"] and len(set(sm.tolist())) == case["G"]
+        ts, tm = wh.trial_table(case)
+        assert len(ts) == case["ntrial"] and ts.max() < case["nseg"] and tm.max() < case["G"] and ts.min() >= 0 and tm.min() >= 0
+        fb = wh.file_table(case)
+        assert fb[-1] <= T and np.all(np.diff(fb) >= 0)
+        assert all(c <= 64 for c in case["trial_ctops"])                                   # gmmiv_llr_trials: ctop <= 64
+    assert wh.SMALL[0]["nseg"] == 5 and wh.SMALL[0]["G"] == 3 and wh.SMALL[0]["ntrial"] == 6
+    assert wh.LARGE[0]["nseg"] == 40 and wh.LARGE[0]["G"] == 7 and wh.LARGE[0]["ntrial"] == 60
+
+
+def test_the_planted_frames_are_where_the_table_says_and_the_large_host_frames_are_float64():
+    for case in wh.LARGE:
+        C, D, T, _ = case["gcase"]
+        k1, k2 = wh.planted(case)
+        assert len(k1) == 8 and len(k2) == 2
+        rows = sorted(list(k1) + list(k2))
+        assert sum(1 for t in rows if t >= T - 16) >= 4 and sum(1 for t in rows if t < 16) >= 4          # the last 16 rows, the first block
+        for form, dtype in (("host", np.float64), ("device", np.float32)):
+            x = wh.frames(case, form)
+            assert x.dtype == dtype and x.shape == (T, D) and not x.flags.writeable
+            bad = ~(np.isfinite(x) & (np.abs(x) <= 1e18)).all(1)
+            assert sorted(np.nonzero(bad)[0].tolist()) == sorted(k1)
+            for t, v in k1.items():
+                col = (7 * t) % D
+                assert (np.isnan(x[t, col]) if np.isnan(v) else x[t, col] == dtype(v)) and np.isfinite(np.delete(x[t], col)).all()
+            assert {np.inf, -np.inf, 1e30} <= set(k1.values()) and any(np.isnan(v) for v in k1.values())
+            for t in k2:
+                assert np.all(x[t] == dtype(wh.FAR_VALUE))
+            # kind 2: the largest logit of a far frame lies below GMMIV_ZERO_LLK by a wide margin
+            w, mean, iv = wh.gr.model(case["gcase"])
+            z = np.log(w) + 0.5 * np.log(iv).sum(1) - 0.5 * D * np.log(2 * np.pi) - 0.5 * (((x[k2[0]].astype(np.float64) - mean) ** 2) * iv).sum(1)
+            assert z.max() < 10 * wh.gr.ZERO_LLK
+    for case in wh.SMALL:
+        assert wh.planted(case) == ({}, ()) and np.isfinite(wh.frames(case, "host")).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- coverage
+HANDLE = re.compile(r"\bgmmiv_(ctx|gmm|gmm_batch)\s*\*")
+
+
+def abi_functions():
+    """{name: argument text} of every function prototype of include/gmmiv.h"""
+    src = open(os.path.join(ROOT, "include", "gmmiv.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = "\n".join(l for l in src.split("\n") if not l.lstrip().startswith("#"))
+    return {m.group(1): m.group(2) for m in re.finditer(r"\b(gmmiv_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", src)}
+
+
+def binding_calls():
+    """capi.py by source: {function or method name: the lib.gmmiv_* calls in its body}, following self.method() one level"""
+    src = open(os.path.join(ROOT, "lia_ral_amd", "capi.py")).read()
+    tree = ast.parse(src)
+    direct, inner = {}, {}
+    for node in ast.walk(tree):
+        if isinstance(node, ast.FunctionDef):
+            libs, calls = set(), set()
+            for n in ast.walk(node):
+                if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "lib" and n.attr.startswith("gmmiv_"):
+                    libs.add(n.attr)
+                if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and isinstance(n.func.value, ast.Name) and n.func.value.id == "self":
+                    calls.add(n.func.attr)
+                if isinstance(n, ast.Call) and isinstance(n.func, ast.Name):
+                    calls.add(n.func.id)
+            direct.setdefault(node.name, set()).update(libs)
+            inner.setdefault(node.name, set()).update(calls)
+    return {name: libs.union(*[direct.get(c, set()) for c in inner[name]]) for name, libs in direct.items()}
+
+
+def source_of(fn, seen=None):
+    """the source of a step function and of the module-level helpers of ws_history it names"""
+    seen = set() if seen is None else seen
+    if fn in seen:
+        return ""
+    seen.add(fn)
+    text = inspect.getsource(fn)
+    for name in fn.__code__.co_names:
+        g = getattr(wh, name, None)
+        if inspect.isfunction(g) and g.__module__ == wh.__name__:
+            text += source_of(g, seen)
+        elif inspect.isclass(g) and g.__module__ == wh.__name__:
+            text += inspect.getsource(g)
+    return text
+
+
+def test_the_abi_is_parsed():
+    f = abi_functions()
+    assert len(f) > 100 and "gmmiv_llk" in f and "gmmiv_ctx_stream" in f and "gmmiv_llr_trials" in f
+    assert HANDLE.search(f["gmmiv_llk"]) and not HANDLE.search(f["gmmiv_em_acc_len"]) and not HANDLE.search(f["gmmiv_allreduce_f64"])
+
+
+def test_every_abi_function_with_a_handle_is_reached_or_exempt():
+    f = abi_functions()
+    subject = {n for n, args in f.items() if HANDLE.search(args)}
+    reached = {e for s in wh.PROGRAMME for e in s.reaches} | set(wh.PLUMBING) | set(wh.HANDLE_TESTS)
+    unknown = (reached | set(wh.EXEMPT)) - set(f)
+    assert not unknown, "named by the programme but not in include/gmmiv.h: %s" % sorted(unknown)
+    both = reached & set(wh.EXEMPT)
+    assert not both, "reached AND exempt: %s" % sorted(both)
+    missing = subject - reached - set(wh.EXEMPT)
+    assert not missing, "ABI functions with a handle that no step reaches and EXEMPT does not name: %s" % sorted(missing)
+    for name, reason in wh.EXEMPT.items():
+        assert reason in wh.EXEMPT_REASONS, (name, reason)
+    # "no workspace" is checked: the body of such a function holds no scratch( and no DevIn / DevOut
+    csrc = os.path.join(ROOT, "lia_ral_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".cpp")))
+    for name, reason in wh.EXEMPT.items():
+        if reason != wh._NO_WS:
+            continue
+        m = re.search(r"\b%s\s*\([^;{)]*\)\s*\{" % name, text)
+        assert m, "no definition of %s found" % name
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(text[i], 0)
+            i += 1
+        body = text[m.end():i]
+        assert "scratch(" not in body and "DevIn" not in body and "DevOut" not in body, name
+
+
+def test_every_step_calls_the_bindings_of_the_entry_points_it_names():
+    calls = binding_calls()
+    wrappers = {}                                   # C entry point -> the binding functions that call it
+    for fn, libs in calls.items():
+        for l in libs:
+            wrappers.setdefault(l, set()).add(fn)
+    for step in wh.PROGRAMME:
+        text = source_of(step.fn)
+        assert step.reaches, step.name
+        for entry in step.reaches:
+            assert entry in wrappers, "%s: capi.py has no lib.%s call" % (step.name, entry)
+            assert any(re.search(r"\.%s\(" % w, text) for w in wrappers[entry]), \
+                "step %r names %s but calls none of its bindings %s" % (step.name, entry, sorted(wrappers[entry]))
+    plumbing = "".join(inspect.getsource(o) for o in (wh.Handles, wh.Step, wh.nan_calls, wh.workspace_table, wh.run_sequence, wh.counters, wh.s_em, wh.s_tv))
+    for entry in wh.PLUMBING:
+        names = {"__init__": {"Context", "gmm", "gmm_batch"}, "__del__": {"close"}}
+        ws = set().union(*[names.get(w, {w}) for w in wrappers[entry]])
+        assert any(re.search(r"\b%s\(" % w, plumbing) for w in ws), (entry, sorted(ws))
+    gpu_test = open(os.path.join(ROOT, "tests", "test_gpu_ws_history.py")).read()
+    for entry, method in wh.HANDLE_TESTS.items():
+        assert method in wrappers[entry] and re.search(r"\.%s\(" % method, gpu_test), entry
+
+
+def test_step_names_are_unique_and_both_forms_exist():
+    names = [s.name for s in wh.PROGRAMME]
+    assert len(names) == len(set(names)) and set(wh.STEPS) == set(names)
+    for s in wh.PROGRAMME:
+        assert s.forms == wh.FORMS, "%s: every binding this step calls accepts device tensors, so both forms run" % s.name
+        assert "form" in inspect.signature(s.fn).parameters
+        assert any(s.applies(c) for c in wh.SMALL) and any(s.applies(c) for c in wh.LARGE)
+    # the options of the programme have defaults in the shared bracket
+    from elementwise_judge import DEFAULTS
+    for s in wh.PROGRAMME:
+        assert set(s.opts) <= set(DEFAULTS)
+    for c in wh.SMALL + wh.LARGE:
+        assert set(c["opts"]) <= set(DEFAULTS)
+    # a sequence is a list of passes over SMALL or LARGE
+    assert set(wh.SEQUENCES) >= {"fresh_small", "fresh_small_again", "fresh_large", "large_then_small", "large_then_small_reversed", "small_then_large"}
+    assert [i[1].name for i in wh.plan(wh.SMALL, True)] == [i[1].name for i in wh.plan(wh.SMALL)][::-1]
