@@ -696,6 +696,48 @@ class Context:
                                   ns.ctypes.data_as(ct.c_void_p), _ptr(segs), _ptr(FTJF), _ptr(out)))
         return out
 
+    # ---- the scoring rules on a LIST of (model, segment) trials (include/gmmiv_iv_trials.h)
+    def iv_trial_piece(self):
+        """gmmiv_iv_trial_piece: the trials per work item the list rules use on this context"""
+        return int(lib.gmmiv_iv_trial_piece(self._h))
+
+    @staticmethod
+    def _trial_args(trial_model, trial_seg, out):
+        # a device tensor is passed on as it is: the library refuses it with a message
+        tm = trial_model if _is_torch(trial_model) else np.ascontiguousarray(trial_model, dtype=np.int32)
+        ts = trial_seg if _is_torch(trial_seg) else np.ascontiguousarray(trial_seg, dtype=np.int32)
+        assert len(tm) == len(ts)
+        if out is None:
+            out = np.empty(len(tm))
+        return tm, ts, out
+
+    def score_cosine_trials(self, models, segs, trial_model, trial_seg, out=None):
+        """the cosine score of every listed trial (trial_model[i], trial_seg[i]), in list order; out: numpy or a device tensor [ntrial]"""
+        tm, ts, out = self._trial_args(trial_model, trial_seg, out)
+        _chk(lib.gmmiv_score_cosine_trials(self._h, models.shape[0], ct.c_int64(models.shape[1]), ct.c_int64(segs.shape[1]), _ptr(models),
+                                           _ptr(segs), _ptr(tm), _ptr(ts), ct.c_int64(len(tm)), _ptr(out)))
+        return out
+
+    def score_mahalanobis_trials(self, models, segs, Mah, trial_model, trial_seg, out=None):
+        tm, ts, out = self._trial_args(trial_model, trial_seg, out)
+        _chk(lib.gmmiv_score_mahalanobis_trials(self._h, models.shape[0], ct.c_int64(models.shape[1]), ct.c_int64(segs.shape[1]),
+                                                _ptr(models), _ptr(segs), _ptr(Mah), _ptr(tm), _ptr(ts), ct.c_int64(len(tm)), _ptr(out)))
+        return out
+
+    def score_twocov_trials(self, models, segs, G, H, trial_model, trial_seg, out=None):
+        tm, ts, out = self._trial_args(trial_model, trial_seg, out)
+        _chk(lib.gmmiv_score_twocov_trials(self._h, models.shape[0], ct.c_int64(models.shape[1]), ct.c_int64(segs.shape[1]), _ptr(models),
+                                           _ptr(segs), _ptr(G), _ptr(H), _ptr(tm), _ptr(ts), ct.c_int64(len(tm)), _ptr(out)))
+        return out
+
+    def score_plda_trials(self, models_sum, nsess, segs, FTJF, trial_model, trial_seg, out=None):
+        tm, ts, out = self._trial_args(trial_model, trial_seg, out)
+        ns = np.ascontiguousarray(nsess, dtype=np.int64)
+        _chk(lib.gmmiv_score_plda_trials(self._h, models_sum.shape[0], ct.c_int64(models_sum.shape[1]), ct.c_int64(segs.shape[1]),
+                                         _ptr(models_sum), ns.ctypes.data_as(ct.c_void_p), _ptr(segs), _ptr(FTJF), _ptr(tm), _ptr(ts),
+                                         ct.c_int64(len(tm)), _ptr(out)))
+        return out
+
     # ---- score normalisation (LIA_SpkDet/ComputeNorm): cohort statistics + the (x - mean) / std passes
     def score_cohort_stats(self, scores, axis, select=None, pre_mean=None, pre_std=None, mean_mode=0, percent_h=0.0,
                            percent_l=0.0, out_mean=None, out_std=None):
@@ -1169,6 +1211,47 @@ def plan_trial_tiles(seg_begin, trial_seg, trial_model, piece_frames=TRIAL_PIECE
     buf = (TrialTile * max(int(n), 1))()
     lib.gmmiv_plan_trial_tiles(*args, ct.cast(buf, ct.c_void_p), ct.c_int64(n))
     return [{k: getattr(buf[i], k) for k, _ in TrialTile._fields_} for i in range(int(n))]
+
+
+lib.gmmiv_plan_iv_trial_tiles.restype = ct.c_int64
+IV_TRIAL_PIECE = int(lib.gmmiv_iv_trial_piece(None))  # GMMIV_IV_TRIAL_PIECE, read from the library
+IV_ANCHOR_AUTO, IV_ANCHOR_MODEL, IV_ANCHOR_SEG = 0, 1, 2
+
+
+class IvTrialTile(ct.Structure):
+    """gmmiv_iv_trial_tile: one wave of k_score_trials"""
+    _fields_ = [("anchor", ct.c_int32), ("reserved", ct.c_int32), ("lo", ct.c_int64), ("hi", ct.c_int64)]
+
+
+def iv_trial_anchor(M, S, trial_model, trial_seg):
+    """gmmiv_iv_trial_anchor (host only): IV_ANCHOR_SEG when the list names fewer distinct segments than models, else IV_ANCHOR_MODEL"""
+    tm = np.ascontiguousarray(trial_model, np.int32)
+    ts = np.ascontiguousarray(trial_seg, np.int32)
+    r = lib.gmmiv_iv_trial_anchor(ct.c_int64(M), ct.c_int64(S), tm.ctypes.data_as(ct.c_void_p), ts.ctypes.data_as(ct.c_void_p), ct.c_int64(len(tm)))
+    if r < 0:
+        raise GmmivError("gmmiv_iv_trial_anchor: bad argument")
+    return int(r)
+
+
+def plan_iv_trial_tiles(M, S, trial_model, trial_seg, anchor=IV_ANCHOR_AUTO, piece=IV_TRIAL_PIECE, cap=None):
+    """gmmiv_plan_iv_trial_tiles (host only, needs no GPU) -> (order [ntrial] int64: list positions sorted by (anchor, partner, position),
+    tiles: list of (anchor, lo, hi), the number of tiles counted).  cap: write at most that many tiles (the count still covers all)."""
+    tm = np.ascontiguousarray(trial_model, np.int32)
+    ts = np.ascontiguousarray(trial_seg, np.int32)
+    assert len(tm) == len(ts)
+    args = (ct.c_int64(M), ct.c_int64(S), tm.ctypes.data_as(ct.c_void_p), ts.ctypes.data_as(ct.c_void_p), ct.c_int64(len(tm)), int(anchor), int(piece))
+    n = lib.gmmiv_plan_iv_trial_tiles(*args, ct.c_void_p(0), ct.c_void_p(0), ct.c_int64(0))
+    if n < 0:
+        raise GmmivError("gmmiv_plan_iv_trial_tiles: bad argument")
+    keep = int(n) if cap is None else min(int(cap), int(n))
+    guard = 4                                           # entries behind `cap` that must stay untouched
+    buf = (IvTrialTile * (keep + guard))()
+    for i in range(keep, keep + guard):
+        buf[i].anchor = -7
+    order = np.zeros(len(tm), np.int64)
+    n2 = lib.gmmiv_plan_iv_trial_tiles(*args, order.ctypes.data_as(ct.c_void_p), ct.cast(buf, ct.c_void_p), ct.c_int64(keep))
+    assert n2 == n and all(buf[i].anchor == -7 for i in range(keep, keep + guard))
+    return order, [(buf[i].anchor, buf[i].lo, buf[i].hi) for i in range(keep)], int(n)
 
 
 MAP_METHODS = {"MAPOccDep": 1, "MAPModelBased": 2, "MAPConst": 3, "MAPConst2": 4}  # anything else: 0, the ML estimate (computeMAP's "mapAlgo unknown")

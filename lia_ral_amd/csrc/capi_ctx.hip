@@ -112,6 +112,8 @@ long gmmiv_ctx_set_option(gmmiv_ctx *c, const char *key, long value)
     else if (!strcmp(key, "models_scratch_mb")) slot = &c->models_scratch_mb;
     else if (!strcmp(key, "trials_scratch_mb")) slot = &c->trials_scratch_mb;
     else if (!strcmp(key, "trials_piece")) slot = &c->trials_piece;
+    else if (!strcmp(key, "iv_trials_anchor")) slot = &c->iv_trials_anchor;
+    else if (!strcmp(key, "iv_trials_piece")) slot = &c->iv_trials_piece;
     else if (!strcmp(key, "tv_batch")) slot = &c->tv_batch;
     else if (!strcmp(key, "tv_tett_direct")) slot = &c->tv_tett_direct;
     else if (!strcmp(key, "tv_stats_split")) slot = &c->tv_stats_split;

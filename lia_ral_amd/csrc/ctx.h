@@ -38,6 +38,7 @@ enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, 
        WS_NORM_OFF, WS_NORM_STATE, WS_NORM_DECAY,
        WS_MB_PT, WS_MB_TILES, WS_MB_IDS, WS_MB_SEG, WS_MB_OFF, WS_MB_FTILES, WS_MB_OFFSRC,
        WS_TR_IDX, WS_TR_NLLK, WS_TR_LLKW, WS_TR_TILES, WS_TR_TAB, WS_TR_PART, WS_TR_ROW,
+       WS_IVT_M, WS_IVT_S, WS_IVT_OUT, WS_IVT_A, WS_IVT_B, WS_IVT_Y, WS_IVT_Q, WS_IVT_MAT, WS_IVT_TAB,
        WS_COUNT }; // WS_GFLAG: the per-frame flags of the kind-(1) counting pass; WS_NORM: score_norm.h, the counts of a device mask;
                    // WS_FEAT_*: gmmiv_feat_compensate / gmmiv_feat_map (packed offsets, a staged host output, top-1 indices, the four model tables);
                    // WS_NORM_*: gmmiv_feat_norm_online (chunk offsets of the files, the carried states, the chunks' decay products)
@@ -45,6 +46,8 @@ enum { WS_X = 0, WS_LSE, WS_PART, WS_SEG, WS_SMALL, WS_T0, WS_T1, WS_T2, WS_T3, 
                    // gmmiv_feat_compensate_models: the packed offsets of a chunk's models, the k_feat_comp tile tables, staged host offsets)
                    // WS_TR_*: gmmiv_llr_trials (a chunk's world indices / remainders / log-likelihoods, the tile table, the trial and segment
                    // tables, the piece partials of the whole call, one trial's per-frame row on the any-shape path)
+                   // WS_IVT_*: gmmiv_score_*_trials (staged host models / segments / scores, the row tables A and B, the GEMM result behind
+                   // qm / qs, qm | qs, the rule's matrices, the tile table with the partner and position arrays)
 
 struct gmmiv_ctx {
     int device = 0;
@@ -108,6 +111,10 @@ struct gmmiv_ctx {
     // whole segments; "trials_piece" (A/B knob, 0 = GMMIV_TRIAL_PIECE) changes the summation pieces and with them the last bits
     long trials_scratch_mb = 2048;
     long trials_piece = 0;
+    // gmmiv_score_*_trials: the anchor side (0 auto, 1 model, 2 segment) and the trials per work item (<= 0: GMMIV_IV_TRIAL_PIECE); A/B
+    // knobs that change no bit of any score
+    long iv_trials_anchor = 0;
+    long iv_trials_piece = 0;
     int n_cu = 256;
     // gmmiv_score_plda: K_n = (n FTJF + I)^-1 and log det K_n per session count n, kept while FTJF stays the same matrix
     // (each costs an O(rankF^3) inverse on the host: 3 ms per call at rankF = 200 when recomputed every time)

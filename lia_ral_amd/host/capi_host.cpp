@@ -781,11 +781,13 @@ int liagpu_plda_train(int device, int dim, long n, double *X, long nspk, const l
 
 // IvTest (IvTest.cpp:73-471).  scoring: 0 cosine, 1 mahalanobis, 2 2cov, 3 plda.  dev [dim x nDev] with sessions grouped by
 // speaker; enrol [dim x nEnrol] grouped by model; test [dim x nTest]; scores [nModels x nTest].
-int liagpu_iv_test(int device, int dim, long nDev, const double *dev, long nspk, const long *sps, long nModels, const long *enrolPerModel,
-                   const double *enrol, long nTest, const double *test, int ivNorm, int ivNormIt, int sphNorm, int lda, int ldaRank,
-                   int wccn, int scoring, int rf, int rg, int pldaIt, const double *F, const double *G, const double *Sigma, double *scores)
+// pldaScoring: 0 native, 1 enrollMean.  trialModel == NULL: the dense matrix [nModels x nTest]; else one score per listed trial.
+static void iv_test_impl(int device, int dim, long nDev, const double *dev, long nspk, const long *sps, long nModels, const long *enrolPerModel,
+                         const double *enrol, long nTest, const double *test, int ivNorm, int ivNormIt, int sphNorm, int lda, int ldaRank,
+                         int wccn, int scoring, int rf, int rg, int pldaIt, const double *F, const double *G, const double *Sigma, int pldaScoring,
+                         long ntrial, const int32_t *trialModel, const int32_t *trialSeg, double *scores)
 {
-    GUARD({
+    {
         static const char *names[] = {"cosine", "mahalanobis", "2cov", "plda"};
         if (scoring < 0 || scoring > 3) throw Exception("Scoring option is invalid, must be: cosine OR mahalanobis OR 2cov OR plda");
         GpuServer srv(device);
@@ -794,6 +796,8 @@ int liagpu_iv_test(int device, int dim, long nDev, const double *dev, long nspk,
         cfg.ivNorm = ivNorm != 0; cfg.ivNormIterationNb = (unsigned long)ivNormIt; cfg.sphNorm = sphNorm != 0;
         cfg.LDA = lda != 0; cfg.ldaRank = (unsigned long)ldaRank; cfg.WCCN = wccn != 0; cfg.scoring = names[scoring];
         cfg.pldaRankF = (unsigned long)rf; cfg.pldaRankG = (unsigned long)rg; cfg.pldaNbIt = (unsigned long)pldaIt;
+        if (pldaScoring != 0 && pldaScoring != 1) throw Exception("pldaScoring must be: native OR enrollMean");
+        cfg.pldaScoring = pldaScoring ? "enrollMean" : "native";
         std::vector<unsigned long> epm(enrolPerModel, enrolPerModel + nModels);
         unsigned long nEnrol = 0;
         for (unsigned long e : epm) nEnrol += e;
@@ -804,9 +808,97 @@ int liagpu_iv_test(int device, int dim, long nDev, const double *dev, long nspk,
             const unsigned long pd_dim = cfg.ivNorm && cfg.LDA ? cfg.ldaRank : (unsigned long)dim;
             f.assign(F, F + pd_dim * rf); g.assign(G, G + pd_dim * rg); s.assign(Sigma, Sigma + pd_dim * pd_dim);
         }
-        std::vector<double> out = ivTest(srv, cfg, pd, std::vector<double>(enrol, enrol + (size_t)dim * nEnrol), epm,
-                                         std::vector<double>(test, test + (size_t)dim * nTest), (unsigned long)nTest, f, g, s);
+        std::vector<double> out;
+        if (trialModel)
+            out = ivTestTrials(srv, cfg, pd, std::vector<double>(enrol, enrol + (size_t)dim * nEnrol), epm, std::vector<double>(test, test + (size_t)dim * nTest),
+                               (unsigned long)nTest, std::vector<int32_t>(trialModel, trialModel + ntrial), std::vector<int32_t>(trialSeg, trialSeg + ntrial), f, g, s);
+        else
+            out = ivTest(srv, cfg, pd, std::vector<double>(enrol, enrol + (size_t)dim * nEnrol), epm,
+                         std::vector<double>(test, test + (size_t)dim * nTest), (unsigned long)nTest, f, g, s);
         memcpy(scores, out.data(), out.size() * sizeof(double));
+    }
+}
+int liagpu_iv_test(int device, int dim, long nDev, const double *dev, long nspk, const long *sps, long nModels, const long *enrolPerModel,
+                   const double *enrol, long nTest, const double *test, int ivNorm, int ivNormIt, int sphNorm, int lda, int ldaRank,
+                   int wccn, int scoring, int rf, int rg, int pldaIt, const double *F, const double *G, const double *Sigma, double *scores)
+{
+    GUARD(iv_test_impl(device, dim, nDev, dev, nspk, sps, nModels, enrolPerModel, enrol, nTest, test, ivNorm, ivNormIt, sphNorm, lda, ldaRank, wccn,
+                       scoring, rf, rg, pldaIt, F, G, Sigma, 0, 0, nullptr, nullptr, scores))
+}
+// IvTest on a list of trials (liagpu::ivTestTrials): trial i = (trialModel[i], trialSeg[i]), scores [ntrial] in list order.  pldaScoring:
+// 0 native, 1 enrollMean.  trialModel == NULL runs the dense liagpu::ivTest with that pldaScoring: scores [nModels x nTest].
+int liagpu_iv_test_trials(int device, int dim, long nDev, const double *dev, long nspk, const long *sps, long nModels, const long *enrolPerModel,
+                          const double *enrol, long nTest, const double *test, int ivNorm, int ivNormIt, int sphNorm, int lda, int ldaRank,
+                          int wccn, int scoring, int rf, int rg, int pldaIt, const double *F, const double *G, const double *Sigma, int pldaScoring,
+                          long ntrial, const int32_t *trialModel, const int32_t *trialSeg, double *scores)
+{
+    GUARD({
+        if (ntrial < 0 || (trialModel && !trialSeg)) throw Exception("liagpu_iv_test_trials: bad trial list");
+        iv_test_impl(device, dim, nDev, dev, nspk, sps, nModels, enrolPerModel, enrol, nTest, test, ivNorm, ivNormIt, sphNorm, lda, ldaRank, wccn, scoring,
+                     rf, rg, pldaIt, F, G, Sigma, pldaScoring, ntrial, trialModel, trialSeg, scores);
+    })
+}
+// loadIvTestNdx (host only): the counts in dims = {models, segments, trials, dropped, enrolment sessions, maxSessions}; with text != NULL the
+// tables as text (cap bytes): one line "M <id> <session> ..." per model, "S <id>" per segment, "T <model index> <segment index>" per trial
+int liagpu_iv_test_ndx_load(const char *ndx, const char *targetIdList, long *dims, char *text, long cap)
+{
+    GUARD({
+        const IvTestNdx nx = loadIvTestNdx(ndx, targetIdList ? targetIdList : "");
+        size_t nsess = 0;
+        for (const auto &v : nx.sessions) nsess += v.size();
+        dims[0] = (long)nx.models.size(); dims[1] = (long)nx.segs.size(); dims[2] = (long)nx.trialModel.size(); dims[3] = (long)nx.dropped;
+        dims[4] = (long)nsess; dims[5] = (long)nx.maxSessions;
+        if (text) {
+            std::ostringstream o;
+            for (size_t m = 0; m < nx.models.size(); ++m) {
+                o << "M " << nx.models[m];
+                for (const std::string &e : nx.sessions[m]) o << " " << e;
+                o << "\n";
+            }
+            for (const std::string &e : nx.segs) o << "S " << e << "\n";
+            for (size_t i = 0; i < nx.trialModel.size(); ++i) o << "T " << nx.trialModel[i] << " " << nx.trialSeg[i] << "\n";
+            const std::string t = o.str();
+            if ((long)t.size() + 1 > cap) throw Exception("liagpu_iv_test_ndx_load: text buffer too small");
+            memcpy(text, t.c_str(), t.size() + 1);
+        }
+    })
+}
+// IvTest from files on an ndx (liagpu::ivTestFiles): the development set as arrays, the enrolment and test vectors from
+// <vector_path>/<id><vector_ext> (matrix format fmt), the result lines into out_path in the order of IvTest.cpp:430-437.  With
+// line_model / line_seg / scores (cap entries each, nullable) the trial and the score of every line; *n_lines = their number.
+int liagpu_iv_test_ndx(int device, int dim, long nDev, const double *dev, long nspk, const long *sps, const char *ndx, const char *targetIdList,
+                       const char *vector_path, const char *vector_ext, const char *fmt, const char *out_path, const char *gender, double threshold,
+                       int ivNorm, int ivNormIt, int sphNorm, int lda, int ldaRank, int wccn, int scoring, int rf, int rg, int pldaIt, const double *F,
+                       const double *G, const double *Sigma, int pldaScoring, long cap, int32_t *line_model, int32_t *line_seg, double *scores,
+                       long *n_lines)
+{
+    GUARD({
+        static const char *names[] = {"cosine", "mahalanobis", "2cov", "plda"};
+        if (scoring < 0 || scoring > 3) throw Exception("Scoring option is invalid, must be: cosine OR mahalanobis OR 2cov OR plda");
+        if (pldaScoring != 0 && pldaScoring != 1) throw Exception("pldaScoring must be: native OR enrollMean");
+        GpuServer srv(device);
+        PldaDev pd(srv, (unsigned long)dim, std::vector<double>(dev, dev + (size_t)dim * nDev), std::vector<unsigned long>(sps, sps + nspk));
+        IvTestFilesCfg cfg;
+        cfg.test.ivNorm = ivNorm != 0; cfg.test.ivNormIterationNb = (unsigned long)ivNormIt; cfg.test.sphNorm = sphNorm != 0;
+        cfg.test.LDA = lda != 0; cfg.test.ldaRank = (unsigned long)ldaRank; cfg.test.WCCN = wccn != 0; cfg.test.scoring = names[scoring];
+        cfg.test.pldaRankF = (unsigned long)rf; cfg.test.pldaRankG = (unsigned long)rg; cfg.test.pldaNbIt = (unsigned long)pldaIt;
+        cfg.test.pldaScoring = pldaScoring ? "enrollMean" : "native";
+        cfg.ndxFilename = ndx; cfg.targetIdList = targetIdList ? targetIdList : ""; cfg.vectorFilesPath = vector_path; cfg.vectorFilesExtension = vector_ext;
+        cfg.loadMatrixFormat = fmt; cfg.outputFilename = out_path ? out_path : ""; cfg.gender = gender ? gender : "M"; cfg.decisionThreshold = threshold;
+        std::vector<double> f, g, s;
+        if (scoring == 3) {
+            const unsigned long pd_dim = cfg.test.ivNorm && cfg.test.LDA ? cfg.test.ldaRank : (unsigned long)dim;
+            f.assign(F, F + pd_dim * rf); g.assign(G, G + pd_dim * rg); s.assign(Sigma, Sigma + pd_dim * pd_dim);
+        }
+        const IvTestFilesResult r = ivTestFiles(srv, cfg, pd, f, g, s);
+        const long n = (long)r.scores.size();
+        if (n_lines) *n_lines = n;
+        if (line_model || line_seg || scores) {
+            if (n > cap) throw Exception("liagpu_iv_test_ndx: output arrays too small");
+            if (line_model) memcpy(line_model, r.lineModel.data(), (size_t)n * sizeof(int32_t));
+            if (line_seg) memcpy(line_seg, r.lineSeg.data(), (size_t)n * sizeof(int32_t));
+            if (scores) memcpy(scores, r.scores.data(), (size_t)n * sizeof(double));
+        }
     })
 }
 

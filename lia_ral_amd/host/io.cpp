@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <fstream>
 #include <map>
 #include <sstream>
@@ -716,6 +717,112 @@ void energyDetectorFiles(GpuServer &srv, const std::vector<std::string> &names, 
         for (const Seg &g : out[k])
             o << frameIdxToTime(g.begin, cfg.frameLength) << " " << frameIdxToTime(g.begin + g.length - 1, cfg.frameLength) << " " << cfg.labelOutputFrames << std::endl;
     }
+}
+
+// ---- IvTest on an ndx ----------------------------------------------------------------------------------------------------------
+namespace {
+// the lines of an XList: blank-separated elements, empty lines skipped
+std::vector<std::vector<std::string> > readListLines(const std::string &path, const char *what)
+{
+    std::ifstream in(path.c_str());
+    if (!in) throw Exception(std::string("cannot open the ") + what + " [" + path + "]");
+    std::vector<std::vector<std::string> > lines;
+    std::string line;
+    while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        std::vector<std::string> el;
+        std::string tok;
+        while (ls >> tok) el.push_back(tok);
+        if (!el.empty()) lines.push_back(el);
+    }
+    return lines;
+}
+} // namespace
+
+IvTestNdx loadIvTestNdx(const std::string &ndx, const std::string &targetIdList)
+{
+    IvTestNdx out;
+    const std::vector<std::vector<std::string> > test = readListLines(ndx, "ndx file");
+    std::map<std::string, int32_t> modelOf, segOf;
+    const bool idList = !targetIdList.empty(); // PldaTools.cpp:3473
+    if (idList) {
+        std::vector<std::vector<std::string> > enrol = readListLines(targetIdList, "targetIdList");
+        if (enrol.empty()) throw Exception("targetIdList [" + targetIdList + "] is empty");
+        // enrollList.sortByElementNumber("descend") (:3487); lines of equal length keep file order (assumed, see io.h)
+        std::stable_sort(enrol.begin(), enrol.end(), [](const std::vector<std::string> &a, const std::vector<std::string> &b) { return a.size() > b.size(); });
+        out.maxSessions = (unsigned long)enrol[0].size() - 1; // :3495
+        for (const std::vector<std::string> &l : enrol) {     // :3497-3511
+            auto it = modelOf.find(l[0]);
+            if (it == modelOf.end()) {
+                it = modelOf.emplace(l[0], (int32_t)out.models.size()).first;
+                out.models.push_back(l[0]);
+                out.sessions.emplace_back();
+            }
+            for (size_t e = 1; e < l.size(); ++e) out.sessions[(size_t)it->second].push_back(l[e]);
+        }
+    }
+    std::map<std::pair<int32_t, int32_t>, bool> seen;
+    for (const std::vector<std::string> &l : test) { // :3520-3545 and :3606-3620 in one pass: the indices never change once given
+        auto is = segOf.find(l[0]);
+        if (is == segOf.end()) {
+            is = segOf.emplace(l[0], (int32_t)out.segs.size()).first;
+            out.segs.push_back(l[0]);
+        }
+        for (size_t e = 1; e < l.size(); ++e) {
+            auto im = modelOf.find(l[e]);
+            if (im == modelOf.end()) {
+                if (idList) { ++out.dropped; continue; } // "WARNING: model ... has no enrollment session" (:3535)
+                im = modelOf.emplace(l[e], (int32_t)out.models.size()).first;
+                out.models.push_back(l[e]);
+                out.sessions.push_back(std::vector<std::string>(1, l[e]));
+            }
+            if (seen.emplace(std::make_pair(im->second, is->second), true).second) {
+                out.trialModel.push_back(im->second);
+                out.trialSeg.push_back(is->second);
+            }
+        }
+    }
+    return out;
+}
+
+IvTestFilesResult ivTestFiles(GpuServer &srv, const IvTestFilesCfg &cfg, PldaDev &dev, const std::vector<double> &pldaF, const std::vector<double> &pldaG,
+                              const std::vector<double> &pldaSigma)
+{
+    IvTestFilesResult r;
+    r.ndx = loadIvTestNdx(cfg.ndxFilename, cfg.targetIdList);
+    const IvTestNdx &nx = r.ndx;
+    if (nx.models.empty() || nx.segs.empty()) throw Exception("ivTestFiles: the ndx [" + cfg.ndxFilename + "] names no model or no segment");
+    std::vector<std::string> enrolIds;
+    std::vector<unsigned long> enrolPerModel;
+    for (const std::vector<std::string> &s : nx.sessions) {
+        if (s.empty()) throw Exception("ivTestFiles: a model of the targetIdList has no enrolment session");
+        enrolIds.insert(enrolIds.end(), s.begin(), s.end());
+        enrolPerModel.push_back((unsigned long)s.size());
+    }
+    unsigned long dimE = 0, dimT = 0;
+    std::vector<double> enrol = loadVectorsById(cfg.vectorFilesPath, enrolIds, cfg.vectorFilesExtension, dimE, cfg.loadMatrixFormat);
+    std::vector<double> test = loadVectorsById(cfg.vectorFilesPath, nx.segs, cfg.vectorFilesExtension, dimT, cfg.loadMatrixFormat);
+    if (dimE != dimT || dimE != dev.getVectSize()) throw Exception("ivTestFiles: the vector files and the development set differ in dimension");
+    const std::vector<double> sc = ivTestTrials(srv, cfg.test, dev, enrol, enrolPerModel, test, (unsigned long)nx.segs.size(), nx.trialModel, nx.trialSeg,
+                                                pldaF, pldaG, pldaSigma);
+    // IvTest.cpp:430-437: for every segment, the models in index order
+    std::vector<size_t> order(sc.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        return nx.trialSeg[a] != nx.trialSeg[b] ? nx.trialSeg[a] < nx.trialSeg[b] : nx.trialModel[a] < nx.trialModel[b];
+    });
+    for (size_t i : order) {
+        r.lineModel.push_back(nx.trialModel[i]);
+        r.lineSeg.push_back(nx.trialSeg[i]);
+        r.scores.push_back(sc[i]);
+    }
+    if (!cfg.outputFilename.empty()) {
+        std::ofstream o(cfg.outputFilename.c_str(), std::ios::out | std::ios::trunc);
+        if (!o.good()) throw Exception("Can't create the result file [" + cfg.outputFilename + "]");
+        for (size_t k = 0; k < r.scores.size(); ++k)
+            o << resultLine(r.scores[k], nx.models[(size_t)r.lineModel[k]], nx.segs[(size_t)r.lineSeg[k]], cfg.gender, cfg.decisionThreshold) << std::endl;
+    }
+    return r;
 }
 
 } // namespace liagpu

@@ -124,6 +124,39 @@ ComputeNormLists loadComputeNormLists(const ComputeNormFilesCfg &cfg);          
 void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg, ComputeNormLists &lists); // normalise + write the output files
 void computeNormListFiles(GpuServer &srv, const ComputeNormFilesCfg &cfg);
 
+// IvTest driven by an ndx (PldaTest::load, PldaTools.cpp:3467-3620; the inputVectorFilename mode -- all against all -- stays with
+// liagpu::ivTest).  Every line of the ndx is "segment model model ...".
+//   without a targetIdList: a model is one vector, named by the ndx; models and segments are indexed in order of first appearance
+//   with one:               its lines "model session session ..." define the models, read in DESCENDING order of their element count
+//                           (XList::sortByElementNumber("descend"); the order of lines of equal count is alize-core's and cannot be
+//                           read in the LIA_RAL tree: ASSUMED stable, i.e. file order).  A model named on several lines is one model
+//                           with the sessions of all of them.  A trial whose model has no enrolment session is DROPPED and counted
+//                           (the reference prints a warning and then indexes _trials with -1).
+// The trial list has duplicates removed -- _trials is a matrix of flags -- and keeps the order of first appearance.
+struct IvTestNdx {
+    std::vector<std::string> models, segs;                 // ids, by index
+    std::vector<std::vector<std::string> > sessions;       // the enrolment sessions of every model (the model's own id without a targetIdList)
+    std::vector<int32_t> trialModel, trialSeg;             // the trials, duplicates removed
+    unsigned long dropped = 0;                             // trials of the ndx whose model has no enrolment session
+    unsigned long maxSessions = 1;                         // _n_enrollSessions_max
+};
+IvTestNdx loadIvTestNdx(const std::string &ndx, const std::string &targetIdList = ""); // host only
+// IvTest from files: the vectors <vectorFilesPath>/<id><vectorFilesExtension> of the enrolment sessions and of the segments
+// (loadVectorsById), the development set as it is given, liagpu::ivTestTrials on the ndx's trials, and the ASCII result file in the order
+// of IvTest.cpp:430-437: segment-major, model index ascending, one resultLine per trial.  Returns the scores in that order.
+struct IvTestFilesCfg {
+    IvTestCfg test;
+    std::string ndxFilename, targetIdList, vectorFilesPath, vectorFilesExtension = ".y", loadMatrixFormat = "DB";
+    std::string outputFilename, gender = "M";
+    double decisionThreshold = 0.0;
+};
+struct IvTestFilesResult {
+    IvTestNdx ndx;
+    std::vector<int32_t> lineModel, lineSeg;               // the trial of every output line
+    std::vector<double> scores;                            // its score
+};
+IvTestFilesResult ivTestFiles(GpuServer &srv, const IvTestFilesCfg &cfg, PldaDev &dev, const std::vector<double> &pldaF = std::vector<double>(),
+                              const std::vector<double> &pldaG = std::vector<double>(), const std::vector<double> &pldaSigma = std::vector<double>());
 
 // NormFeat driven by files (NormFeat.cpp:302-509): every feature file <featureFilesPath><name><loadFeatureFileExtension> of the list is
 // loaded at its full width into ONE resident buffer (the files must share their dimension), the clusters come from

@@ -3066,14 +3066,25 @@ void normaliseColumns(GpuServer &srv, std::vector<double> &X, unsigned long &dim
 }
 } // namespace
 
-std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> enrol,
-                           const std::vector<unsigned long> &enrolPerModel, std::vector<double> test, unsigned long nTest,
-                           const std::vector<double> &pldaF, const std::vector<double> &pldaG, const std::vector<double> &pldaSigma)
+namespace {
+// steps 1-4 of IvTest, shared by ivTest and ivTestTrials: what the scoring rule of step 5 reads
+struct IvTestPrepared {
+    unsigned long dim = 0, nModels = 0;
+    std::vector<double> models, test;       // [dim x nModels], [dim x nTest]
+    std::vector<int64_t> nsess;
+    std::vector<double> mah, W, B, FTJF;
+};
+void ivTestPrepare(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> &enrol, const std::vector<unsigned long> &enrolPerModel,
+                   std::vector<double> &test, unsigned long nTest, const std::vector<double> &pldaF, const std::vector<double> &pldaG,
+                   const std::vector<double> &pldaSigma, IvTestPrepared &out)
 {
     unsigned long dimE = dev.getVectSize(), dimT = dev.getVectSize(), nEnrol = 0;
     for (unsigned long v : enrolPerModel) nEnrol += v;
     const unsigned long nModels = enrolPerModel.size();
     if (enrol.size() != dimE * nEnrol || test.size() != dimT * nTest) throw Exception("ivTest: enrol / test must be vectSize x count");
+    if (cfg.pldaScoring != "native" && cfg.pldaScoring != "enrollMean") throw Exception("pldaScoring must be: native OR enrollMean");
+    // pldaMeanScoring (PldaTools.cpp:4612-4709): the MEAN of a model's vectors scored as one session
+    const bool sumModels = cfg.scoring == "plda" && cfg.pldaScoring == "native";
     // 1. normalisation parameters on the development set (IvTest.cpp:131-160, 262-290)
     std::vector<std::vector<double> > mats, means;
     std::vector<double> ldaMat;
@@ -3127,14 +3138,29 @@ std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, s
     for (unsigned long m = 0; m < nModels; ++m) {
         const unsigned long ns = enrolPerModel[m];
         if (ns == 0) throw Exception("ivTest: a model without enrolment vector");
-        nsess[m] = (int64_t)ns;
+        nsess[m] = sumModels ? (int64_t)ns : 1;
         for (unsigned long d = 0; d < dimE; ++d) {
             double a = 0.0;
             for (unsigned long e = 0; e < ns; ++e) a += enrol[d * nEnrol + s0 + e];
-            models[d * nModels + m] = cfg.scoring == "plda" ? a : a / (double)ns;
+            models[d * nModels + m] = sumModels ? a : a / (double)ns;
         }
         s0 += ns;
     }
+    out.dim = dimE; out.nModels = nModels;
+    out.models.swap(models); out.test.swap(test); out.nsess.swap(nsess);
+    out.mah.swap(mah); out.W.swap(W); out.B.swap(B); out.FTJF.swap(FTJF);
+}
+} // namespace
+
+std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> enrol,
+                           const std::vector<unsigned long> &enrolPerModel, std::vector<double> test_in, unsigned long nTest,
+                           const std::vector<double> &pldaF, const std::vector<double> &pldaG, const std::vector<double> &pldaSigma)
+{
+    IvTestPrepared pr;
+    ivTestPrepare(srv, cfg, dev, enrol, enrolPerModel, test_in, nTest, pldaF, pldaG, pldaSigma, pr);
+    const unsigned long dimE = pr.dim, nModels = pr.nModels;
+    const std::vector<double> &models = pr.models, &test = pr.test, &mah = pr.mah, &W = pr.W, &B = pr.B, &FTJF = pr.FTJF;
+    const std::vector<int64_t> &nsess = pr.nsess;
     // 5. scoring (:330-395)
     std::vector<double> scores(nModels * nTest);
     if (cfg.scoring == "cosine")
@@ -3149,6 +3175,35 @@ std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, s
         srv.check(gmmiv_score_twocov(srv.ctx(), (int)dimE, (int64_t)nModels, (int64_t)nTest, models.data(), test.data(), Gm.data(), Hm.data(), scores.data()));
     } else
         srv.check(gmmiv_score_plda(srv.ctx(), (int)cfg.pldaRankF, (int64_t)nModels, (int64_t)nTest, models.data(), nsess.data(), test.data(), FTJF.data(), scores.data()));
+    return scores;
+}
+
+std::vector<double> ivTestTrials(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> enrol,
+                                 const std::vector<unsigned long> &enrolPerModel, std::vector<double> test, unsigned long nTest,
+                                 const std::vector<int32_t> &trialModel, const std::vector<int32_t> &trialSeg, const std::vector<double> &pldaF,
+                                 const std::vector<double> &pldaG, const std::vector<double> &pldaSigma)
+{
+    if (trialModel.size() != trialSeg.size()) throw Exception("ivTestTrials: trialModel and trialSeg must have one entry per trial");
+    IvTestPrepared pr;
+    ivTestPrepare(srv, cfg, dev, enrol, enrolPerModel, test, nTest, pldaF, pldaG, pldaSigma, pr);
+    const int dim = (int)pr.dim;
+    const int64_t M = (int64_t)pr.nModels, S = (int64_t)nTest, n = (int64_t)trialModel.size();
+    // 5. the rule on the listed trials only (cosineDistance / mahalanobisDistance test _trials(m, s), PldaTools.cpp:3871, :3889)
+    std::vector<double> scores(trialModel.size());
+    if (cfg.scoring == "cosine")
+        srv.check(gmmiv_score_cosine_trials(srv.ctx(), dim, M, S, pr.models.data(), pr.test.data(), trialModel.data(), trialSeg.data(), n, scores.data()));
+    else if (cfg.scoring == "mahalanobis")
+        srv.check(gmmiv_score_mahalanobis_trials(srv.ctx(), dim, M, S, pr.models.data(), pr.test.data(), pr.mah.data(), trialModel.data(), trialSeg.data(), n,
+                                                 scores.data()));
+    else if (cfg.scoring == "2cov") {
+        const size_t dd = pr.dim * pr.dim;
+        std::vector<double> Gm(dd), Hm(dd);
+        twoCovModel(srv, pr.dim, pr.W, pr.B, Gm, Hm);
+        srv.check(gmmiv_score_twocov_trials(srv.ctx(), dim, M, S, pr.models.data(), pr.test.data(), Gm.data(), Hm.data(), trialModel.data(), trialSeg.data(), n,
+                                            scores.data()));
+    } else
+        srv.check(gmmiv_score_plda_trials(srv.ctx(), (int)cfg.pldaRankF, M, S, pr.models.data(), pr.nsess.data(), pr.test.data(), pr.FTJF.data(),
+                                          trialModel.data(), trialSeg.data(), n, scores.data()));
     return scores;
 }
 

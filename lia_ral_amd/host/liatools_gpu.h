@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/gmmiv.h"
+#include "../../include/gmmiv_iv_trials.h"
 
 namespace liagpu {
 
@@ -805,6 +806,9 @@ struct IvTestCfg {
     bool WCCN = false;                    // wccn (cosine scoring only)
     std::string scoring = "cosine";       // cosine | mahalanobis | 2cov | plda
     unsigned long pldaRankF = 0, pldaRankG = 0, pldaNbIt = 0; // pldaEigenVoiceNumber / pldaEigenChannelNumber / pldaNbIt
+    // pldaScoring (IvTest.cpp:397-406): "native" scores the SUM of a model's vectors with its session count (pldaNativeScoring),
+    // "enrollMean" their MEAN as one session (pldaMeanScoring, PldaTools.cpp:4612-4709).  Anything else is an Exception.
+    std::string pldaScoring = "native";
 };
 // dev: development set (modified: normalised in place like the reference's PldaDev).
 // enrol [dim x nEnrol] one enrolment vector per column, enrolPerModel[m] consecutive columns per model (cosine,
@@ -814,6 +818,14 @@ struct IvTestCfg {
 std::vector<double> ivTest(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> enrol,
                            const std::vector<unsigned long> &enrolPerModel, std::vector<double> test, unsigned long nTest,
                            const std::vector<double> &pldaF, const std::vector<double> &pldaG, const std::vector<double> &pldaSigma);
+// The same on a LIST of trials: trial i is model trialModel[i] against test vector trialSeg[i], in any order (include/gmmiv_iv_trials.h).
+// Steps 1-4 (normalisation, back-end matrices, projection, one vector per model) are those of ivTest; only the listed pairs are
+// scored, as cosineDistance / mahalanobisDistance do under _trials (PldaTools.cpp:3871, :3889).  Returns one score per trial, in list
+// order: the cell [trialModel[i]][trialSeg[i]] of ivTest's matrix to the last bits of another summation order.
+std::vector<double> ivTestTrials(GpuServer &srv, const IvTestCfg &cfg, PldaDev &dev, std::vector<double> enrol,
+                                 const std::vector<unsigned long> &enrolPerModel, std::vector<double> test, unsigned long nTest,
+                                 const std::vector<int32_t> &trialModel, const std::vector<int32_t> &trialSeg, const std::vector<double> &pldaF,
+                                 const std::vector<double> &pldaG, const std::vector<double> &pldaSigma);
 
 // ---- ComputeNorm (LIA_SpkDet/ComputeNorm/src/ComputeNorm.cpp:491-760) on resident score matrices ------------------------------
 // The reference reads NIST result lines and keeps one DistribNorm per name; here the same four chains run on dense matrices

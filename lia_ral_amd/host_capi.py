@@ -398,23 +398,96 @@ def plda_train(X, sps, F, G, Sigma, nb_it, device=0):
     return dict(X=X, F=F, G=G, Sigma=Sigma, Delta=Delta, original_mean=om)
 
 
-def iv_test(dev, sps, enrol, enrol_per_model, test, scoring="cosine", iv_norm=False, iv_norm_it=1, sph_norm=False, lda_rank=0,
-            wccn=False, plda=None, plda_it=0, device=0):
-    """IvTest end to end.  plda = (F, G, Sigma) initial matrices in the normalised space.  -> scores [nModels, nTest]."""
-    dev = np.ascontiguousarray(dev, np.float64); enrol = np.ascontiguousarray(enrol, np.float64); test = np.ascontiguousarray(test, np.float64)
-    dim, n_dev = dev.shape
-    sps = np.ascontiguousarray(sps, np.int64); epm = np.ascontiguousarray(enrol_per_model, np.int64)
-    code = {"cosine": 0, "mahalanobis": 1, "2cov": 2, "plda": 3}[scoring]
+_SCORING = {"cosine": 0, "mahalanobis": 1, "2cov": 2, "plda": 3}
+_PLDA_SCORING = {"native": 0, "enrollMean": 1}
+
+
+def _iv_test_cfg(scoring, iv_norm, iv_norm_it, sph_norm, lda_rank, wccn, plda, plda_it, plda_scoring):
+    """-> (the configuration arguments shared by the IvTest exports, the arrays they point to)"""
+    if plda_scoring not in _PLDA_SCORING:
+        raise HostError("pldaScoring must be: native OR enrollMean")
     if plda is not None:
         F, G, S = [np.ascontiguousarray(a, np.float64) for a in plda]
         rf, rg = F.shape[1], G.shape[1]
     else:
         F = G = S = np.zeros(1); rf = rg = 0
-    out = np.empty((len(epm), test.shape[1]))
-    _chk(lib.liagpu_iv_test(device, dim, ct.c_long(n_dev), _d(dev), ct.c_long(len(sps)), sps.ctypes.data_as(_lp), ct.c_long(len(epm)),
-                            epm.ctypes.data_as(_lp), _d(enrol), ct.c_long(test.shape[1]), _d(test), int(iv_norm), int(iv_norm_it), int(sph_norm),
-                            int(lda_rank > 0), int(lda_rank), int(wccn), code, rf, rg, int(plda_it), _d(F), _d(G), _d(S), _d(out)))
+    args = (int(iv_norm), int(iv_norm_it), int(sph_norm), int(lda_rank > 0), int(lda_rank), int(wccn), _SCORING[scoring], rf, rg, int(plda_it),
+            _d(F), _d(G), _d(S), _PLDA_SCORING[plda_scoring])
+    return args, (F, G, S)
+
+
+def iv_test(dev, sps, enrol, enrol_per_model, test, scoring="cosine", iv_norm=False, iv_norm_it=1, sph_norm=False, lda_rank=0,
+            wccn=False, plda=None, plda_it=0, device=0, plda_scoring="native"):
+    """IvTest end to end.  plda = (F, G, Sigma) initial matrices in the normalised space; plda_scoring "native" (the sum of a model's
+    vectors with its session count) or "enrollMean" (their mean as one session).  -> scores [nModels, nTest]."""
+    return iv_test_trials(dev, sps, enrol, enrol_per_model, test, None, None, scoring, iv_norm, iv_norm_it, sph_norm, lda_rank, wccn, plda, plda_it,
+                          device, plda_scoring)
+
+
+def iv_test_trials(dev, sps, enrol, enrol_per_model, test, trial_model, trial_seg, scoring="cosine", iv_norm=False, iv_norm_it=1, sph_norm=False,
+                   lda_rank=0, wccn=False, plda=None, plda_it=0, device=0, plda_scoring="native"):
+    """IvTest on a list of trials (liagpu::ivTestTrials): trial i is model trial_model[i] against test vector trial_seg[i].
+    -> scores [ntrial] in list order.  trial_model = None: the dense matrix [nModels, nTest] (liagpu::ivTest)."""
+    dev = np.ascontiguousarray(dev, np.float64); enrol = np.ascontiguousarray(enrol, np.float64); test = np.ascontiguousarray(test, np.float64)
+    dim, n_dev = dev.shape
+    sps = np.ascontiguousarray(sps, np.int64); epm = np.ascontiguousarray(enrol_per_model, np.int64)
+    cfg, keep = _iv_test_cfg(scoring, iv_norm, iv_norm_it, sph_norm, lda_rank, wccn, plda, plda_it, plda_scoring)
+    head = (device, dim, ct.c_long(n_dev), _d(dev), ct.c_long(len(sps)), sps.ctypes.data_as(_lp), ct.c_long(len(epm)), epm.ctypes.data_as(_lp),
+            _d(enrol), ct.c_long(test.shape[1]), _d(test))
+    if trial_model is None:
+        out = np.empty((len(epm), test.shape[1]))
+        if plda_scoring == "native":
+            _chk(lib.liagpu_iv_test(*head, *cfg[:-1], _d(out)))
+        else:
+            _chk(lib.liagpu_iv_test_trials(*head, *cfg, ct.c_long(0), None, None, _d(out)))
+        return out
+    tm = np.ascontiguousarray(trial_model, np.int32); ts = np.ascontiguousarray(trial_seg, np.int32)
+    assert tm.shape == ts.shape and tm.ndim == 1
+    out = np.empty(len(tm))
+    _chk(lib.liagpu_iv_test_trials(*head, *cfg, ct.c_long(len(tm)), ct.c_void_p(tm.ctypes.data), ct.c_void_p(ts.ctypes.data), _d(out)))
     return out
+
+
+def load_iv_test_ndx(ndx_path, target_id_list=None):
+    """liagpu::loadIvTestNdx (host only, needs no GPU) -> dict(models, sessions, segs, trial_model, trial_seg, dropped, max_sessions)"""
+    dims = (ct.c_long * 6)()
+    tl = None if not target_id_list else str(target_id_list).encode()
+    _chk(lib.liagpu_iv_test_ndx_load(str(ndx_path).encode(), tl, dims, None, ct.c_long(0)))
+    cap = os.path.getsize(ndx_path) + (os.path.getsize(target_id_list) if target_id_list else 0) + 32 * (dims[0] + dims[1] + dims[2]) + 64
+    buf = ct.create_string_buffer(cap)
+    _chk(lib.liagpu_iv_test_ndx_load(str(ndx_path).encode(), tl, dims, buf, ct.c_long(cap)))
+    models, sessions, segs, tm, ts = [], [], [], [], []
+    for line in buf.value.decode().splitlines():
+        f = line.split()
+        if f[0] == "M":
+            models.append(f[1]); sessions.append(f[2:])
+        elif f[0] == "S":
+            segs.append(f[1])
+        else:
+            tm.append(int(f[1])); ts.append(int(f[2]))
+    return dict(models=models, sessions=sessions, segs=segs, trial_model=np.array(tm, np.int32), trial_seg=np.array(ts, np.int32),
+                dropped=int(dims[3]), max_sessions=int(dims[5]))
+
+
+def iv_test_ndx(dev, sps, ndx_path, vector_path, out_path, target_id_list=None, vector_ext=".y", fmt="DB", gender="M", threshold=0.0,
+                scoring="cosine", iv_norm=False, iv_norm_it=1, sph_norm=False, lda_rank=0, wccn=False, plda=None, plda_it=0, device=0,
+                plda_scoring="native"):
+    """IvTest from files on an ndx (liagpu::ivTestFiles): writes the result lines to out_path (segment-major, model index ascending).
+    -> dict(line_model, line_seg, scores) of the lines, in file order."""
+    dev = np.ascontiguousarray(dev, np.float64)
+    dim, n_dev = dev.shape
+    sps = np.ascontiguousarray(sps, np.int64)
+    cfg, keep = _iv_test_cfg(scoring, iv_norm, iv_norm_it, sph_norm, lda_rank, wccn, plda, plda_it, plda_scoring)
+    nx = load_iv_test_ndx(ndx_path, target_id_list)
+    n = len(nx["trial_model"])
+    lm = np.zeros(max(n, 1), np.int32); ls = np.zeros(max(n, 1), np.int32); sc = np.zeros(max(n, 1)); cnt = ct.c_long(0)
+    tl = None if not target_id_list else str(target_id_list).encode()
+    _chk(lib.liagpu_iv_test_ndx(device, dim, ct.c_long(n_dev), _d(dev), ct.c_long(len(sps)), sps.ctypes.data_as(_lp), str(ndx_path).encode(), tl,
+                                str(vector_path).encode(), vector_ext.encode(), fmt.encode(), str(out_path).encode(), gender.encode(),
+                                ct.c_double(threshold), *cfg, ct.c_long(n), ct.c_void_p(lm.ctypes.data), ct.c_void_p(ls.ctypes.data), _d(sc),
+                                ct.byref(cnt)))
+    k = cnt.value
+    return dict(line_model=lm[:k], line_seg=ls[:k], scores=sc[:k], ndx=nx)
 
 
 def tv_train(N, F, ubm, Tmat, nb_it, min_div=True, device=0):
