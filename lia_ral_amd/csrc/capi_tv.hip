@@ -179,7 +179,7 @@ static int tv_estep(gmmiv_ctx *c, int64_t U, int C, int D, int R, const double *
             double *Lp = Lp0 + (size_t)(u0 - s0) * P;
             if ((rc = ws.begin(nb))) return rc;
             // L (packed) = N * TETt ; + I when it is read
-            c->t_begin("k_dgemm(L)");
+            c->t_begin("k_dgemm(L)", u0 == 0); // one event pair per batch of the call, not the last batch alone
             GCHK(tvk_dgemm(c->stream, false, false, nb, (int)P, C, 1.0, Nc, C, 0, i_te.d, (long)P, 0, 0.0, Lp, (long)P, 0, 1));
             c->t_end();
             if ((rc = ws.from_packed(Lp, (long)P, 1.0))) return rc;

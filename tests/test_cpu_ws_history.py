@@ -1,7 +1,8 @@
 """What tests/test_gpu_ws_history.py relies on, checked without a GPU: the large cases dominate the judged ones in every quantity
-that sizes a workspace and do not align with them; the degenerate frames are where the table says; and the programme reaches
-every function of include/gmmiv.h that takes a context, model or batch handle -- or names it in EXEMPT with a reason -- so a new
-ABI function with neither fails here."""
+that sizes a workspace -- those of the i-vector back end included -- and do not align with them; every judged back-end shape is a row
+of its reference module's own table; the degenerate frames are where the table says; and the programme reaches every function of
+include/gmmiv.h and include/gmmiv_iv_trials.h that takes a context, model or batch handle -- or names it in EXEMPT with a reason --
+so a new ABI function with neither fails here."""
 import ast
 import inspect
 import os
@@ -9,6 +10,9 @@ import re
 
 import numpy as np
 
+import backend_ref as br
+import estimation_ref as es
+import tv_ref as tr
 import ws_history as wh
 from conftest import ROOT
 
@@ -40,6 +44,100 @@ def test_every_judged_case_is_dominated_by_a_large_case_that_does_not_align_with
     assert max(c["online_rows"] * c["gcase"][1] for c in wh.LARGE) >= max((wh.TORCH_SMALL_BLOCK // (4 * c["gcase"][1]) + 2048) * c["gcase"][1] for c in wh.SMALL)
     assert {c["gcase"][:3] for c in wh.SMALL} == {(37, 13, 65), (129, 60, 257), (40, 97, 66)}
     assert 70 in wh.CASES["s129x60x257"]["ctops"] and {10, 17} <= set(wh.SMALL[0]["ctops"])
+
+
+def test_the_dirtying_back_end_shapes_dominate_the_judged_ones_and_do_not_align_with_them():
+    """every large case on its own, in every quantity of iv_sizes -- a judged slot request that a dirtying one does not cover would be
+    handed out fresh (and cleared) in the small pass; and no dirtying set is the judged one scaled: of the quantities that give a
+    buffer its row length, none is a multiple of the judged value in at least one dirtying case"""
+    strides = ("tv_CD", "tv_R", "tv_P", "tv_U", "score_dim", "score_M", "score_S", "ivn_in", "ivn_n", "dev_dim", "dev_sessions", "plda_dim", "eig",
+               "ortho_SV", "jfa_CD", "jfa_sessions", "em_sessions", "gemm_N")
+    aligned = {}
+    for large in wh.LARGE:
+        l = wh.iv_sizes(large)
+        assert set(strides) <= set(l)
+        for small in wh.SMALL:
+            s = wh.iv_sizes(small)
+            assert set(s) == set(l)
+            short = {k: (s[k], l[k]) for k in s if l[k] < s[k]}
+            assert not short, "%s does not dominate %s: %s" % (large["name"], small["name"], short)
+            aligned.setdefault(small["name"], []).append([k for k in strides if l[k] % s[k] == 0])
+        # finite: the large pass stays a comparison of complete results; NaN enters through nan_calls alone
+        for _, key, p in wh.chains(large):
+            assert all(np.isfinite(v).all() for v in p.values() if isinstance(v, np.ndarray)), key
+        assert np.isfinite(wh.dev_data(large)[0]).all() and all(np.isfinite(a).all() for a in wh.em_state(large, 0))
+        assert all(np.isfinite(v).all() for v in wh.jfa_data(large).values() if isinstance(v, np.ndarray))
+        M, S = large["iv"]["score"][1:]
+        assert M % 2 and S % 2 and min(M, S) > 257 and l["dev_speakers"] > 257 and l["dev_longest"] > 600
+    # some dirtying case aligns with the judged one in none of these -- but for the smallest judged set, whose 1, 2 and 3 (jfa C D = 3,
+    # n = 7 vectors) divide too much to be avoided: two there
+    assert [min(len(a) for a in aligned[c["name"]]) for c in wh.SMALL] == [2, 0, 0], aligned
+    # one even and one odd rank, the first a row of tv_ref.ESTEP_CASES; the NaN calls run at the odd one and at dirtying sizes
+    assert [c["iv"]["tv"][0][2] % 2 for c in wh.LARGE] == [0, 1]
+    assert wh.LARGE[0]["iv"]["tv"][0] in {c[:3] + (u,) for c in tr.ESTEP_CASES for u in c[3]}
+    assert wh.NAN_TV == wh.LARGE[1]["iv"]["tv"][0] and wh.NAN_TV[2] % 2 and wh.NAN_DEV == wh.LARGE[1]["iv"]["dev"] and wh.NAN_DEV[0] % 2
+    assert wh.NAN_IVN == wh.LARGE[1]["iv"]["ivn"] and wh.NAN_SCORE == wh.LARGE[1]["iv"]["score"] and wh.NAN_EM == wh.LARGE[1]["iv"]["em"][0]
+    j = wh.jfa_data(wh.LARGE[1])
+    assert wh.NAN_JFA == (j["C"], j["D"], j["R"], j["nspk"], j["nsess"]) and all(n % 2 for n in wh.NAN_SCORE + wh.NAN_IVN)
+
+
+def test_every_judged_back_end_shape_is_a_row_of_its_reference_table():
+    estep = {c[:3] + (u,) for c in tr.ESTEP_CASES for u in c[3]}
+    scores = {(d,) + c for d in br.SCORE_DIMS for c in br.SCORE_COUNTS}
+    want = dict(tv=[((5, 3, 2, 7),), ((8, 12, 35, 20),), ((16, 12, 40, 75), (6, 4, 70, 65))], dev=["3x[1,2,1]", "33x257", "8x[600,1,2]"],
+                plda=[(5, 2, 1), (33, 7, 3), (34, 5, 5)], score=[(5, 3, 7), (33, 33, 31), (130, 131, 129)], ivn=[(5, 3, 7), (60, 40, 33), (33, 33, 130)],
+                jfa=[(3, 1, 1), (6, 5, 3), (5, 13, 7)], eig=[2, 33, 65])
+    for k, rows in want.items():
+        assert [c["iv"][k] for c in wh.SMALL] == rows, k
+    for case in wh.SMALL:
+        iv = case["iv"]
+        assert set(iv["tv"]) <= estep and iv["dev"] in br.DEV_CASES and iv["dev"] in es.DEV_SETS and iv["plda"] in es.PRECOMPUTE_CASES
+        assert iv["score"] in scores and iv["ivn"] in br.IVN_SHAPES and iv["jfa"] in br.JFA_SHAPES and iv["eig"] in es.EIGEN_ORDERS
+        assert ("spd", iv["eig"], wh.EIG_COND) in es.eigen_matrices() and ("spd", iv["eig"], wh.EIG_COND) in es.lda_matrices()
+        assert (iv["eig"], wh.EIG_COND) in es.TWOCOV_CASES and set(iv["ortho"]) <= set(es.ORTHO_CASES) and set(iv["em"]) <= set(es.EM_CASES)
+        assert all(k[:2] in es.ORTHO_SHAPES for k in iv["ortho"])
+        for name in iv["em"]:                                                               # of matching size: the PLDA shape or the development set
+            dim, rf, rg, sps = es.EM_CASES[name]
+            assert (dim, rf, rg) == iv["plda"] or name.split()[-1] == iv["dev"].split("x")[-1], name
+    assert [c["iv"]["ortho"][0][:2] for c in wh.SMALL] == [(2, 3), (33, 520), (24, 1000)]
+    # both routes of tv_orthonormalize_t, told from the 80-bit factor
+    routes = [es.ortho_route(k) for k in wh.SMALL[2]["iv"]["ortho"]]
+    assert routes == ["gram", "step"] and wh.SMALL[2]["iv"]["ortho"][1][2] in es.ORTHO_RATIOS
+    assert all([es.ortho_route(k) for k in c["iv"]["ortho"]] == ["gram", "step"] for c in wh.LARGE)
+
+
+def test_both_spd_routes_the_short_batches_and_the_pad_copies_are_in_the_judged_table():
+    """the timer names no kernel of SpdBatch, so the route is told from the order: even orders take the left-looking kernels, odd ones
+    (and every order under chol_gemm 1) unpack and take the GEMM-built factorisation (capi_tv_util.h)"""
+    ranks = [t[2] for c in wh.SMALL for t in c["iv"]["tv"]]
+    assert 35 in ranks and 70 in ranks and 70 % 32 and any(r % 2 == 0 and r < 32 for r in ranks)
+    assert {c["iv"]["eig"] % 2 for c in wh.SMALL} == {0, 1} and {c["iv"]["plda"][0] % 2 for c in wh.SMALL} == {0, 1}
+    opts = {s.name: s.opts for s in wh.PROGRAMME}
+    assert opts["tv e-step [tv_batch 16 tv_acc_mb 0]"] == {"tv_batch": 16, "tv_acc_mb": 0} and opts["tv e-step [chol_gemm 1]"] == {"chol_gemm": 1}
+    assert opts["tv tett [tv_tett_direct 0]"] == {"tv_tett_direct": 0} and opts["tv update_t [tv_mstep_solve 0]"] == {"tv_mstep_solve": 0}
+    assert opts["tv min_divergence [tv_md_device 0]"] == {"tv_md_device": 0} and opts["dgemm split-K [gemm_nt80 0]"] == {"gemm_nt80": 0}
+    # (16, 12, 40, 75) in two calls of 37 + 38 utterances under tv_batch 16: 16 + 16 + 5 and 16 + 16 + 6; (6, 4, 70, 65) crosses 64 utterances
+    assert (16, 12, 40, 75) in wh.SMALL[2]["iv"]["tv"] and 75 // 2 % wh.TV_BATCH and (75 - 75 // 2) % wh.TV_BATCH
+    assert any(t[3] > 64 > t[3] // 2 for t in wh.SMALL[2]["iv"]["tv"])
+    assert wh.estep_batches(wh.LARGE[0], wh.TV_BATCH) == [4, 5] and wh.estep_batches(wh.LARGE[0], 1024) == [1, 1]
+    # odd counts on both sides: ScoreArgs::even_stride copies both matrices; the PLDA runs of odd length are gathered with a pad
+    for c in wh.SMALL[1:]:
+        dim, M, S = c["iv"]["score"]
+        assert M % 2 and S % 2
+        runs = np.diff(np.flatnonzero(np.diff(np.r_[-1, wh.score_data(c)["nsess"], -1])))
+        assert (runs % 2).any()
+    # the split-K product: layers of 48 and a short last one; two shapes take the 128 x 80 tile unless "gemm_nt80" is 0
+    for c in wh.SMALL + wh.LARGE:
+        M, N, K, nz = c["iv"]["gemm"]
+        kc = ((K + nz - 1) // nz + 15) // 16 * 16
+        assert kc == 48 and (K + kc - 1) // kc == nz >= 3 and 0 < K % kc < kc
+    nt80 = [c["name"] for c in wh.SMALL + wh.LARGE if c["iv"]["gemm"][0] % 128 == 0 and c["iv"]["gemm"][1] % 80 == 0 and c["iv"]["gemm"][1] % 128
+            and c["iv"]["gemm"][2] % 16 == 0]
+    assert nt80 == ["s129x60x257", "L530x60x4300"]
+    # FTJF B differs from A in one element, and stays a model
+    for c in wh.SMALL:
+        A, B = wh.ftjf_pair(c)
+        assert (A != B).sum() == 1 and np.linalg.eigvalsh(B + np.eye(len(B))).min() > 0
 
 
 def test_tables_are_valid_and_have_an_empty_segment():
@@ -87,9 +185,12 @@ def test_the_planted_frames_are_where_the_table_says_and_the_large_host_frames_a
 HANDLE = re.compile(r"\bgmmiv_(ctx|gmm|gmm_batch)\s*\*")
 
 
+HEADERS = ("gmmiv.h", "gmmiv_iv_trials.h")
+
+
 def abi_functions():
-    """{name: argument text} of every function prototype of include/gmmiv.h"""
-    src = open(os.path.join(ROOT, "include", "gmmiv.h")).read()
+    """{name: argument text} of every function prototype of include/gmmiv.h and include/gmmiv_iv_trials.h"""
+    src = "\n".join(open(os.path.join(ROOT, "include", h)).read() for h in HEADERS)
     src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
     src = re.sub(r"//[^\n]*", " ", src)
     src = "\n".join(l for l in src.split("\n") if not l.lstrip().startswith("#"))
@@ -135,6 +236,8 @@ def source_of(fn, seen=None):
 def test_the_abi_is_parsed():
     f = abi_functions()
     assert len(f) > 100 and "gmmiv_llk" in f and "gmmiv_ctx_stream" in f and "gmmiv_llr_trials" in f
+    assert {"gmmiv_score_cosine_trials", "gmmiv_score_mahalanobis_trials", "gmmiv_score_twocov_trials", "gmmiv_score_plda_trials"} <= set(f)
+    assert HANDLE.search(f["gmmiv_score_plda_trials"]) and HANDLE.search(f["gmmiv_iv_trial_piece"]) and not HANDLE.search(f["gmmiv_plan_iv_trial_tiles"])
     assert HANDLE.search(f["gmmiv_llk"]) and not HANDLE.search(f["gmmiv_em_acc_len"]) and not HANDLE.search(f["gmmiv_allreduce_f64"])
 
 
@@ -143,13 +246,17 @@ def test_every_abi_function_with_a_handle_is_reached_or_exempt():
     subject = {n for n, args in f.items() if HANDLE.search(args)}
     reached = {e for s in wh.PROGRAMME for e in s.reaches} | set(wh.PLUMBING) | set(wh.HANDLE_TESTS)
     unknown = (reached | set(wh.EXEMPT)) - set(f)
-    assert not unknown, "named by the programme but not in include/gmmiv.h: %s" % sorted(unknown)
+    assert not unknown, "named by the programme but in neither header: %s" % sorted(unknown)
     both = reached & set(wh.EXEMPT)
     assert not both, "reached AND exempt: %s" % sorted(both)
     missing = subject - reached - set(wh.EXEMPT)
     assert not missing, "ABI functions with a handle that no step reaches and EXEMPT does not name: %s" % sorted(missing)
     for name, reason in wh.EXEMPT.items():
         assert reason in wh.EXEMPT_REASONS, (name, reason)
+    # the i-vector back end is IN the programme: only functions without a workspace and the communicator stay outside
+    assert set(wh.EXEMPT_REASONS) == {wh._NO_WS, wh._COMM}
+    back_end = {n for n in subject if re.match(r"gmmiv_(tv|jfa|dev|score|plda|twocov|sym_eigen|iv_normalize)", n)}
+    assert len(back_end) >= 45 and back_end <= {e for s in wh.PROGRAMME for e in s.reaches}, sorted(back_end - {e for s in wh.PROGRAMME for e in s.reaches})
     # "no workspace" is checked: the body of such a function holds no scratch( and no DevIn / DevOut
     csrc = os.path.join(ROOT, "lia_ral_amd", "csrc")
     text = "".join(open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".cpp")))

@@ -3,18 +3,22 @@
 The workspaces of a context are grow-only and never cleared; a fresh hipMalloc comes back zeroed, so on a context that has done
 nothing else a read of memory the call has not written sees 0 -- and every other GPU file of this suite runs on such contexts.
 Here the programme of tests/ws_history.py (every frame-consuming entry point, the batched models, the front end, the score
-normalisation) runs on contexts with different histories and the outputs are compared BIT FOR BIT, no reference and no tolerance:
+normalisation and the i-vector back end: the T-matrix chain, the development set, PLDA, the scoring rules on matrices and on trial
+lists, JFA) runs on contexts with different histories and the outputs are compared BIT FOR BIT, no reference and no tolerance:
 
     fresh_small, fresh_small_again        the judged shapes on two fresh contexts: the precondition (they must agree)
-    fresh_large                           the dirtying shapes alone: NaN / Inf / 1e30 / far frames, chunked scratch, NaN-as-data calls
+    fresh_large                           the dirtying shapes alone: NaN / Inf / 1e30 / far frames, chunked scratch, finite back-end inputs,
+                                          then one NaN-as-data call per back-end family
     large_then_small, .._reversed         the judged shapes on every slot the large pass left dirty  == fresh_small
     small_then_large                      every slot freed and reallocated in mid-life               == fresh_large
     large_moved_then_small                the large pass with an option moved for one step each and put back == fresh_small
 
-One test per programme step and form compares every output of the step in every sequence; the non-vacuity test holds what keeps
+One test per sequence runs it (on one context, kept for the rest of the module) and holds that every step of its plan ran; one test
+per programme step and form then compares every output of the step in every sequence; the non-vacuity test holds what keeps
 them from passing emptily (no slot grew in the small pass, the large pass touched every slot the small one uses, the NaN calls
-returned NaN, the planted frames were counted, the chunked steps launched twice).  With WS_HISTORY_JSON set to a path the outcome per
-step, the seconds, the workspace tables and the launch counts are written there (profiles/r21/ws_history.json).
+returned NaN or "not positive definite" as each must, the planted frames were counted, the chunked steps launched twice, the E-step
+under tv_batch 16 ran its short batches).  With WS_HISTORY_JSON set to a path the outcome per step, the seconds, the workspace tables
+and the launch counts are written there (profiles/r23/ws_history.json).
 """
 import json
 import os
@@ -30,7 +34,10 @@ import ws_history as wh
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(300)]
 
 MOVED = {"llk": {"glds": 0}, "em_accumulate": {"wg_waves": 4}, "occ": {"short_calls": 0}, "tv_stats": {"z_waves": 4},
-         "batch llk": {"models_scratch_mb": 0}, "llr_trials per-model tables": {"trials_scratch_mb": 0}}
+         "batch llk": {"models_scratch_mb": 0}, "llr_trials per-model tables": {"trials_scratch_mb": 0},
+         # the back end: a step that does not set the option itself (the bracket of elementwise_judge.options expects the default)
+         "tv e-step": {"tv_batch": 48}, "tv m-step": {"tv_mstep_solve": 0, "tv_md_device": 0}, "tv tett": {"tv_tett_direct": 0},
+         "tv estimate_w": {"chol_gemm": 1}, "dgemm split-K": {"gemm_nt80": 0}}
 wh.SEQUENCES["large_moved_then_small"] = wh.SEQUENCES["large_then_small"]
 # sequence -> (the sequence whose results it must repeat, the cases compared)
 AGAINST = {"fresh_small_again": ("fresh_small", wh.SMALL), "large_then_small": ("fresh_small", wh.SMALL),
@@ -80,8 +87,10 @@ def record():
                    "module_seconds": round(total, 1), "sequence_seconds": {s: round(r["total"], 1) for s, r in runs.items()},
                    "steps": steps, "outputs_compared": len(COMPARED),
                    "workspace_bytes": {s: [{"after": p, "bytes": t} for p, t in r["ws"]] for s, r in runs.items()},
-                   "launches (k_llk_mfma, k_stats_z)": {s: {" | ".join(k): v for k, v in r["log"].items()} for s, r in runs.items()},
-                   "nan_calls_returned_nan": {s: r["nan_ok"] for s, r in runs.items() if r["nan_ok"] is not None}}, f, indent=1)
+                   "launches ((k_llk_mfma, k_stats_z); k_dgemm(L) after either call of an E-step)":
+                       {s: {" | ".join(k): v for k, v in r["log"].items()} for s, r in runs.items()},
+                   "nan_calls_answered_as_they_must": {s: r["nan_ok"] for s, r in runs.items() if r["nan_ok"] is not None},
+                   "nan_calls": sorted(set().union(*[r.get("nan", {}) for r in runs.values()]))}, f, indent=1)
 
 
 def compare(j, step, form, name):
@@ -100,6 +109,15 @@ def compare(j, step, form, name):
             j.same_bits(out, a[out], b[out], base_name)
             COMPARED.add((name,) + key + (out,))
     EQUAL.setdefault((step.name, form), {})[name] = len(j.bad) == before
+
+
+@pytest.mark.parametrize("name", list(wh.SEQUENCES))
+def test_sequence_runs_every_step_of_its_plan(name):
+    """one context per sequence, run here and kept for the comparisons below: no test of this module takes longer than one sequence"""
+    r = sequence(name)
+    want = [(c["name"], s.name, f) for cases, reverse in wh.SEQUENCES[name] for c, s, f in wh.plan(cases, reverse)]
+    assert want and set(r["results"]) == set(want) and [p for p, _ in r["ws"]] == ["large" if cases is wh.LARGE else "small" for cases, _ in wh.SEQUENCES[name]]
+    assert all(r["results"][k] for k in want), "a step returned nothing"
 
 
 STEP_FORMS = [(s.name, f) for s in wh.PROGRAMME for f in s.forms]
@@ -149,9 +167,32 @@ def test_the_comparisons_are_not_vacuous():
     regrown = [i for i in range(64) if s1[i] > s0[i] > 0]
     print("\n[ws_history] slots in use after the small pass: %d, freed and reallocated by the large pass: %d" % (sum(1 for v in s0 if v), len(regrown)))
     assert s0 == ws_small and regrown and all(b >= a for a, b in zip(s0, s1)), (s0, s1)
-    # the NaN-as-data calls returned NaN wherever a large pass ran
+    # the small pass of the back end allocated nothing either: its slots alone, step by step -- every back-end step of the judged cases ran
+    # in both forms after the large pass, and the table did not move (the check above), so each reused what the large pass left
+    ran = [k for k in sequence("large_then_small")["results"] if k[0] in {c["name"] for c in wh.SMALL}]
+    names = [s.name for s in wh.PROGRAMME]
+    back_end = names[names.index(wh.BACKEND_FROM):]
+    assert len(back_end) == 20 and {(c["name"], n, f) for c in wh.SMALL for n in back_end for f in wh.FORMS} <= set(ran)
+    # the NaN-as-data calls answered as they must wherever a large pass ran: NaN everywhere, or "not positive definite" and nothing else
     for name in ("fresh_large", "large_then_small", "large_then_small_reversed", "small_then_large", "large_moved_then_small"):
-        assert sequence(name)["nan_ok"] is True, name
+        r = sequence(name)
+        assert r["nan_ok"] is True and len(r["nan"]) == 27, (name, sorted(k for k, v in r["nan"].items() if not v))
+    families = ("tv_estimate_a_and_c", "tv_update_t", "tv_min_divergence", "dev_cov_mat", "dev_mahalanobis", "iv_normalize", "jfa_subtract",
+                "jfa_estimate_z_and_d", "score_cosine_trials", "score_mahalanobis_trials", "score_twocov_trials", "score_plda_trials", "plda_em_iteration",
+                "a finite call after them")
+    assert set(families) <= set(large["nan"])
+    # the short-batch E-step ran its batches: k_dgemm(L) is launched once per batch, and the timer holds the launches of the last call --
+    # 64 and 65 utterances under tv_batch 16 are 4 and 4 + a batch of one; the default E-step is one batch per call
+    timed = [c for c in wh.LARGE if c["opts"].get("timing")]
+    assert timed
+    for case in timed:
+        assert case["iv"]["tv"][-1][3] == 129
+        for form in wh.FORMS:
+            assert large["log"][(case["name"], "e-step in batches", form)] == wh.estep_batches(case, wh.TV_BATCH) == [4, 5]
+            assert large["log"][(case["name"], "e-step", form)] == [1, 1]
+            assert large["log"][(case["name"], "e-step chol_gemm", form)] == [1, 1]
+        moved = sequence("large_moved_then_small")["log"]
+        assert moved[(case["name"], "e-step", "host")] == wh.estep_batches(case, MOVED["tv e-step"]["tv_batch"]) == [2, 2]
     # the planted frames were seen and counted (llk: two calls per step)
     for case in wh.LARGE:
         k1, k2 = wh.planted(case)

@@ -1,5 +1,6 @@
-"""The programme behind tests/test_gpu_ws_history.py: every frame-consuming entry point, the batched models and the front-end /
-score calls of one context as an ordered list of named steps, run on small (judged) and large (dirtying) cases in several orders.
+"""The programme behind tests/test_gpu_ws_history.py: every frame-consuming entry point, the batched models, the front-end / score
+calls and the i-vector back end (T-matrix chain, development set, PLDA, scoring rules, JFA) of one context as an ordered list of
+named steps, run on small (judged) and large (dirtying) cases in several orders.
 Plain numpy at import: the GPU is touched only inside a step.  No reference is involved -- a step returns EVERYTHING its call
 produces and the test compares bits between contexts with different histories ("Results do not depend on a context's
 history").
@@ -8,7 +9,10 @@ step        (ctx, handles, case, form) -> {name: array}.  form "host": numpy in 
             workspaces, float64 frames); form "device": torch tensors (float32 frames).  Every step ends with the deltas of the
             three counters; an output with rows the call must not touch is the whole buffer, pre-filled with a sentinel.
 case        a row of SMALL or LARGE.  Data comes from the generators of the reference modules (gmm_ref.model / frames,
-            mllr_ref.generate, energy_ref.energy_like); only the integer tables (segments, trials, runs) are laid out here.
+            mllr_ref.generate, energy_ref.energy_like, tv_ref.statistics, backend_ref.score_case / ivn_inputs / dev_inputs / jfa_inputs,
+            estimation_ref.em_inputs / precompute_inputs / eigen_matrix / lda_inputs / twocov_inputs / ortho_inputs); only the integer
+            tables (segments, trials, runs) and the inputs of the dirtying back-end shapes -- the same recipes at sizes the reference
+            tables do not hold -- are laid out here.
 sequence    an ordered list of (case, step, form) run on ONE context: see SEQUENCES.
 """
 import functools
@@ -16,9 +20,13 @@ import time
 
 import numpy as np
 
+import backend_ref as br
 import energy_ref as er
+import estimation_ref as es
 import gmm_ref as gr
+import iv_trials_ref as ivr
 import mllr_ref
+import tv_ref as tr
 from elementwise_judge import SENTINEL, options
 from test_gpu_gmm_elementwise import chunk_plan, layouts
 
@@ -31,22 +39,54 @@ MLLR_MAX_DIM = 62                # mllr.hip: the augmented system must fit one 6
 Z_MB_530 = chunk_plan(530)[0]    # the smallest stored-likelihood scratch the library accepts at C = 530: chunks of 4096 frames
 
 # ---------------------------------------------------------------------------------------------------------------- the cases
+# The i-vector part of a case (its "iv" entry).  tv: the T-matrix chains (C, D, R, U); dev: a development set -- a name of
+# backend_ref.DEV_CASES, or (dim, speakers, sessions of the longest speaker); plda: (dim, rf, rg) of plda_precompute; score: (dim, M, S)
+# of the scoring rules, rf = dim for PLDA; ivn: (dim_in, dim_out, n); jfa: (C, D, R) on backend_ref's 11 speakers and 24 sessions, or
+# (C, D, R, sessions per speaker); eig: the order of sym_eigen / dev_efr_matrix / dev_lda / twocov_model; ortho: keys of
+# estimation_ref.ortho_inputs (the "row at 5e-5" ones take the step route); em: names of estimation_ref.EM_CASES, or (dim, rf, rg) on
+# the session counts of the case's own development set; gemm: (M, N, K, nz) of the split-K product, NT, K layers of 48 and a short last one
+# ((128, 80, 112) and (256, 240, 208) qualify for the 128 x 80 tile of "gemm_nt80": full row tiles, N = k 80, K = k 16).
+# Judged: every shape is a row of the reference modules' own tables, so each has a per-element verdict elsewhere.  Odd R = 35 takes
+# the GEMM-built SPD route, even R = 70 the left-looking kernels at an order that is no multiple of 32; (16, 12, 40, 75) under tv_batch
+# 16 is two calls of 16 + 16 + 5 and 16 + 16 + 6 utterances; (6, 4, 70, 65) crosses the 64 utterances of the narrow column sum; both scoring counts of
+# the second and third case are odd (the even-stride pad copy on either side).
+IV_SMALL = (
+    dict(tv=((5, 3, 2, 7),), dev="3x[1,2,1]", plda=(5, 2, 1), score=(5, 3, 7), ivn=(5, 3, 7), jfa=(3, 1, 1), eig=2, ortho=((2, 3, "plain"),),
+         em=("5x2x1 [1,2,1,3]",), gemm=(5, 3, 100, 3)),
+    dict(tv=((8, 12, 35, 20),), dev="33x257", plda=(33, 7, 3), score=(33, 33, 31), ivn=(60, 40, 33), jfa=(6, 5, 3), eig=33,
+         ortho=((33, 520, "plain"),), em=("33x7x3 257 speakers",), gemm=(128, 80, 112, 3)),
+    dict(tv=((16, 12, 40, 75), (6, 4, 70, 65)), dev="8x[600,1,2]", plda=(34, 5, 5), score=(130, 131, 129), ivn=(33, 33, 130), jfa=(5, 13, 7), eig=65,
+         ortho=((24, 1000, "plain"), (24, 1000, "row at 5e-5")), em=("34x5x5 [3]*40", "8x3x2 [600,1,2]"), gemm=(130, 160, 100, 3)),
+)
+# Dirtying, all finite: each dominates every judged set in every quantity of sizes().  (36, 60, 92, 129) is a row of tv_ref.ESTEP_CASES;
+# its odd companion there, (8, 12, 91, 129), has fewer Gaussians than the judged 16 and is widened to (18, 14, 91, 129).
+JFA_SESSIONS_LARGE = ((2, 0, 5, 13, 1, 3, 0, 0, 7, 1, 2, 4, 1), (1, 3, 0, 11, 2, 2, 0, 6, 1, 5, 1, 0, 3, 2, 4))
+IV_LARGE = (
+    dict(tv=((36, 60, 92, 129),), dev=(35, 259, 601), plda=(67, 9, 11), score=(133, 263, 259), ivn=(61, 43, 263), jfa=(7, 15, 9, JFA_SESSIONS_LARGE[0]),
+         eig=67, ortho=((35, 1003, "plain"), (35, 1003, "row at 5e-5")), em=((35, 9, 7),), gemm=(256, 240, 208, 5)),
+    dict(tv=((18, 14, 91, 129),), dev=(37, 261, 603), plda=(69, 11, 7), score=(131, 259, 261), ivn=(67, 41, 259), jfa=(9, 14, 8, JFA_SESSIONS_LARGE[1]),
+         eig=69, ortho=((37, 1100, "plain"), (37, 1100, "row at 5e-5")), em=((37, 8, 6),), gemm=(257, 163, 292, 7)),
+)
+TV_BATCH = 16                    # the "tv_batch" of the short-batch E-step; with "tv_acc_mb" 0 every batch is a super-batch of its own
+EIG_COND = 1e3                   # the condition number (estimation_ref.CONDS) of the eigen / LDA / two-covariance inputs
+
 # name, (C, D, T, spread), segments, models, trials, ctop of determine_top / of llr_trials, utterance layouts of tv_stats, online
 # files, energy files (frames), cohort length, list lengths, matrix (M, S), options of the whole case, planted frames
 SMALL = (
     dict(name="s37x13x65", gcase=(37, 13, 65, 2.0), nseg=5, G=3, ntrial=6, ctops=(10, 17), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[0]),
     dict(name="s129x60x257", gcase=(129, 60, 257, 2.0), nseg=5, G=3, ntrial=6, ctops=(10, 17, 70), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[1]),
     dict(name="s40x97x66", gcase=(40, 97, 66, 0.5), nseg=5, G=3, ntrial=6, ctops=(10, 17), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[2]),
 )
 LARGE = (
     dict(name="L530x60x4300", gcase=(530, 60, 4300, 2.0), nseg=40, G=7, ntrial=60, ctops=(10, 17, 70, 100), trial_ctops=(17, 64), tv="bc",
          nfiles=3, energy=(5000, 2500, 0, 6001, 700, 9000, 1300), cohort=100003, lists=(100003, 7, 2049, 64), ms=(7, 11),
-         opts={"z_scratch_mb": Z_MB_530, "timing": 1}, plant=True, online_rows=48000),
+         opts={"z_scratch_mb": Z_MB_530, "timing": 1}, plant=True, online_rows=48000, iv=IV_LARGE[0]),
     dict(name="L96x101x700", gcase=(96, 101, 700, 0.5), nseg=40, G=7, ntrial=60, ctops=(10, 17, 64), trial_ctops=(17, 64), tv="abc", nfiles=3,
-         energy=(5000, 2500, 0, 6001, 700, 9000, 1300), cohort=100003, lists=(100003, 7, 2049, 64), ms=(7, 11), opts={}, plant=True, online_rows=48000),
+         energy=(5000, 2500, 0, 6001, 700, 9000, 1300), cohort=100003, lists=(100003, 7, 2049, 64), ms=(7, 11), opts={}, plant=True, online_rows=48000,
+         iv=IV_LARGE[1]),
 )
 CASES = {c["name"]: c for c in SMALL + LARGE}
 PLANT_HEAD = {1: np.nan, 5: np.inf, 11: -np.inf, 13: 1e30}     # row -> the value put into one of its dimensions (kind 1: screened)
@@ -126,9 +166,159 @@ def _batch_models(name):
 def sizes(case):
     """every quantity that sizes a workspace (tests/test_cpu_ws_history.py: dominance)"""
     C, D, T, _ = case["gcase"]
-    return dict(C=C, D_tiles=(D + 3) // 4, T=T, nseg=case["nseg"], G=case["G"], ntrial=case["ntrial"], ctop=max(case["ctops"]),
-                trial_ctop=max(case["trial_ctops"]), nfiles=case["nfiles"], energy_files=len(case["energy"]), energy_frames=max(case["energy"]),
-                cohort=case["cohort"], list_len=max(case["lists"]), nlists=len(case["lists"]), M=case["ms"][0], S=case["ms"][1])
+    out = dict(C=C, D_tiles=(D + 3) // 4, T=T, nseg=case["nseg"], G=case["G"], ntrial=case["ntrial"], ctop=max(case["ctops"]),
+               trial_ctop=max(case["trial_ctops"]), nfiles=case["nfiles"], energy_files=len(case["energy"]), energy_frames=max(case["energy"]),
+               cohort=case["cohort"], list_len=max(case["lists"]), nlists=len(case["lists"]), M=case["ms"][0], S=case["ms"][1])
+    out.update(iv_sizes(case))
+    return out
+
+
+def iv_sizes(case):
+    """the quantities that size a workspace of the i-vector back end: the largest of each over the sets of the case"""
+    iv = case["iv"]
+    tv = iv["tv"]
+    _, sps = dev_data(case)
+    ems = [em_state(case, k) for k in range(len(iv["em"]))]
+    jfa = jfa_data(case)
+    out = dict(tv_C=max(t[0] for t in tv), tv_D=max(t[1] for t in tv), tv_CD=max(t[0] * t[1] for t in tv), tv_R=max(t[2] for t in tv),
+               tv_P=max(t[2] * (t[2] + 1) // 2 for t in tv), tv_U=max(t[3] for t in tv), tv_batches=max(-(-t[3] // TV_BATCH) for t in tv),
+               tv_UCD=max(t[3] * t[0] * t[1] for t in tv), tv_RCD=max(t[2] * t[0] * t[1] for t in tv), tv_CP=max(t[0] * t[2] * (t[2] + 1) // 2 for t in tv),
+               dev_dim=iv["dev"][0] if not isinstance(iv["dev"], str) else br.DEV_CASES[iv["dev"]][0], dev_speakers=len(sps), dev_sessions=int(sps.sum()),
+               dev_longest=int(sps.max()), plda_dim=iv["plda"][0], plda_rf=iv["plda"][1], plda_rg=iv["plda"][2], score_dim=iv["score"][0],
+               score_M=iv["score"][1], score_S=iv["score"][2], score_trials=len(trial_lists(case)[0]), ivn_in=iv["ivn"][0], ivn_out=iv["ivn"][1],
+               ivn_n=iv["ivn"][2], jfa_C=jfa["C"], jfa_D=jfa["D"], jfa_CD=jfa["C"] * jfa["D"], jfa_R=jfa["R"], jfa_speakers=jfa["nspk"],
+               jfa_sessions=jfa["nsess"], eig=iv["eig"], ortho_R=max(k[0] for k in iv["ortho"]), ortho_SV=max(k[1] for k in iv["ortho"]),
+               em_dim=max(s[0].shape[0] for s in ems), em_sessions=max(s[0].shape[1] for s in ems), em_speakers=max(len(s[1]) for s in ems),
+               em_longest=max(int(s[1].max()) for s in ems), em_rf=max(s[2].shape[1] for s in ems), em_rg=max(s[3].shape[1] for s in ems),
+               gemm_M=iv["gemm"][0], gemm_N=iv["gemm"][1], gemm_K=iv["gemm"][2], gemm_slabs=iv["gemm"][0] * iv["gemm"][1] * iv["gemm"][3])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- i-vector inputs
+def _frozen(d):
+    for v in (d.values() if isinstance(d, dict) else d):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def tv_inputs(C, D, R, U):
+    """one T-matrix chain in double: tv_ref.statistics, and on them, in plain numpy, what each link is handed -- the centred statistics
+    F0, the packed TETt, the normalised statistics and T of the approximate extractors with their Wm / Dm / Q, SPD accumulators for the
+    M-step and the sums of a minimum-divergence call (the recipe of tv_ref.md_problem on this chain's T)"""
+    s = tr.statistics(C, D, R, U)
+    N, F, means, iv, Tm = s["N"], s["F"], s["means"], s["invvar"], s["Tm"]
+    rng = np.random.default_rng(7919 * C + 101 * R + U)
+    il = np.tril_indices(R)
+    F0 = np.ascontiguousarray(F - np.repeat(N, D, axis=1) * means[None, :])
+    Tc, ivc = Tm.reshape(R, C, D), iv.reshape(C, D)
+    te = np.stack([((Tc[:, c, :] * ivc[c]) @ Tc[:, c, :].T)[il] for c in range(C)])
+    siv = np.sqrt(iv)[None, :]
+    Fn, Tn = np.ascontiguousarray(F0 * siv), np.ascontiguousarray(Tm * siv)
+    weight = rng.dirichlet(np.ones(C))
+    Q = np.ascontiguousarray(np.linalg.qr(rng.normal(size=(R, R)))[0])
+    Wm = (Tn * np.repeat(weight, D)[None, :]) @ Tn.T
+    A3 = (Tn.T @ Q).reshape(C, D, R)
+    G = rng.normal(size=(C, R, R + 3))
+    A = np.einsum("cik,cjk->cij", G, G) / (R + 3) + 0.5 * np.eye(R)[None]
+    n = 50
+    Wn = rng.normal(size=(n, R)) * np.exp(rng.normal(0.0, 1.0, R))[None, :] + 0.3
+    Rm = Wn.T @ Wn + 0.1 * n * np.eye(R)
+    return _frozen(dict(N=N, F=F, means=means, invvar=iv, Tm=Tm, F0=F0, te=np.ascontiguousarray(te), Wv=rng.normal(size=(U, R)), Fn=Fn, Tn=Tn,
+                        weight=weight, Q=Q, Wm=np.ascontiguousarray((Wm + Wm.T) / 2), Dm=np.ascontiguousarray(np.sum(A3 * A3, 1)),
+                        Ap=np.ascontiguousarray(A[:, il[0], il[1]]), Cmx=rng.normal(size=(R, C * D)), md_Rm=np.ascontiguousarray((Rm + Rm.T) / 2),
+                        md_r=Wn.sum(0), md_meanW=Wn.sum(0) / n, md_n=n))
+
+
+def chains(case):
+    return [("%dx%dx%dx%d " % k, k, tv_inputs(*k)) for k in case["iv"]["tv"]]
+
+
+@functools.lru_cache(maxsize=None)
+def _dev_large(dim, nspk, longest):
+    """the recipe of backend_ref.dev_inputs on ragged counts of 1 .. 4 sessions and one speaker of `longest`"""
+    rng = np.random.default_rng(100 * dim + nspk)
+    sps = rng.integers(1, 5, nspk).astype(np.int64)
+    sps[nspk // 3] = longest
+    cls = np.repeat(np.arange(nspk), sps)
+    X = np.ascontiguousarray((rng.normal(size=(dim, nspk)) * 1.5)[:, cls] + rng.normal(size=(dim, int(sps.sum()))))
+    return _frozen((X, sps))
+
+
+def dev_data(case):
+    """-> (X [dim, n], sessions per speaker)"""
+    d = case["iv"]["dev"]
+    return es.dev_set(d) if isinstance(d, str) else _dev_large(*d)
+
+
+@functools.lru_cache(maxsize=None)
+def _em_large(dim, rf, rg, dev):
+    """the recipe of estimation_ref.em_inputs on the session counts of a large development set"""
+    sps = _dev_large(*dev)[1]
+    rng = np.random.default_rng(1000 * dim + 10 * rf + rg)
+    k, n = len(sps), int(sps.sum())
+    cls = np.repeat(np.arange(k), sps)
+    Ft, Gt = rng.normal(size=(dim, rf)), 0.5 * rng.normal(size=(dim, rg))
+    X = Ft @ rng.normal(size=(rf, k))[:, cls] + Gt @ rng.normal(size=(rg, n)) + 0.3 * rng.normal(size=(dim, n)) + 0.2
+    F, G = rng.normal(size=(dim, rf)), 0.5 * rng.normal(size=(dim, rg))
+    return _frozen(tuple(np.ascontiguousarray(a) for a in (X, sps, F, G, np.cov(X) + 0.1 * np.eye(dim), 0.1 * rng.normal(size=dim) + 0.05)))
+
+
+def em_state(case, k):
+    """-> (X, sps, F, G, Sigma, Delta) of the k-th EM set of the case"""
+    e = case["iv"]["em"][k]
+    return es.em_inputs(e) if isinstance(e, str) else _em_large(*e, case["iv"]["dev"])
+
+
+@functools.lru_cache(maxsize=None)
+def _jfa_large(C, D, R, sessions):
+    """the recipe of backend_ref.jfa_inputs on another table of sessions per speaker"""
+    rng = np.random.default_rng(10007 * C + 101 * D + R)
+    SV = C * D
+    nses = np.asarray(sessions, np.int64)
+    nspk, nsess = len(nses), int(nses.sum())
+    sb = np.concatenate([[0], np.cumsum(nses)]).astype(np.int64)
+
+    def mag(shape):
+        return rng.uniform(1.0, 2.0, shape) * rng.choice([-1.0, 1.0], shape)
+    g = np.ones(C)
+    g[br.jfa_faint(C)], g[0] = br.JFA_FAINT, br.JFA_LOUD
+    Nh = rng.uniform(0.2, 8.0, (nsess, C)) * g[None, :]
+    Fh = (Nh[:, :, None] * rng.uniform(-1.0, 1.0, (nsess, C, D))).reshape(nsess, SV)
+    N = np.stack([Nh[sb[i]:sb[i + 1]].sum(0) for i in range(nspk)])
+    F = np.stack([Fh[sb[i]:sb[i + 1]].sum(0) for i in range(nspk)])
+    return _frozen(dict(C=C, D=D, R=R, nspk=nspk, nsess=nsess, sb=sb, owner=np.repeat(np.arange(nspk), nses).astype(np.int64), Nh=np.ascontiguousarray(Nh),
+                        Fh=np.ascontiguousarray(Fh), N=np.ascontiguousarray(N), F=np.ascontiguousarray(F), m=mag(SV), V=mag((R, SV)), Um=mag((R, SV)),
+                        Y=mag((nspk, R)), X=mag((nsess, R)), Dm=rng.uniform(1.0, 2.0, SV), Z=mag((nspk, SV)), iv=rng.uniform(0.5, 2.0, SV)))
+
+
+def jfa_data(case):
+    j = case["iv"]["jfa"]
+    return br.jfa_inputs(*j) if len(j) == 3 else _jfa_large(*j)
+
+
+def score_data(case):
+    return br.score_case(*case["iv"]["score"], "plain")
+
+
+def ftjf_pair(case):
+    """-> (A, B): the FTJF of the case and a second one of the same rf that differs from it in ONE element (A stays positive definite)"""
+    A = score_data(case)["FTJF"]
+    B = A.copy()
+    B[A.shape[0] // 2, A.shape[0] // 2] += 0.25
+    return A, B
+
+
+def trial_lists(case):
+    dim, M, S = case["iv"]["score"]
+    return ivr.trial_list("sparse", M, S)
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_operands(M, N, K, nz):
+    rng = np.random.default_rng([M, N, K])
+    return _frozen((rng.normal(size=(M, K)), rng.normal(size=(N, K)), rng.normal(size=(M, N))))
 
 
 # ---------------------------------------------------------------------------------------------------------------- plumbing
@@ -174,7 +364,8 @@ def host(a):
 class Handles:
     """the model handles of one context, made on first use and kept (a used handle is part of the history); log: what the
     non-vacuity assertions read: (launches of k_llk_mfma, of k_stats_z) after the chunked calls, in programme order -- the first
-    entry is the default path, the second the "stats_z 0" step (no k_stats_z there: its count is the earlier call's)"""
+    entry is the default path, the second the "stats_z 0" step (no k_stats_z there: its count is the earlier call's) -- and the
+    launches of k_dgemm(L) after either call of an E-step (ws_history.estep)"""
 
     def __init__(self, ctx):
         self.ctx, self.h, self.log = ctx, {}, {}
@@ -597,10 +788,237 @@ def s_score_lists(ctx, h, case, form):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- i-vector back end
+def mut(form, a):
+    """a writable copy in the form: what a call that works in place is handed (the cached inputs are read-only)"""
+    return np.array(a) if form == "host" else dev(a)
+
+
+def s_tv_centre(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        N, m = to(form, p["N"]), to(form, p["means"])
+        out[tag + "subtract_m"] = ctx.tv_subtract_m(N, mut(form, p["F"]), m, C, D)
+        out[tag + "subtract_m_to"] = ctx.tv_subtract_m_to(N, to(form, p["F"]), buf(form, p["F"].shape), m, C, D)
+        inplace = mut(form, p["F"])
+        out[tag + "subtract_m_to in place"] = ctx.tv_subtract_m_to(N, inplace, inplace, m, C, D)
+        out[tag + "norm_statistics"] = ctx.tv_norm_statistics(N, mut(form, p["F"]), m, to(form, p["invvar"]), C, D)
+        out[tag + "subtract_m_plus_tw"] = ctx.tv_subtract_m_plus_tw(N, mut(form, p["F"]), m, to(form, p["Tm"]), to(form, p["Wv"]), C, D)
+    return out
+
+
+def s_tv_tett(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        out[tag + "tett"] = ctx.tv_tett(to(form, p["Tm"]), to(form, p["invvar"]), C, D, out=buf(form, p["te"].shape))
+    return out
+
+
+def s_tv_estimate_w(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        out[tag + "W"] = ctx.tv_estimate_w(*(to(form, p[k]) for k in ("N", "F0", "Tm", "invvar", "te")), C, D, out=buf(form, (U, R)))
+    return out
+
+
+def estep(ctx, h, case, form, log):
+    """tv_estimate_a_and_c on the two halves of the utterances into ONE set of accumulators: host arrays (the library works on
+    hipMalloc'd copies of them) or device tensors.  Where the case times its kernels, the launches of k_dgemm(L) -- one per batch -- of
+    either call go to the log"""
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        N, F0, Tm, iv, te = (to(form, p[k]) for k in ("N", "F0", "Tm", "invvar", "te"))
+        acc = {k: buf(form, s, fill=0.0) for k, s in (("A", p["Ap"].shape), ("Cmx", (R, C * D)), ("Rm", (R, R)), ("r", (R,)), ("meanW", (R,)))}
+        half = U // 2
+        for k, (lo, hi) in enumerate(((0, half), (half, U))):
+            acc["W"] = buf(form, (hi - lo, R))
+            ctx.tv_estimate_a_and_c(N[lo:hi], F0[lo:hi], Tm, iv, te, C, D, acc=acc)
+            out[tag + "W of call %d" % (k + 1)] = acc["W"]
+            if k == 0:
+                out[tag + "A after call 1"] = host(acc["A"])
+            if case["opts"].get("timing"):
+                h.log.setdefault((case["name"], log, form), []).append(ctx.kernel_launches("k_dgemm(L)"))
+        out.update({tag + k: acc[k] for k in ("A", "Cmx", "Rm", "r", "meanW")})
+    return out
+
+
+def estep_batches(case, tv_batch):
+    """the batches -- one launch of k_dgemm(L) each -- of either call of the E-step on the last chain of the case"""
+    U = case["iv"]["tv"][-1][3]
+    return [-(-n // min(n, tv_batch)) for n in (U // 2, U - U // 2)]
+
+
+def s_tv_estep(ctx, h, case, form):
+    return estep(ctx, h, case, form, "e-step")
+
+
+def s_tv_estep_batches(ctx, h, case, form):
+    return estep(ctx, h, case, form, "e-step in batches")
+
+
+def s_tv_estep_chol_gemm(ctx, h, case, form):
+    return estep(ctx, h, case, form, "e-step chol_gemm")
+
+
+def s_tv_update_t(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        out[tag + "T"] = ctx.tv_update_t(to(form, p["Ap"]), to(form, p["Cmx"]), C, D, out=buf(form, (R, C * D)))
+    return out
+
+
+def s_tv_min_divergence(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        Rm, r, mean, Tm = (mut(form, p[k]) for k in ("md_Rm", "md_r", "means", "Tm"))
+        ctx.tv_min_divergence(Rm, r, to(form, p["md_meanW"]), mean, Tm, p["md_n"], C, D)
+        out.update({tag + "Rn": Rm, tag + "r / n": r, tag + "mean": mean, tag + "Ch T": Tm})
+    return out
+
+
+def s_tv_mstep(ctx, h, case, form):
+    out = s_tv_update_t(ctx, h, case, form)
+    out.update(s_tv_min_divergence(ctx, h, case, form))
+    for key in case["iv"]["ortho"]:
+        out["orthonormalize_t %dx%d %s" % key] = ctx.tv_orthonormalize_t(mut(form, es.ortho_inputs(key)))
+    return out
+
+
+def s_tv_approximate(ctx, h, case, form):
+    out = {}
+    for tag, (C, D, R, U), p in chains(case):
+        N, Fn, Tn, Q = (to(form, p[k]) for k in ("N", "Fn", "Tn", "Q"))
+        out[tag + "norm_t"] = ctx.tv_norm_t(mut(form, p["Tm"]), to(form, p["invvar"]), C, D)
+        out[tag + "weighted_cov"] = ctx.tv_weighted_cov(Tn, to(form, p["weight"]), C, D, out=buf(form, (R, R)))
+        out[tag + "approximate_tctc"] = ctx.tv_approximate_tctc(Tn, Q, C, D, out=buf(form, (C, R), fill=0.0))
+        out[tag + "approximate_tctc onto a start"] = ctx.tv_approximate_tctc(Tn, Q, C, D, out=mut(form, p["Dm"]))
+        out[tag + "W ubm_weight"] = ctx.tv_estimate_w_ubm_weight(N, Fn, Tn, to(form, p["Wm"]), C, D, out=buf(form, (U, R), fill=0.0))
+        out[tag + "W ubm_weight onto a start"] = ctx.tv_estimate_w_ubm_weight(N, Fn, Tn, to(form, p["Wm"]), C, D, out=mut(form, p["Wv"]))
+        out[tag + "W eigen"] = ctx.tv_estimate_w_eigen(N, Fn, Tn, to(form, p["Dm"]), Q, C, D, out=buf(form, (U, R), fill=0.0))
+    return out
+
+
+def s_dgemm_splitk(ctx, h, case, form):
+    """gmmiv_dgemm takes device operands only.  The two forms are two calls of the split-K product on them: "host" writes alpha A B^T over
+    a sentinel-filled C (beta = 0 must not read it), "device" accumulates -2 C onto it"""
+    M, N, K, nz = case["iv"]["gemm"]
+    A, B, C0 = gemm_operands(M, N, K, nz)
+    Cm = buf("device", (M, N)) if form == "host" else dev(C0)
+    ctx.dgemm(0, 1, 1.0 if form == "host" else -0.5, dev(A), dev(B), 0.0 if form == "host" else -2.0, Cm, nz=nz)
+    return {"C": Cm}
+
+
+def s_iv_normalize(ctx, h, case, form):
+    din, dout, n = case["iv"]["ivn"]
+    p = br.ivn_inputs(din, dout, n)
+    out = {}
+    for mean, M, ln in br.IVN_FORMS:
+        mu, Mx = (to(form, p["mean"]) if mean else None), (to(form, p["M"]) if M else None)
+        tag = "mean %d M %d length_norm %d" % (bool(mean), bool(M), ln)
+        out[tag] = ctx.iv_normalize(to(form, p["X"]), mu, Mx, ln, out=buf(form, (dout if M else din, n)))
+        if not M:
+            X = mut(form, p["X"])
+            out[tag + " in place"] = ctx.iv_normalize(X, mu, None, ln, out=X)
+    return out
+
+
+def s_dev_set(ctx, h, case, form):
+    """the results of dev_means / _cov_mat / _scatter_mat are host arrays in either form (the binding allocates them); the two calls
+    governed by an inverse run on the sets that have one (more than 2 dim sessions)"""
+    X, sps = dev_data(case)
+    dim, n = X.shape
+    Xa = to(form, X)
+    out = dict(zip(("mean", "speaker means"), ctx.dev_means(Xa, sps)))
+    out.update(zip(("Sigma", "W", "B"), ctx.dev_cov_mat(Xa, sps)))
+    out.update(zip(("SB", "SW"), ctx.dev_scatter_mat(Xa, sps)))
+    if n > 2 * dim:
+        out["wccn_chol"] = ctx.dev_wccn_chol(Xa, sps, out=buf(form, (dim, dim)))
+        out["mahalanobis"] = ctx.dev_mahalanobis(Xa, sps, out=buf(form, (dim, dim)))
+    return out
+
+
+def s_eigen(ctx, h, case, form):
+    n = case["iv"]["eig"]
+    A = to(form, es.eigen_matrix(("spd", n, EIG_COND)))
+    W, B = (to(form, a) for a in es.lda_inputs(("spd", n, EIG_COND)))
+    out = {}
+    for rank in sorted({n, max(n // 2, 1)}, reverse=True):
+        out["sym_eigen rank %d vect" % rank], out["sym_eigen rank %d val" % rank] = ctx.sym_eigen(A, rank, out=(buf(form, (n, rank)), buf(form, (rank,))))
+        out["lda rank %d mat" % rank], out["lda rank %d val" % rank] = ctx.dev_lda(W, B, rank, out=(buf(form, (rank, n)), buf(form, (rank,))))
+    out["efr_matrix"] = ctx.dev_efr_matrix(A, out=buf(form, (n, n)))
+    return out
+
+
+def s_plda(ctx, h, case, form):
+    out = {}
+    for k in range(len(case["iv"]["em"])):
+        state = em_state(case, k)
+        sps = state[1]
+        X, F, G, Sigma, Delta = (mut(form, state[i]) for i in (0, 2, 3, 4, 5))
+        for it in (1, 2):
+            ctx.plda_em_iteration(X, sps, F, G, Sigma, Delta)
+            out.update({"em set %d iteration %d %s" % (k, it, name): host(a) for name, a in zip(("X", "F", "G", "Sigma", "Delta"), (X, F, G, Sigma, Delta))})
+    dim, rf, rg = case["iv"]["plda"]
+    F, G, S = (to(form, a) for a in es.precompute_inputs((dim, rf, rg)))
+    out["FTJ"], out["FTJF"] = ctx.plda_precompute(F, G, S, out=(buf(form, (rf, dim)), buf(form, (rf, rf))))
+    n = case["iv"]["eig"]
+    W, B = (to(form, a) for a in es.twocov_inputs((n, EIG_COND)))
+    out["twocov G"], out["twocov H"] = ctx.twocov_model(W, B, out=(buf(form, (n, n)), buf(form, (n, n))))
+    return out
+
+
+def s_score_rules(ctx, h, case, form):
+    """the five rules and the trial mask; PLDA with FTJF A, with B (one element of A moved, the same session counts: a K_n kept from A
+    would be used again), then with A again"""
+    p = score_data(case)
+    M, S = p["M"], p["S"]
+    m, s, ms = to(form, p["m"]), to(form, p["s"]), to(form, p["msum"])
+    A, B = ftjf_pair(case)
+    out = {"cosine": ctx.score_cosine(m, s, out=buf(form, (M, S))),
+           "mahalanobis": ctx.score_mahalanobis(m, s, to(form, p["Mah"]), out=buf(form, (M, S))),
+           "twocov": ctx.score_twocov(m, s, to(form, p["G"]), to(form, p["H"]), out=buf(form, (M, S))),
+           "twocov_mix_part": ctx.score_twocov_mix_part(m, s, to(form, p["G"]), mut(form, p["C_in"]))}
+    for tag, Fm in (("A", A), ("B", B), ("A again", A)):
+        out["plda FTJF " + tag] = ctx.score_plda(ms, p["nsess"], s, to(form, Fm), out=buf(form, (M, S)))
+    mask = (np.random.default_rng(M + S).random((M, S)) < 0.3).astype(np.uint8)
+    out["apply_trials"] = ctx.score_apply_trials(to(form, mask), mut(form, p["C_in"]), -7.5)
+    return out
+
+
+def s_score_trials(ctx, h, case, form):
+    """the four list rules on a sparse shuffled list; PLDA with the FTJF the matrix rule used last (the context's K_n cache is shared)"""
+    p = score_data(case)
+    m, s, ms = to(form, p["m"]), to(form, p["s"]), to(form, p["msum"])
+    tm, ts = trial_lists(case)
+    A, _ = ftjf_pair(case)
+    return {"cosine": ctx.score_cosine_trials(m, s, tm, ts, out=buf(form, (len(tm),))),
+            "mahalanobis": ctx.score_mahalanobis_trials(m, s, to(form, p["Mah"]), tm, ts, out=buf(form, (len(tm),))),
+            "twocov": ctx.score_twocov_trials(m, s, to(form, p["G"]), to(form, p["H"]), tm, ts, out=buf(form, (len(tm),))),
+            "plda": ctx.score_plda_trials(ms, p["nsess"], s, to(form, A), tm, ts, out=buf(form, (len(tm),)))}
+
+
+def s_jfa(ctx, h, case, form):
+    p = jfa_data(case)
+    C, D = p["C"], p["D"]
+    out = {}
+    for f in br.JFA_SUBTRACT_FORMS:
+        N, F, kw = br.jfa_subtract_args(p, f)
+        out["subtract " + f] = ctx.jfa_subtract(to(form, N), mut(form, F), C, D, **{k: to(form, v) for k, v in kw.items()})
+    out["subtract_sessions"] = ctx.jfa_subtract_sessions(p["sb"], to(form, p["Nh"]), mut(form, p["F"]), to(form, p["Um"]), to(form, p["X"]), C, D)
+    N, F, iv = to(form, p["N"]), to(form, p["F"]), to(form, p["iv"])
+    for tau in (-1.0, 14.0):
+        out["estimate_z tau %g" % tau] = ctx.jfa_estimate_z(N, F, iv, to(form, p["Dm"]), C, D, tau=tau, out=buf(form, p["F"].shape))
+    Dm = mut(form, p["Dm"])
+    out["estimate_z_and_d Z"] = ctx.jfa_estimate_z_and_d(N, F, iv, Dm, C, D, out=buf(form, p["F"].shape))
+    out["estimate_z_and_d D"] = Dm
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- the programme
-_use = ("gmmiv_llk_determine_top", "gmmiv_llk_use_top", "gmmiv_llk_use_top_multi")
+_use =("gmmiv_llk_determine_top", "gmmiv_llk_use_top", "gmmiv_llk_use_top_multi")
 _em = ("gmmiv_em_accumulate", "gmmiv_em_get", "gmmiv_variance_control")
 _mllr_ok = lambda case: case["gcase"][1] <= MLLR_MAX_DIM
+_approx = ("gmmiv_tv_norm_t", "gmmiv_tv_weighted_cov", "gmmiv_tv_approximate_tctc", "gmmiv_tv_estimate_w_ubm_weight", "gmmiv_tv_estimate_w_eigen")
 PROGRAMME = (
     Step("llk", s_llk, ("gmmiv_llk", "gmmiv_segment_means")),
     Step("occ", s_occ, ("gmmiv_occ",)),
@@ -634,7 +1052,31 @@ PROGRAMME = (
     Step("energy_detect", s_energy, ("gmmiv_energy_train", "gmmiv_energy_select")),
     Step("score matrix", s_score_matrix, ("gmmiv_score_cohort_stats", "gmmiv_score_normalize")),
     Step("score lists", s_score_lists, ("gmmiv_score_list_stats", "gmmiv_score_normalize_list")),
+    # the i-vector back end: in every sequence -- the reversed one too -- these interleave with the GMM side on one context
+    Step("tv centre", s_tv_centre, ("gmmiv_tv_subtract_m", "gmmiv_tv_subtract_m_to", "gmmiv_tv_norm_statistics", "gmmiv_tv_subtract_m_plus_tw")),
+    Step("tv tett", s_tv_tett, ("gmmiv_tv_tett",)),
+    Step("tv estimate_w", s_tv_estimate_w, ("gmmiv_tv_estimate_w",)),
+    Step("tv e-step", s_tv_estep, ("gmmiv_tv_estimate_a_and_c",)),
+    Step("tv m-step", s_tv_mstep, ("gmmiv_tv_update_t", "gmmiv_tv_min_divergence", "gmmiv_tv_orthonormalize_t")),
+    Step("tv approximate", s_tv_approximate, _approx),
+    Step("tv e-step [tv_batch 16 tv_acc_mb 0]", s_tv_estep_batches, ("gmmiv_tv_estimate_a_and_c",), opts={"tv_batch": TV_BATCH, "tv_acc_mb": 0}),
+    Step("tv e-step [chol_gemm 1]", s_tv_estep_chol_gemm, ("gmmiv_tv_estimate_a_and_c",), opts={"chol_gemm": 1}),
+    Step("tv tett [tv_tett_direct 0]", s_tv_tett, ("gmmiv_tv_tett",), opts={"tv_tett_direct": 0}),
+    Step("tv update_t [tv_mstep_solve 0]", s_tv_update_t, ("gmmiv_tv_update_t",), opts={"tv_mstep_solve": 0}),
+    Step("tv min_divergence [tv_md_device 0]", s_tv_min_divergence, ("gmmiv_tv_min_divergence",), opts={"tv_md_device": 0}),
+    Step("dgemm split-K", s_dgemm_splitk, ("gmmiv_dgemm",)),
+    Step("dgemm split-K [gemm_nt80 0]", s_dgemm_splitk, ("gmmiv_dgemm",), opts={"gemm_nt80": 0}),
+    Step("iv_normalize", s_iv_normalize, ("gmmiv_iv_normalize",)),
+    Step("dev set", s_dev_set, ("gmmiv_dev_means", "gmmiv_dev_cov_mat", "gmmiv_dev_wccn_chol", "gmmiv_dev_mahalanobis", "gmmiv_dev_scatter_mat")),
+    Step("eigen", s_eigen, ("gmmiv_sym_eigen", "gmmiv_dev_efr_matrix", "gmmiv_dev_lda")),
+    Step("plda", s_plda, ("gmmiv_plda_em_iteration", "gmmiv_plda_precompute", "gmmiv_twocov_model")),
+    Step("score rules", s_score_rules, ("gmmiv_score_cosine", "gmmiv_score_mahalanobis", "gmmiv_score_twocov", "gmmiv_score_twocov_mix_part",
+                                        "gmmiv_score_plda", "gmmiv_score_apply_trials")),
+    Step("score trials", s_score_trials, ("gmmiv_score_cosine_trials", "gmmiv_score_mahalanobis_trials", "gmmiv_score_twocov_trials",
+                                          "gmmiv_score_plda_trials")),
+    Step("jfa", s_jfa, ("gmmiv_jfa_subtract", "gmmiv_jfa_subtract_sessions", "gmmiv_jfa_estimate_z", "gmmiv_jfa_estimate_z_and_d")),
 )
+BACKEND_FROM = "tv centre"       # the first step of the i-vector back end
 STEPS = {s.name: s for s in PROGRAMME}
 # reached by the plumbing of every sequence (Handles, Step.run, nan_calls, workspace_table), not by one step
 PLUMBING = ("gmmiv_ctx_create", "gmmiv_ctx_destroy", "gmmiv_ctx_sync", "gmmiv_ctx_set_option", "gmmiv_ctx_kernel_launches", "gmmiv_ctx_workspace_bytes",
@@ -642,24 +1084,14 @@ PLUMBING = ("gmmiv_ctx_create", "gmmiv_ctx_destroy", "gmmiv_ctx_sync", "gmmiv_ct
             "gmmiv_gmm_batch_destroy", "gmmiv_score_cosine", "gmmiv_dgemm")
 # reached by the used-handle tests of tests/test_gpu_ws_history.py: C entry point -> the binding's method those tests call
 HANDLE_TESTS = {"gmmiv_gmm_set": "set", "gmmiv_gmm_set_cov": "set_cov", "gmmiv_gmm_batch_packed": "packed"}
-_BACKEND = "history case in test_gpu_backend_elementwise / test_gpu_estimation_elementwise"
 _NO_WS = "no workspace: no `scratch(` in its body"
 _COMM = "communicator"
-_IVEC = "i-vector back end: not in this programme's families and no history case of its own yet"
-EXEMPT_REASONS = (_BACKEND, _NO_WS, _COMM, _IVEC)
+EXEMPT_REASONS = (_NO_WS, _COMM)
 EXEMPT = {
-    "gmmiv_score_mahalanobis": _BACKEND, "gmmiv_score_twocov": _BACKEND, "gmmiv_score_plda": _BACKEND, "gmmiv_score_twocov_mix_part": _BACKEND,
-    "gmmiv_plda_precompute": _BACKEND,
     "gmmiv_ctx_set_hook": _NO_WS, "gmmiv_ctx_last_kernel_ms": _NO_WS, "gmmiv_ctx_kernel_ms": _NO_WS, "gmmiv_trial_piece": _NO_WS,
-    "gmmiv_ctx_stream": _NO_WS,
+    "gmmiv_ctx_stream": _NO_WS, "gmmiv_iv_trial_piece": _NO_WS,
     "gmmiv_comm_create": _COMM,
 }
-EXEMPT.update({"gmmiv_" + n: _IVEC for n in (
-    "tv_subtract_m", "tv_subtract_m_to", "tv_tett", "tv_estimate_w", "tv_estimate_a_and_c", "tv_update_t", "tv_min_divergence", "tv_orthonormalize_t",
-    "tv_norm_statistics", "tv_subtract_m_plus_tw", "tv_norm_t", "tv_weighted_cov", "tv_approximate_tctc", "tv_estimate_w_ubm_weight",
-    "tv_estimate_w_eigen", "iv_normalize", "dev_means", "dev_cov_mat", "dev_wccn_chol", "dev_mahalanobis", "dev_scatter_mat", "sym_eigen",
-    "dev_efr_matrix", "dev_lda", "plda_em_iteration", "twocov_model", "score_apply_trials", "jfa_subtract", "jfa_subtract_sessions", "jfa_estimate_z",
-    "jfa_estimate_z_and_d")})
 
 
 # ---------------------------------------------------------------------------------------------------------------- sequences
@@ -680,17 +1112,98 @@ SEQUENCES = {
 NAN_SHAPE = (33, 45, 47)         # score_cosine on NaN vectors of (33, 45) x (33, 47), as test_gpu_backend_elementwise.py
 
 
+NAN_TV = (18, 14, 91, 129)      # the odd-rank dirtying chain: the GEMM-built SPD route, nine batches under tv_batch 16
+NAN_DEV = (37, 261, 603)
+NAN_IVN = (67, 41, 259)
+NAN_JFA = (9, 14, 8, 15, 41)     # C, D, R, speakers, sessions
+NAN_SCORE = (131, 259, 261)
+NAN_EM = (37, 8, 6)
+
+
+def nan(*shape):
+    return np.full(shape, np.nan)
+
+
+def all_nan(*arrays):
+    return all(bool(np.isnan(host(a)).all()) for a in arrays)
+
+
+def not_positive_definite(call):
+    """a call with an SPD system in it, all of its data NaN: GMMIV_ERR_NUMERIC "not positive definite" and nothing else.  A HIP error
+    (-2) is not data any more: it goes up, and the module starts nothing on the GPU after it"""
+    from lia_ral_amd import capi
+    try:
+        call()
+    except capi.GmmivError as e:
+        if "error -2" in str(e):
+            raise
+        return "gmmiv error -4" in str(e) and "not positive definite" in str(e)
+    return False
+
+
 def nan_calls(ctx):
-    """the two NaN-as-data calls that finish a large pass: the shared WS_T* slots hold NaN afterwards -> True when both returned NaN"""
+    """the NaN-as-data calls that finish a large pass, one per family of the back end at a large odd shape, host arrays in (they are
+    staged through the shared WS_T* / WS_X / WS_LSE / WS_PART / WS_TIV / WS_IVT_* slots, which hold NaN afterwards) -> {call: whether it
+    answered as it must}: NaN everywhere from a call without an SPD system, "not positive definite" from one with; the last entry is a
+    finite call the context must still serve"""
     t = _torch()
+    ok = {}
     dim, M, S = NAN_SHAPE
-    sc = ctx.score_cosine(np.full((dim, M), np.nan), np.full((dim, S), np.nan))
+    ok["score_cosine"] = all_nan(ctx.score_cosine(nan(dim, M), nan(dim, S)))
     A = t.full((130, 70), float("nan"), dtype=t.float64, device="cuda")
     B = t.full((70, 90), float("nan"), dtype=t.float64, device="cuda")
     Cm = t.zeros((130, 90), dtype=t.float64, device="cuda")
     ctx.dgemm(0, 0, 1.0, A, B, 0.0, Cm)
     t.cuda.synchronize()
-    return bool(np.isnan(sc).all()) and bool(t.isnan(Cm).all().item())
+    ok["dgemm"] = bool(t.isnan(Cm).all().item())
+    # the T-matrix chain
+    C, D, R, U = NAN_TV
+    P, SV = R * (R + 1) // 2, C * D
+    ok["tv_subtract_m"] = all_nan(ctx.tv_subtract_m(nan(U, C), nan(U, SV), nan(SV), C, D))
+    ok["tv_tett"] = all_nan(ctx.tv_tett(nan(R, SV), nan(SV), C, D))
+    with options(ctx, {"tv_batch": TV_BATCH}):
+        ok["tv_estimate_w"] = not_positive_definite(lambda: ctx.tv_estimate_w(nan(U, C), nan(U, SV), nan(R, SV), nan(SV), nan(C, P), C, D))
+        ok["tv_estimate_a_and_c"] = not_positive_definite(lambda: ctx.tv_estimate_a_and_c(nan(U, C), nan(U, SV), nan(R, SV), nan(SV), nan(C, P), C, D))
+    ok["tv_update_t"] = not_positive_definite(lambda: ctx.tv_update_t(nan(C, P), nan(R, SV), C, D))
+    ok["tv_min_divergence"] = not_positive_definite(lambda: ctx.tv_min_divergence(nan(R, R), nan(R), nan(R), nan(SV), nan(R, SV), 50, C, D))
+    ok["tv_norm_t"] = all_nan(ctx.tv_norm_t(nan(R, SV), nan(SV), C, D))
+    ok["tv_estimate_w_eigen"] = all_nan(ctx.tv_estimate_w_eigen(nan(U, C), nan(U, SV), nan(R, SV), nan(C, R), nan(R, R), C, D))
+    # the development set
+    dim, nspk, longest = NAN_DEV
+    sps = _dev_large(*NAN_DEV)[1]
+    X = nan(dim, int(sps.sum()))
+    ok["dev_means"] = all_nan(*ctx.dev_means(X, sps))
+    ok["dev_cov_mat"] = all_nan(*ctx.dev_cov_mat(X, sps))
+    ok["dev_scatter_mat"] = all_nan(*ctx.dev_scatter_mat(X, sps))
+    ok["dev_mahalanobis"] = not_positive_definite(lambda: ctx.dev_mahalanobis(X, sps))
+    ok["dev_wccn_chol"] = not_positive_definite(lambda: ctx.dev_wccn_chol(X, sps))
+    # iv_normalize, JFA
+    din, dout, n = NAN_IVN
+    ok["iv_normalize"] = all_nan(ctx.iv_normalize(nan(din, n), nan(din), nan(dout, din), True))
+    C, D, R, nspk, nsess = NAN_JFA
+    SV = C * D
+    ok["jfa_subtract"] = all_nan(ctx.jfa_subtract(nan(nspk, C), nan(nspk, SV), C, D, means=nan(SV), T=nan(R, SV), W=nan(nspk, R), Dm=nan(SV), Z=nan(nspk, SV)))
+    sb = np.concatenate([[0], np.cumsum(JFA_SESSIONS_LARGE[1])]).astype(np.int64)
+    ok["jfa_subtract_sessions"] = all_nan(ctx.jfa_subtract_sessions(sb, nan(nsess, C), nan(nspk, SV), nan(R, SV), nan(nsess, R), C, D)[np.diff(sb) > 0])
+    ok["jfa_estimate_z"] = all_nan(ctx.jfa_estimate_z(nan(nspk, C), nan(nspk, SV), nan(SV), nan(SV), C, D))
+    Dm = nan(SV)
+    ok["jfa_estimate_z_and_d"] = all_nan(ctx.jfa_estimate_z_and_d(nan(nspk, C), nan(nspk, SV), nan(SV), Dm, C, D), Dm)
+    # the four rules on a trial list: NaN vectors under finite matrices
+    dim, M, S = NAN_SCORE
+    p = br.score_case(dim, M, S, "plain")
+    tm, ts = ivr.trial_list("sparse", M, S)
+    ok["score_cosine_trials"] = all_nan(ctx.score_cosine_trials(nan(dim, M), nan(dim, S), tm, ts))
+    ok["score_mahalanobis_trials"] = all_nan(ctx.score_mahalanobis_trials(nan(dim, M), nan(dim, S), p["Mah"], tm, ts))
+    ok["score_twocov_trials"] = all_nan(ctx.score_twocov_trials(nan(dim, M), nan(dim, S), p["G"], p["H"], tm, ts))
+    ok["score_plda_trials"] = all_nan(ctx.score_plda_trials(nan(dim, M), p["nsess"], nan(dim, S), p["FTJF"], tm, ts))
+    ok["score_plda_trials NaN FTJF"] = not_positive_definite(lambda: ctx.score_plda_trials(nan(dim, M), p["nsess"], nan(dim, S), nan(dim, dim), tm, ts))
+    # PLDA EM
+    dim, rf, rg = NAN_EM
+    n = int(sps.sum())
+    ok["plda_em_iteration"] = not_positive_definite(lambda: ctx.plda_em_iteration(nan(dim, n), sps, nan(dim, rf), nan(dim, rg), nan(dim, dim), nan(dim)))
+    fin = br.score_case(5, 3, 7, "plain")
+    ok["a finite call after them"] = bool(np.isfinite(ctx.score_cosine(fin["m"], fin["s"])).all())
+    return ok
 
 
 def workspace_table(ctx):
@@ -699,7 +1212,7 @@ def workspace_table(ctx):
 
 def run_sequence(name, moved=None):
     """one context, the passes of SEQUENCES[name] -> dict(results {(case, step, form): outputs}, seconds {...}, ws [(pass, table)],
-    nan_ok, log, total).  moved: {step name: options} set for that step of the FIRST pass only and put back after it"""
+    nan {call: answered as it must}, nan_ok, log, total).  moved: {step name: options} set for that step of the FIRST pass only and put back after it"""
     from lia_ral_amd import capi
     ctx = capi.Context(0)
     h = Handles(ctx)
@@ -713,7 +1226,8 @@ def run_sequence(name, moved=None):
                     res["results"][(case["name"], step.name, form)] = step.run(ctx, h, case, form)
                 res["seconds"][(case["name"], step.name, form)] = time.perf_counter() - t0
             if cases is LARGE:
-                ok = nan_calls(ctx)
+                res["nan"] = nan_calls(ctx)
+                ok = all(res["nan"].values())
                 res["nan_ok"] = ok if res["nan_ok"] is None else (res["nan_ok"] and ok)
             res["ws"].append(("large" if cases is LARGE else "small", workspace_table(ctx)))
     finally:
