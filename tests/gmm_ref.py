@@ -241,14 +241,22 @@ def clamp(v, lo, hi, bar=None):
     return c if bar is None else (c, np.where(none, 0.0, np.asarray(bar, np.float64)))
 
 
-def use_top(client, idx, world_nontop_log, world, mask, complete=True):
+def use_top(client, idx, world_nontop_log, world, mask, complete=True, count=None):
     """USE_TOP_DISTRIBS.  COMPLETE: llk_t = log(sum_{c in idx[t]} exp(z^client_tc) + nontop^world_t) in long double, and its bar:
     the share-weighted logit errors of the terms (the client's for the selected Gaussians, the world's for the remainder, which
     also goes through a log and an exp: 4u |log nontop| more) + 4u |llk| + 4u, as B_t.  PARTIAL (complete=False): the same
     expression without the remainder term, log sum_{c in idx[t]} exp(z^client_tc) and the share-weighted rho of the selected
-    logits + 4u |llk| + 4u.  Before the clamp; a frame with a NaN feature comes back NaN (clamp() makes it lo, bar 0)."""
+    logits + 4u |llk| + 4u.  Before the clamp; a frame with a NaN feature comes back NaN (clamp() makes it lo, bar 0).
+    count [T] (a stored selection of variable length, TopGauss::get): only the first count[t] entries of idx[t] are terms of the
+    sum, what stands behind them (-1) is never read.  world = None: the remainder is a number the caller handed to the library
+    (log of a stored snsl), judged from that same double -- it carries no logit error, only the 4u |log nontop| of its log / exp."""
+    if count is not None:
+        live = np.arange(idx.shape[1])[None, :] < np.asarray(count)[:, None]
+        idx = np.where(live, idx, 0)
     zc = np.take_along_axis(client.z, idx, axis=1)
     rc = np.take_along_axis(client.rho, idx, axis=1)
+    if count is not None:
+        zc, rc = np.where(live, zc, LD(-np.inf)), np.where(live, rc, 0.0)
     if not complete:
         llk = log_sum_exp(zc)
         with np.errstate(invalid="ignore"):
@@ -258,9 +266,13 @@ def use_top(client, idx, world_nontop_log, world, mask, complete=True):
     llk = log_sum_exp(allz)
     with np.errstate(invalid="ignore"):
         share = np.exp(allz - llk[:, None]).astype(np.float64)
-    tot = np.where(mask, world.g64, 0.0).sum(1)
+    if world is None:
+        rn = 0.0
+    else:
+        tot = np.where(mask, world.g64, 0.0).sum(1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rn = np.where(tot > 0, (np.where(mask, world.g64 * world.rho, 0.0).sum(1)) / np.where(tot > 0, tot, 1.0), 0.0)
     with np.errstate(invalid="ignore", divide="ignore"):
-        rn = np.where(tot > 0, (np.where(mask, world.g64 * world.rho, 0.0).sum(1)) / np.where(tot > 0, tot, 1.0), 0.0)
         ln = np.where(np.isfinite(world_nontop_log), np.abs(world_nontop_log), LD(0)).astype(np.float64)
     bar = (share[:, :-1] * rc).sum(1) + share[:, -1] * (rn + 4 * U * ln) + 4 * U * np.abs(llk.astype(np.float64)) + 4 * U
     return llk, bar
