@@ -161,7 +161,8 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
 /* ---- DEGENERATE INPUTS: what every frame-consuming entry point does with them ------------------------------------------
  * The reference has no defined behaviour here (a NaN feature poisons every accumulator it touches; ALIZE's handling of a frame of
  * likelihood 0 is not visible from LIA_RAL -- SURVEY.md U1; the one in-tree guard, TopGauss.cpp:247, maps a NaN likelihood to
- * exp(minLLK)).  This library defines it, and tests/test_gpu_degenerate.py holds every path to it:
+ * exp(minLLK)).  This library defines it, and tests/test_gpu_degenerate.py holds every path to it -- tests/test_gpu_gmm_dead_frames.py
+ * per frame, per posterior and per accumulator element, counters included, on every shape and option path of the core entry points:
  *
  * A frame is a ZERO-LIKELIHOOD FRAME when (1) one of its feature values is NaN, infinite or larger than 1e18 in magnitude, or
  * (2) its likelihood is 0 in fp64: the LARGEST term w_c lk_c(x_t) lies below 2^-1075 = exp(-745.13) (so every term of the
@@ -172,7 +173,9 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  *   gmmiv_llk_determine_top       idx = 0 .. ctop-1 (the tie rule -- lowest index first -- on equal, zero, likelihoods), lk = 0,
  *                                 nontop_lk = 0, nontop_llk = -inf, nontop_w = 1 - sum of those weights, llk = min_llk
  *   gmmiv_topgauss_compute        as determine_top; count = cap for a mass threshold (the reference's loop runs to the end), idx as above
- *   gmmiv_llk_use_top(_multi)     llk_t = min_llk
+ *   gmmiv_llk_use_top(_multi)     llk_t = min_llk on a kind-(1) frame; a kind-(2) frame is seen through the client's logits of the selected
+ *                                 Gaussians (0 .. ctop-1) and the world's remainder (-inf) only: llk_t = the clamp of their log-sum, which
+ *                                 is min_llk wherever the client's own value lies below min_llk
  *   gmmiv_occ                     a row of zeros
  *   gmmiv_em_accumulate           the frame adds NOTHING: no occupancy, no first / second order statistics, nothing to the sum of
  *                                 log-likelihoods and nothing to the frame count (the M-step weights still sum to 1)

@@ -30,6 +30,12 @@ cases        (C, D, T, spread): the smallest shapes at which the structure of th
              15 / 20 / generic at D <= 16 / 32 / 60 / 80 / above, Gaussian tiles of 16, stages of 32, workgroup groups of 256 (EM)
              and 512 (N / F), 16-frame blocks, 64-frame tiles, 128- and 256-frame workgroups.  In every case at most 1 % of the
              pairs are judged by the floor alone (reference gamma < 2^-900).
+the rule     RuleReference: the same reference on frames that hold unusable values, with the zero-likelihood rule of include/gmmiv.h
+             applied (a dead frame: llk = lo, posteriors, bars and B exactly 0).  planted(): DEAD_CASES with dead frames of eight kinds
+             at 0, T - 1, both sides of the 16 / 64 / 128 / 256 frame boundaries and over the block 32 .. 47, and alive frames at
+             largest logit -700 next to them; planted_conditions() asserts what the cases rest on; restate_rule / judge_rule are the
+             float64 restatement with the rule and its planted defects (tests/test_cpu_gmm_dead_ref.py,
+             tests/test_gpu_gmm_dead_frames.py).
 """
 import functools
 
@@ -378,3 +384,231 @@ def ragged_bounds(T):
     a = max(1, (70 * T) // 266)
     b = a + max(1, (131 * T) // 266)
     return np.array([0, a, a, min(b, T - 2), T - 1, T], np.int64)
+
+
+# ---------------------------------------------------------------- the zero-likelihood rule (include/gmmiv.h, "DEGENERATE INPUTS")
+DEAD_LO, DEAD_HI = -1000.0, 1e9   # the clamp of the dead-frame calls: -1e9 as lo would swamp the bar of a sum of log-likelihoods, -200 would clamp the alive far frames
+DEAD_CASES = ((1, 1, 17, 2.0), (2, 1, 65, 2.0), (17, 2, 129, 2.0), (33, 16, 257, 2.0), (37, 17, 300, 2.0), (65, 33, 64, 2.0), (129, 60, 256, 2.0),
+              (300, 60, 130, 2.0), (530, 60, 70, 2.0), (40, 61, 66, 2.0), (96, 81, 70, 0.5))
+DEAD_PATH_CASES = ((129, 60, 256, 2.0), (37, 17, 300, 2.0), (300, 60, 130, 2.0))
+DEAD_CANDIDATES = (-1, 0, 16, 15, 64, 63, 128, 127, 256, 255) + tuple(range(32, 48))    # -1: T - 1; then the whole 16-frame block 32 .. 47
+FAR_CANDIDATES = (1, -2, 17, 65)                                                        # -2: T - 2
+DEAD_LOGIT, FAR_LOGIT = -800.0, -700.0
+KIND_NAMES = ("NaN in one dimension", "+Inf in one dimension", "-Inf in one dimension", "1e30 in one dimension", "-2e18 in the last dimension",
+              "every dimension 3e17", "every dimension NaN", "largest logit -800")
+KINDS_SCREENED = (0, 1, 2, 3, 4, 6)     # kind (1) of the header: an unusable value; the other two are kind (2), finite and usable
+assert all(c in CASES for c in DEAD_CASES) and all(c in DEAD_CASES for c in DEAD_PATH_CASES)
+
+
+class RuleReference(Reference):
+    """Reference on frames that may hold unusable values, with the zero-likelihood rule applied: a value that is NaN, infinite or
+    beyond UNUSABLE in magnitude is read as READ_AS; a frame that had one, or whose largest logit is not above ZERO_LLK, is dead():
+    gamma, g64, dgamma exactly 0 (bar 0: only 0 passes), B 0, llk = lo.  sums() and utt_stats() then leave the dead frames out with no
+    further code.  The two things the header counts differently: gmmiv_llk's sums count EVERY frame, the dead ones with lo
+    (llk_sum(every=True)); gmmiv_em_accumulate's llk and count, the N / F rows and seg_llk count the ALIVE frames only (llk_sum(),
+    count_bar(), alive_count())."""
+
+    def __init__(self, w, mean, iv, x, floor=PHI, lo=DEAD_LO):
+        with np.errstate(invalid="ignore"):
+            unusable = ~(np.abs(x) <= UNUSABLE)             # a NaN compares false: unusable
+        super().__init__(w, mean, iv, np.where(unusable, x.dtype.type(READ_AS), x), floor)
+        self.unusable = unusable.any(1)                     # kind (1): what "screened_frames" counts
+        self.lo = lo
+        d = self._dead = self.unusable | Reference.dead(self)
+        self.gamma[d], self.g64[d], self.dgamma[d], self.B[d], self.llk[d] = 0, 0.0, 0.0, 0.0, lo
+
+    def dead(self):
+        return self._dead
+
+    def alive_count(self, lo=0, hi=None):
+        return int((~self._dead[lo:self.T if hi is None else hi]).sum())
+
+    def llk_sum(self, lo=0, hi=None, s=1.0, every=False):
+        """s sum_t llk_t over the alive frames -- with every=True over all frames, a dead one entering with self.lo -- and its bar, the
+        one of Reference.llk_sum (B_t is 0 on a dead frame; the summation term counts every step of the range)"""
+        hi = self.T if hi is None else hi
+        l = self.llk[lo:hi] if every else np.where(self._dead[lo:hi], LD(0), self.llk[lo:hi])
+        return LD(s) * l.sum(), abs(s) * (self.B[lo:hi].sum() + (hi - lo + 8) * U * float(np.abs(l).sum()))
+
+    def count_bar(self, weights):
+        n = float(sum(weights)) * self.alive_count()
+        return n, (self.T + 8) * U * n
+
+
+def largest_logit(w, mean, iv, x):
+    """the largest logit of every frame in float64, direct form (for placing a frame: +- 1e-2 is asked of it)"""
+    x = np.asarray(x, np.float64)
+    a = np.log(w) + 0.5 * np.log(iv).sum(1) - 0.5 * mean.shape[1] * LOG_2PI
+    d = x[:, None, :] - mean[None]
+    return (a[None] - 0.5 * np.einsum("tcd,tcd,cd->tc", d, d, iv)).max(1)
+
+
+def frame_at(w, mean, iv, c0, target, seed, dtype):
+    """a frame mean[c0] + s u of `dtype` whose LARGEST logit is `target` (+- 1e-2): u a random direction scaled by the Gaussian's
+    standard deviations, s by bisection (the method of _frame_at in tests/test_gpu_degenerate.py)"""
+    u = np.random.default_rng(seed).normal(0.0, 1.0, mean.shape[1]) / np.sqrt(iv[c0])
+    at = lambda s: float(largest_logit(w, mean, iv, (mean[c0] + s * u).astype(dtype)[None])[0])
+    lo, hi = 0.0, 1e3
+    while at(hi) > target:
+        hi *= 2.0
+    assert at(lo) > target
+    for _ in range(200):
+        s = 0.5 * (lo + hi)
+        lo, hi = (s, hi) if at(s) > target else (lo, s)
+    xf = (mean[c0] + lo * u).astype(dtype)
+    assert abs(at(lo) - target) < 1e-2, (c0, target, at(lo))
+    return xf
+
+
+def _positions(T, candidates):
+    out = []
+    for p in candidates:
+        p = p + T if p < 0 else p
+        if 0 <= p < T and p not in out:
+            out.append(p)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def planted(case, dtype_str):
+    """frames(case, dtype) with dead and alive far frames planted -> dict x [T, D] (read-only), dead (positions, in planting order),
+    kind (position -> index into KIND_NAMES), far (positions of the alive far frames).
+    Dead: the first max(1, T // 3) of DEAD_CANDIDATES that lie inside the call, the i-th of kind i mod 8.  Far: up to two of
+    FAR_CANDIDATES that are free, built like kind 7 at FAR_LOGIT."""
+    C, D, T, _ = case
+    dtype = np.dtype(dtype_str).type
+    w, mean, iv = model(case)
+    x = frames(case, dtype).copy()
+    dead = _positions(T, DEAD_CANDIDATES)[:max(1, T // 3)]
+    kind = {}
+    for i, t in enumerate(dead):
+        k = kind[t] = i % 8
+        d = (7 * t) % D
+        if k < 4:
+            x[t, d] = (np.nan, np.inf, -np.inf, 1e30)[k]
+        elif k == 4:
+            x[t, D - 1] = -2e18
+        elif k == 5:
+            x[t, :] = 3e17
+        elif k == 6:
+            x[t, :] = np.nan
+        else:
+            x[t] = frame_at(w, mean, iv, t % C, DEAD_LOGIT, 1000 + t, dtype)
+    far = [t for t in _positions(T, FAR_CANDIDATES) if t not in dead][:2]
+    for t in far:
+        x[t] = frame_at(w, mean, iv, t % C, FAR_LOGIT, 2000 + t, dtype)
+    x.setflags(write=False)
+    return {"x": x, "dead": tuple(dead), "kind": kind, "far": tuple(far)}
+
+
+@functools.lru_cache(maxsize=None)
+def rule_reference(case, dtype_str, shift=0, floor=PHI):
+    """the cached RuleReference of model(case, shift) on the planted frames; never modified by its users"""
+    return RuleReference(*model(case, shift), planted(case, dtype_str)["x"], floor)
+
+
+def planted_conditions(case, dtype_str, shifts=(0,)):
+    """what the planted cases rest on, asserted from the references alone -> dict of the figures.  The planted set is dead() under the
+    world model; under EVERY model that reads the frames (shifts) no largest logit lies within 20 of ZERO_LLK and the dead set is the
+    same; at least half of the frames are ordinary; at most 1 % of the pairs of ordinary frames are judged by the floor alone; every
+    alive far frame has its largest posterior under a bar above the floor."""
+    p = planted(case, dtype_str)
+    T = case[2]
+    planted_mask = np.zeros(T, bool)
+    planted_mask[list(p["dead"])] = True
+    out = {"dead": len(p["dead"]), "far": len(p["far"]), "margin": np.inf}
+    for s in shifts:
+        r = rule_reference(case, dtype_str, s)
+        assert np.array_equal(r.dead(), planted_mask), (case, dtype_str, s, np.flatnonzero(r.dead() != planted_mask))
+        margin = float(np.abs(r.z.max(1).astype(np.float64) - ZERO_LLK).min())
+        assert margin > 20.0, (case, dtype_str, s, margin)
+        out["margin"] = min(out["margin"], margin)
+    r = rule_reference(case, dtype_str)
+    screened = sorted(t for t, k in p["kind"].items() if k in KINDS_SCREENED)
+    assert np.flatnonzero(r.unusable).tolist() == screened, (case, dtype_str)
+    ordinary = ~planted_mask
+    ordinary[list(p["far"])] = False
+    out["ordinary"] = int(ordinary.sum())
+    assert 2 * out["ordinary"] >= T, (case, out)
+    out["floor_share"] = float((r.gamma[ordinary] < FLOOR_ONLY).mean())
+    assert out["floor_share"] <= 0.01, (case, dtype_str, out)
+    zmax = r.z.max(1).astype(np.float64)
+    for t in p["far"]:
+        c = int(np.argmax(r.gamma[t]))
+        assert abs(zmax[t] - FAR_LOGIT) < 1e-2 and r.g64[t, c] > 0.5 and r.dgamma[t, c] > 2 * r.floor, (case, dtype_str, t, zmax[t], r.g64[t, c])
+    for t, k in p["kind"].items():
+        assert k != 7 or abs(zmax[t] - DEAD_LOGIT) < 1e-2, (case, dtype_str, t, zmax[t])
+    return out
+
+
+def dead_layouts(T):
+    """utterance bounds for the planted cases: (a) one frame per utterance -- every dead frame a zero row of N and F; (b)
+    ragged_bounds with one more bound at 40, inside the dead 16-frame block 32 .. 47; (c) one utterance"""
+    b = ragged_bounds(T)
+    if T > 41:
+        b = np.sort(np.append(b, 40))
+    return (("a", np.arange(T + 1, dtype=np.int64)), ("b", b.astype(np.int64)), ("c", np.array([0, T], np.int64)))
+
+
+RULE_DEFECTS = ("uniform posterior on a dead frame", "lo of a dead frame in the EM llk sum", "dead frame in the EM frame count",
+                "unusable value read as 0, frame kept alive", "-700 frame dropped as dead", "-800 frame kept alive",
+                "dead frame keeps the reference's top list")
+
+
+def restate_rule(w, mean, iv, x, ctop, lo=DEAD_LO, defect=None):
+    """restate() with the rule applied as the kernels apply it, float64: unusable values read as READ_AS, a frame dead where its
+    largest logit is not above ZERO_LLK (a frame read at 1e10 is one by its logits), dead rows of zero posteriors, llk = lo,
+    idx = 0 .. ctop - 1.  -> dict llk, gamma, occ, sx, sxx, z, dead, em_llk, em_count (alive frames), llk_every (all frames), idx.
+    defect: one of RULE_DEFECTS (tests/test_cpu_gmm_dead_ref.py)."""
+    assert defect is None or defect in RULE_DEFECTS
+    x = x.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        x = np.where(np.abs(x) <= UNUSABLE, x, 0.0 if defect == RULE_DEFECTS[3] else READ_AS)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        r = restate(w, mean, iv, x)
+    zmax = r["z"].max(1)
+    cut = {RULE_DEFECTS[4]: -650.0, RULE_DEFECTS[5]: -850.0}.get(defect, ZERO_LLK)
+    dead = ~(zmax > cut)
+    C = r["z"].shape[1]
+    gamma = np.where(dead[:, None], 1.0 / C if defect == RULE_DEFECTS[0] else 0.0, r["gamma"])
+    llk = np.where(dead, lo, r["llk"])
+    order = np.argsort(-r["z"], axis=1, kind="stable")[:, :ctop]
+    idx = order if defect == RULE_DEFECTS[6] else np.where(dead[:, None], np.arange(ctop)[None, :], order)
+    return {"llk": llk, "gamma": gamma, "occ": gamma.sum(0), "sx": gamma.T @ x, "sxx": gamma.T @ (x * x), "z": r["z"], "dead": dead, "idx": idx,
+            "em_llk": (llk if defect == RULE_DEFECTS[1] else llk[~dead]).sum(), "em_count": float(len(llk) if defect == RULE_DEFECTS[2] else (~dead).sum()),
+            "llk_every": llk.sum()}
+
+
+def judge_rule(ref, got):
+    """the largest ratio to its bar of everything the dead-frame module judges on the single-model entry points, for a restatement
+    `got` (restate_rule): dict name -> float.  "idx dead" is 0 or inf: a dead frame selects 0 .. ctop - 1."""
+    out = judge(ref, got)
+    s, sb = ref.llk_sum()
+    out["em llk"] = float(ratio(np.array([got["em_llk"]]).astype(LD) - s, sb).max())
+    n, nb = ref.count_bar((1.0,))
+    out["em count"] = float(ratio(np.array([got["em_count"] - n]), nb).max())
+    s, sb = ref.llk_sum(every=True)
+    out["llk sums"] = float(ratio(np.array([got["llk_every"]]).astype(LD) - s, sb).max())
+    d = ref.dead()
+    ctop = got["idx"].shape[1]
+    out["idx dead"] = 0.0 if np.array_equal(got["idx"][d], np.broadcast_to(np.arange(ctop), (int(d.sum()), ctop))) else np.inf
+    short, slack = ref.selection_shortfall(np.where(d[:, None], ref.top(ctop), got["idx"]))
+    out["idx alive"] = float(ratio(np.where(d[:, None], 0.0, short), slack).max())
+    x = ref.x
+    for name, ub in dead_layouts(ref.T):
+        N, F, Nb, Fb = ref.utt_stats(ub)
+        seg = np.add.reduceat(got["gamma"], ub[:-1][np.diff(ub) > 0], axis=0)
+        out["tv(%s) N" % name] = float(ratio(seg.astype(LD) - N[np.diff(ub) > 0], Nb[np.diff(ub) > 0]).max())
+        if name != "a":
+            Fg = np.stack([got["gamma"][ub[u]:ub[u + 1]].T @ x[ub[u]:ub[u + 1]] for u in range(len(ub) - 1)])
+            out["tv(%s) F" % name] = float(ratio(Fg.astype(LD) - F, Fb).max())
+    return out
+
+
+def clamp_below(v, bar, lo, hi):
+    """clamp() with bars, and: a value that lies below lo by more than its bar is lo whatever the admitted error, so its bar is 0
+    (a frame read at 1e10 has a log-sum near -1e19 with a bar of thousands; its clamped value is exactly lo)"""
+    c, b = clamp(v, lo, hi, bar)
+    with np.errstate(invalid="ignore"):
+        sure = np.asarray(v, LD) + b < LD(lo)
+    return c, np.where(sure, 0.0, b)
