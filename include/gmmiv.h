@@ -53,6 +53,15 @@ int gmmiv_ctx_sync(gmmiv_ctx *ctx);
 /* The hipStream_t every call of this context is enqueued on (the one given to gmmiv_ctx_create, or the private one): a host
  * layer that keeps its own device buffers orders its copies / memsets on it instead of synchronising around every call. */
 void *gmmiv_ctx_stream(gmmiv_ctx *ctx);
+/* STREAM ORDER.  A device array handed to a call is read and written in the order of the context's stream: the call behaves like a
+ * kernel launched on that stream.  The library never reads such an array from another stream, and never on the host before the
+ * stream has reached the call -- so an input need not be complete when the call is MADE, only when the stream gets to it: the
+ * output of gmmiv_plda_precompute, of gmmiv_dgemm or of the caller's own kernel on this stream can go straight into the next call,
+ * with no synchronisation in between.  Conversely it is NOT enough for an array written on ANOTHER stream to be complete at the time
+ * of the call unless that stream has been joined with the context's (an event, or gmmiv_ctx_sync after a host wait).  A call that has
+ * to look at device data on the host (the PLDA rules read FTJF for their K_n cache, the host factorisations of the T-matrix M-step
+ * their small matrices) copies it on the context's stream and waits for that stream.  Outputs in device memory are valid in stream order; which calls return with the
+ * stream still busy ("only enqueue") is said per entry point, and DESIGN.md section 4 has the observed table. */
 const char *gmmiv_last_error(void);
 const char *gmmiv_version(void);
 /* Runtime knobs; returns the previous value (-1: unknown key).  EVERY option is state of the context it is set on -- two
@@ -202,6 +211,10 @@ void gmmiv_gmm_destroy(gmmiv_gmm *g);
  * -0.5e20 / variance: the frame then IS a frame of kind (2) for every kernel (holds for variances in 1e-17 .. 1e17) and follows the
  * table above with no host decision -- no flags read back, no compaction, NO SYNCHRONISATION: a call whose arrays are all device
  * pointers only enqueues on the context's stream (rounds 1-5 screened on the host and waited for the stream once per call).
+ * That holds for gmmiv_llk, gmmiv_occ, gmmiv_em_accumulate, gmmiv_llk_use_top(_multi) and gmmiv_frame_moments.  It does NOT hold for
+ * gmmiv_llk_determine_top and gmmiv_topgauss_compute (the fallback flags are read back once per chunk), gmmiv_tv_stats(_lines) (the call
+ * waits once for its utterance table), gmmiv_feat_map (its top-1 selection) and the *_models / gmmiv_llr_trials calls (their table
+ * uploads): these wait for the stream for reasons of their own, whatever the screening does.
  * What remains of the screening is a COUNT: at the start of a frame-consuming call one pass over x (0.3 % of an EM pass) adds the number
  * of kind-(1) frames to a device counter, option "screened_frames" (read / reset like "zero_llk_frames" below).  The option
  * "assume_finite" 1 skips that pass; RESULTS do not depend on it (the C++ host layer checks a FeatureBuffer once, at upload, and

@@ -256,7 +256,11 @@ int gmmiv_score_plda(gmmiv_ctx *c, int rf, int64_t M, int64_t S, const double *m
     if ((rc = a.init(c, rf, M, S, models_sum, segs, scores))) return rc;
     const size_t nn = (size_t)rf * rf;
     std::vector<double> hF(nn);
-    GCHK(hipMemcpy(hF.data(), FTJF, nn * 8, gmmiv_is_device_ptr(FTJF) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    // a device FTJF is read in the order of the context's stream: the call that wrote it (gmmiv_plda_precompute, gmmiv_dgemm) may still be queued
+    if (gmmiv_is_device_ptr(FTJF)) {
+        GCHK(hipMemcpyAsync(hF.data(), FTJF, nn * 8, hipMemcpyDeviceToHost, c->stream));
+        GCHK(hipStreamSynchronize(c->stream));
+    } else memcpy(hF.data(), FTJF, nn * 8);
     // K_n = (n FTJF + I)^-1 and alpha_n = log det K_n on the host, cached per n in the context for as long as FTJF is unchanged
     typedef gmmiv_ctx::PldaK KN;
     if (c->plda_ftjf.size() != nn || memcmp(c->plda_ftjf.data(), hF.data(), nn * 8) != 0) {

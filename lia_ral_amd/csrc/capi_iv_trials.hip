@@ -394,7 +394,11 @@ int gmmiv_score_plda_trials(gmmiv_ctx *c, int rf, int64_t M, int64_t S, const do
 
     const size_t nn = (size_t)rf * rf;
     std::vector<double> hF(nn);
-    GCHK(hipMemcpy(hF.data(), FTJF, nn * 8, gmmiv_is_device_ptr(FTJF) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    // a device FTJF is read in the order of the context's stream, as in gmmiv_score_plda
+    if (gmmiv_is_device_ptr(FTJF)) {
+        GCHK(hipMemcpyAsync(hF.data(), FTJF, nn * 8, hipMemcpyDeviceToHost, c->stream));
+        GCHK(hipStreamSynchronize(c->stream));
+    } else memcpy(hF.data(), FTJF, nn * 8);
     // K_n = (n FTJF + I)^-1 and a_n = log det K_n: the context's cache, shared with gmmiv_score_plda
     typedef gmmiv_ctx::PldaK KN;
     if (c->plda_ftjf.size() != nn || memcmp(c->plda_ftjf.data(), hF.data(), nn * 8) != 0) {

@@ -328,15 +328,18 @@ def _torch():
 
 
 _KEEP = []                       # every device tensor of the running step: see dev()
+RECORDER = None                  # tests/stream_order.py: while set, every device tensor of a step is registered with it under its role
 
 
-def dev(a):
+def dev(a, role="in"):
     """a device copy that lives until the step has synchronised its context (Step.run).  The contexts here own a private stream and a
     call on device tensors only enqueues: a tensor dropped right after the call goes back to torch's caching allocator, and the next
     tensor -- filled on torch's stream -- may land in it while the kernel that reads it is still queued"""
     t = _torch()
     out = t.from_numpy(np.array(a)).cuda()
     _KEEP.append(out)
+    if RECORDER is not None:
+        RECORDER.register(out, role)
     return out
 
 
@@ -349,7 +352,7 @@ def buf(form, shape, dtype=np.float64, fill=None):
     if fill is None:
         fill = SENT32 if np.dtype(dtype) == np.float32 else (SENTINEL if np.dtype(dtype) == np.float64 else -77)
     a = np.full(shape, fill, dtype)
-    return a if form == "host" else dev(a)
+    return a if form == "host" else dev(a, "out")
 
 
 def host(a):
@@ -791,7 +794,7 @@ def s_score_lists(ctx, h, case, form):
 # ---------------------------------------------------------------------------------------------------------------- i-vector back end
 def mut(form, a):
     """a writable copy in the form: what a call that works in place is handed (the cached inputs are read-only)"""
-    return np.array(a) if form == "host" else dev(a)
+    return np.array(a) if form == "host" else dev(a, "inout")
 
 
 def s_tv_centre(ctx, h, case, form):
