@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GMMIV_LIB_PATH") or os.path.join(_HERE, "csrc", "libgmmiv.so")
 
 F32, F64 = 0, 1
+NORMWIN_CMS, NORMWIN_VAR = 1, 2  # include/gmmiv_feat_window.h
 TOP_PARTIAL, TOP_COMPLETE = 0, 1
 
 
@@ -45,6 +46,7 @@ def _load():
     lib.gmmiv_plan_trial_tiles.restype = ct.c_int64
     lib.gmmiv_plan_score_lists.restype = ct.c_int64
     lib.gmmiv_energy_stage_frames.restype = ct.c_int64
+    lib.gmmiv_plan_norm_windows.restype = ct.c_int64
     return lib
 
 
@@ -335,6 +337,27 @@ class Context:
         _chk(lib.gmmiv_feat_norm_online(self._h, _vptr(x), dt, ct.c_int64(ldx), x.shape[1], _ptr(fb), ct.c_int64(fb.shape[0] - 1), ct.c_int64(window),
                                         ct.c_int64(look_ahead), _vptr(out), odt, ct.c_int64(ldo)))
         return out
+
+    # ---- NormFeat's windowMode (include/gmmiv_feat_window.h): the steps of plan_norm_windows, every file's chain in one launch
+    def feat_norm_window(self, x, runs, nfiles, step_off, steps, alpha, cms_only=False, var_only=False, gstat=None, step_stat=None, stats=True):
+        """gmmiv_feat_norm_window, in place on x (a torch device frame matrix, column slices allowed): runs [nrun, 3] int64 (first frame,
+        length, file), step_off [nfiles + 1], steps [nsteps, 4], alpha [nsteps] as plan_norm_windows returns them, host or device.
+        -> (gstat [nfiles, 2 D] = gm | gs, step_stat [nsteps, 2 D] = m' | s'): numpy unless torch device arrays are passed (with device
+        tables the call then only enqueues); stats=False passes NULL for both and returns (None, None)."""
+        x, dt, T, ldx = _feat_view(x)
+        D = x.shape[1]
+        r, so, st = self._tab(runs), self._tab(step_off), self._tab(steps)
+        al = alpha if alpha is None or _is_torch(alpha) else np.ascontiguousarray(alpha, np.float64)
+        nrun = 0 if r is None else r.shape[0]
+        nsteps = 0 if al is None else al.shape[0]
+        if stats and gstat is None:
+            gstat = np.zeros((nfiles, 2 * D))
+        if stats and step_stat is None:
+            step_stat = np.zeros((nsteps, 2 * D))
+        flags = (NORMWIN_CMS if cms_only else 0) | (NORMWIN_VAR if var_only else 0)
+        _chk(lib.gmmiv_feat_norm_window(self._h, _vptr(x), dt, ct.c_int64(ldx), D, _ptr(r), ct.c_int64(nrun), ct.c_int64(nfiles), _ptr(so), _ptr(st), _ptr(al),
+                                        ct.c_int64(nsteps), flags, _ptr(gstat), _ptr(step_stat)))
+        return gstat, step_stat
 
     # ---- EnergyDetector on resident frames: x is the ENERGY COLUMN, a torch device view [T, 1] (x[:, 16:17] of a wider matrix keeps its stride)
     def energy_train(self, x, runs, nfiles, C=3, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.0, model=None, threshold=None,
@@ -834,6 +857,22 @@ ENERGY_EMPTY, ENERGY_NONFINITE, ENERGY_FLOORED, ENERGY_CEILED, ENERGY_MAX_C = 1,
 def energy_stage_frames(dtype_code=F32):
     """gmmiv_energy_stage_frames: the longest selection gmmiv_energy_train stages in LDS; one frame more is streamed per iteration"""
     return int(lib.gmmiv_energy_stage_frames(int(dtype_code)))
+
+
+def plan_norm_windows(runs, nfiles, file_first, window_duration=5.0, window_comp=1.0, frame_length=0.01):
+    """gmmiv_plan_norm_windows (pure host): the schedule of NormFeat's windowMode on the run table [nrun, 3] (first frame, length, file);
+    file_first [nfiles] = the buffer frame where each file starts -> (step_off [nfiles + 1], steps [nsteps, 4], alpha [nsteps])."""
+    r = np.ascontiguousarray(runs, np.int64).reshape(-1, 3)
+    ff = np.ascontiguousarray(file_first, np.int64)
+    assert ff.shape[0] == nfiles
+    off = np.zeros(nfiles + 1, np.int64)
+    steps = np.zeros((max(r.shape[0], 1), 4), np.int64)  # at most one step per run
+    alpha = np.zeros(max(r.shape[0], 1))
+    n = lib.gmmiv_plan_norm_windows(_ptr(r), ct.c_int64(r.shape[0]), ct.c_int64(nfiles), _ptr(ff), ct.c_double(window_duration), ct.c_double(window_comp),
+                                    ct.c_double(frame_length), _ptr(off), _ptr(steps), _ptr(alpha))
+    if n < 0:
+        raise GmmivError("gmmiv error: %s" % lib.gmmiv_last_error().decode())
+    return off, np.ascontiguousarray(steps[:n]), np.ascontiguousarray(alpha[:n])
 
 
 def score_list_class(n, streaming):

@@ -1339,6 +1339,44 @@ int liagpu_norm_feat_files(int device, int n, const char **names, const char *fe
     })
 }
 
+// liagpu::normFeat with windowMode on the frames x [T x D] (rewritten in place), sources and clusters as liagpu_norm_feat takes them;
+// fileMode != 0 applies the file pass afterwards
+int liagpu_norm_feat_window(int device, float *x, long T, int D, long nsrc, const long *src_first, const long *clu_off, const long *seg_begin,
+                            const long *seg_len, double windowDuration, double windowComp, double frameLength, int fileMode, int cmsOnly, int varOnly,
+                            int first_col, int ncols)
+{
+    GUARD({
+        GpuServer srv(device);
+        std::vector<unsigned long> first(src_first, src_first + nsrc);
+        if (nsrc < 1 || src_first[nsrc] != T) throw Exception("norm_feat_window: src_first must end at the frame count");
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D, first);
+        NormFeatCfg cfg;
+        cfg.windowMode = true; cfg.windowDuration = windowDuration; cfg.windowComp = windowComp; cfg.frameLength = frameLength;
+        cfg.fileMode = fileMode != 0; cfg.cmsOnly = cmsOnly != 0; cfg.varOnly = varOnly != 0;
+        normFeat(fs, clusters_from(clu_off, nsrc, seg_begin, seg_len), cfg, (unsigned long)first_col, (unsigned long)ncols);
+        fs.download(x);
+    })
+}
+
+// liagpu::normFeatFiles with windowMode (the other arguments as liagpu_norm_feat_files)
+int liagpu_norm_feat_files_window(int device, int n, const char **names, const char *feature_path, const char *load_ext, const char *save_path,
+                                  const char *save_ext, const char *label_path, const char *label_ext, const char *label, double frameLength,
+                                  const char *mask, int writeAllFeatures, int fileMode, int cmsOnly, int varOnly, double windowDuration, double windowComp)
+{
+    GUARD({
+        GpuServer srv(device);
+        NormFeatFilesCfg cfg;
+        cfg.norm.windowMode = true; cfg.norm.windowDuration = windowDuration; cfg.norm.windowComp = windowComp;
+        cfg.norm.fileMode = fileMode != 0; cfg.norm.cmsOnly = cmsOnly != 0; cfg.norm.varOnly = varOnly != 0;
+        cfg.featureFilesPath = feature_path ? feature_path : ""; cfg.loadFeatureFileExtension = load_ext ? load_ext : "";
+        cfg.saveFeatureFilePath = save_path ? save_path : ""; cfg.saveFeatureFileExtension = save_ext ? save_ext : "";
+        cfg.labelFilesPath = label_path ? label_path : ""; cfg.labelFilesExtension = label_ext ? label_ext : "";
+        cfg.labelSelectedFrames = label ? label : ""; cfg.frameLength = frameLength; cfg.featureServerMask = mask ? mask : "";
+        cfg.writeAllFeatures = writeAllFeatures != 0;
+        normFeatFiles(srv, std::vector<std::string>(names, names + n), cfg);
+    })
+}
+
 // ComputeTest from FILES for one ndx line (test file + client list): RAW models, .prm features with
 // featureServerMask, .lbl selection.  Writes the NIST-style result lines (segmental mode) into out_text
 // and the LLRs into llr_out[nseg x nClients].  ComputeTest.cpp:129-215 + the format readers of io.h.

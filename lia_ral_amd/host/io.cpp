@@ -636,6 +636,10 @@ void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const 
         else c = selectSegments(readLabelFile(cfg.labelFilesPath + names[k] + cfg.labelFilesExtension), cfg.labelSelectedFrames, cfg.frameLength, k);
         for (const Seg &g : c)
             if (g.begin + g.length > f.nFrames) throw Exception("normFeatFiles: a segment of [" + names[k] + "] ends after the last frame of the file");
+        if (cfg.norm.windowMode)
+            for (size_t i = 1; i < c.size(); ++i)
+                if (c[i].begin < c[i - 1].begin + c[i - 1].length)
+                    throw Exception("normFeatFiles: windowMode: the selected segments of [" + names[k] + "] overlap or are not in increasing order");
         clusters.push_back(c);
     }
     if (!dim) throw Exception("normFeatFiles: no frames");
@@ -652,6 +656,7 @@ void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const 
             size_t b = a + 1;
             while (b < cols.size() && cols[b] == cols[b - 1] + 1) ++b;
             NormFeatCfg nc = cfg.norm;
+            nc.frameLength = cfg.frameLength;                  // windowMode counts its windows in the label files' time base
             if (!nc.extMean.empty()) {
                 if (nc.extMean.size() != cols.size() || nc.extStd.size() != cols.size()) throw Exception("normFeatFiles: external mean / std must have one value per masked column");
                 nc.extMean.assign(cfg.norm.extMean.begin() + done, cfg.norm.extMean.begin() + done + (b - a));

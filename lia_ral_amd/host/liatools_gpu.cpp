@@ -1011,17 +1011,47 @@ void pushRuns(std::vector<int64_t> &runs, unsigned long first, unsigned long len
         first += l; len -= l;
     }
 }
+// windowMode: the schedule of every source on the host, then every source's chain of steps in one launch.  A run is one label
+// segment, never cut: the windows are counted in segments.
+void normFeatWindowPass(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSource, const NormFeatCfg &cfg, unsigned long firstCol, int D)
+{
+    const int64_t nfiles = (int64_t)selectedPerSource.size();
+    std::vector<int64_t> runs, fileFirst((size_t)nfiles);
+    for (int64_t s = 0; s < nfiles; ++s) {
+        fileFirst[(size_t)s] = (int64_t)fs.getFirstFeatureIndexOfASource((unsigned long)s);
+        const SegCluster &c = selectedPerSource[(size_t)s];
+        for (size_t i = 0; i < c.size(); ++i) {
+            if (c[i].length < 1) throw Exception("normFeat: windowMode: source " + std::to_string(s) + " has an empty segment");
+            if (i > 0 && c[i].begin < c[i - 1].begin + c[i - 1].length)
+                throw Exception("normFeat: windowMode: the segments of source " + std::to_string(s) + " overlap or are not in increasing order (segment " + std::to_string(i) + ")");
+            runs.push_back(fileFirst[(size_t)s] + (int64_t)c[i].begin); runs.push_back((int64_t)c[i].length); runs.push_back(s);
+        }
+    }
+    const int64_t nrun = (int64_t)(runs.size() / 3);
+    if (nrun == 0) return;
+    GpuServer &srv = fs.server();
+    std::vector<int64_t> stepOff((size_t)nfiles + 1), steps((size_t)nrun * 4);   // at most one step per run
+    std::vector<double> alpha((size_t)nrun);
+    const int64_t nsteps = gmmiv_plan_norm_windows(runs.data(), nrun, nfiles, fileFirst.data(), cfg.windowDuration, cfg.windowComp, cfg.frameLength, stepOff.data(),
+                                                   steps.data(), alpha.data());
+    if (nsteps < 0) throw Exception(std::string("normFeat: windowMode: ") + gmmiv_last_error());
+    const int flags = cfg.cmsOnly ? GMMIV_NORMWIN_CMS : cfg.varOnly ? GMMIV_NORMWIN_VAR : 0;
+    // host tables: the call uploads them and returns when the stream has used them
+    srv.check(gmmiv_feat_norm_window(srv.ctx(), fs.mutableDevice() + firstCol, GMMIV_F32, (int64_t)fs.getVectSize(), D, runs.data(), nrun, nfiles, stepOff.data(),
+                                     steps.data(), alpha.data(), nsteps, flags, nullptr, nullptr));
+}
 } // namespace
 
 void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSource, const NormFeatCfg &cfg, unsigned long firstCol, unsigned long nCols)
 {
+    if (cfg.segmentalMode && cfg.windowMode) throw Exception(" Incompatible modes (segmental/windowMode)");
     if (cfg.cmsOnly && cfg.varOnly) throw Exception(" cmsOnly and varOnly are not compatible)");
     if (selectedPerSource.size() != fs.getSourceCount()) throw Exception("normFeat: one SegCluster per source of the feature buffer expected");
     if (firstCol >= fs.getVectSize() || firstCol + nCols > fs.getVectSize()) throw Exception("normFeat: the column slice lies outside vectSize");
     const int D = (int)(nCols ? nCols : fs.getVectSize() - firstCol);
     if (cfg.extMean.size() != cfg.extStd.size() || (!cfg.extMean.empty() && cfg.extMean.size() != (size_t)D))
         throw Exception("normFeat: external mean / std must both have the length of the normalised columns");
-    const bool fileMode = cfg.fileMode || !cfg.segmentalMode;
+    const bool fileMode = cfg.fileMode || (!cfg.segmentalMode && !cfg.windowMode);
     for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
         for (const Seg &g : selectedPerSource[s])
             if (g.begin + g.length > fs.getFeatureCountOfASource(s)) throw Exception("segment ends after the last frame of its source");
@@ -1032,6 +1062,7 @@ void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSourc
             for (const Seg &g : selectedPerSource[s]) pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, group++);
         normFeatPass(fs, runs, group, cfg, firstCol, D);
     }
+    if (cfg.windowMode) normFeatWindowPass(fs, selectedPerSource, cfg, firstCol, D);
     if (fileMode) {
         runs.clear();
         for (unsigned long s = 0; s < selectedPerSource.size(); ++s)

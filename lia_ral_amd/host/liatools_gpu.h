@@ -17,6 +17,7 @@
 
 #include "../../include/gmmiv.h"
 #include "../../include/gmmiv_iv_trials.h"
+#include "../../include/gmmiv_feat_window.h"
 
 namespace liagpu {
 
@@ -522,9 +523,17 @@ std::vector<SegCluster> energyDetectorBatch(FeatureBuffer &fs, const std::vector
 // (GeneralTools.cpp:670-682) on those frames, in place in the resident buffer.  Both set: segmental first, then file (:272).
 // cmsOnly: the std is replaced by 1 (:358); varOnly: the mean by 0 (:359); both: refused (:261).  extMean / extStd (both vectSize long,
 // or both empty): externalStatsFilename's vectors replace the computed ones (:347-350, :451-453).
+// windowMode (:372-447, include/gmmiv_feat_window.h): every selected segment by the statistics of a window of about windowDuration
+// seconds of selected speech around it, blended with the file's by windowComp and how full the window is; frameLength turns frame
+// indices into the truncated milliseconds the windows are counted in.  segmentalMode with it is refused (:241), ext vectors are
+// ignored by it like the reference does, fileMode with it applies the file pass afterwards (:272, :448); alone it is NOT followed by
+// the file pass (:243).  One plan on the host (gmmiv_plan_norm_windows) and one launch for all sources; a source is one workgroup, so
+// a single long source runs on one compute unit.  A cluster whose segments overlap or are out of order is refused.
 struct NormFeatCfg {
     bool segmentalMode = false, fileMode = false, cmsOnly = false, varOnly = false;
     std::vector<double> extMean, extStd;
+    bool windowMode = false;
+    double windowDuration = 5, windowComp = 1, frameLength = 0.01;
 };
 // ALL sources of the buffer in one batch: selectedPerSource[s] is the cluster of selected segments of source s (Seg::begin counts
 // from the source's first frame; Seg::source is ignored).  A pass is three enqueues on the whole batch -- gmmiv_frame_moments_groups,

@@ -725,11 +725,34 @@ def norm_feat_online(x, src_first=None, window_duration=300, init_with_delay=0, 
     return x
 
 
+def norm_feat_window(x, clusters, src_first=None, window_duration=5.0, window_comp=1.0, frame_length=0.01, file_mode=False, cms_only=False,
+                     var_only=False, first_col=0, ncols=0, device=0):
+    """liagpu::normFeat with windowMode (NormFeat.cpp:372-447) on float32 frames [T, D]: clusters and src_first as norm_feat takes them;
+    the segments of a cluster in increasing order and not overlapping.  file_mode: the file pass afterwards -> the normalised frames."""
+    x = np.array(x, np.float32)
+    T, D = x.shape
+    sf = _sources(src_first, T)
+    off, b, l = _clusters(clusters)
+    _chk(lib.liagpu_norm_feat_window(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(len(sf) - 1), sf.ctypes.data_as(_lp), off.ctypes.data_as(_lp),
+                                     b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), ct.c_double(window_duration), ct.c_double(window_comp),
+                                     ct.c_double(frame_length), int(file_mode), int(cms_only), int(var_only), int(first_col), int(ncols)))
+    return x
+
+
 def norm_feat_files(names, feature_path="", load_ext=".prm", save_ext=".norm.prm", label_path="", label_ext=".lbl", label="speech",
                     frame_length=0.01, mask="", write_all_features=True, save_path="", segmental_mode=False, file_mode=False, cms_only=False,
-                    var_only=False, device=0):
-    """liagpu::normFeatFiles: <feature_path><name><load_ext> -> <save_path or feature_path><name><save_ext> for every name, one batch."""
+                    var_only=False, device=0, window_mode=False, window_duration=5.0, window_comp=1.0):
+    """liagpu::normFeatFiles: <feature_path><name><load_ext> -> <save_path or feature_path><name><save_ext> for every name, one batch.
+    window_mode: NormFeat's windowMode with window_duration / window_comp (segmental_mode with it is refused, file_mode follows it)."""
     arr = (ct.c_char_p * len(names))(*[n.encode() for n in names])
+    if window_mode:
+        if segmental_mode:
+            raise HostError(" Incompatible modes (segmental/windowMode)")
+        _chk(lib.liagpu_norm_feat_files_window(device, len(names), arr, feature_path.encode(), load_ext.encode(), save_path.encode(), save_ext.encode(),
+                                               label_path.encode(), label_ext.encode(), label.encode(), ct.c_double(frame_length), mask.encode(),
+                                               int(write_all_features), int(file_mode), int(cms_only), int(var_only), ct.c_double(window_duration),
+                                               ct.c_double(window_comp)))
+        return
     _chk(lib.liagpu_norm_feat_files(device, len(names), arr, feature_path.encode(), load_ext.encode(), save_path.encode(), save_ext.encode(),
                                     label_path.encode(), label_ext.encode(), label.encode(), ct.c_double(frame_length), mask.encode(),
                                     int(write_all_features), int(segmental_mode), int(file_mode), int(cms_only), int(var_only)))
