@@ -18,6 +18,9 @@ LIB_PATH = os.environ.get("GMMIV_LIB_PATH") or os.path.join(_HERE, "csrc", "libg
 
 F32, F64 = 0, 1
 NORMWIN_CMS, NORMWIN_VAR = 1, 2  # include/gmmiv_feat_window.h
+TURN_GLR, TURN_DGLR, TURN_BIC = 0, 1, 2  # include/gmmiv_turn.h
+TURN_BAD_COV, TURN_CLAMPED = 1, 2
+TURN_CRIT = {"GLR": TURN_GLR, "DGLR": TURN_DGLR, "BIC": TURN_BIC}
 TOP_PARTIAL, TOP_COMPLETE = 0, 1
 
 
@@ -47,6 +50,7 @@ def _load():
     lib.gmmiv_plan_score_lists.restype = ct.c_int64
     lib.gmmiv_energy_stage_frames.restype = ct.c_int64
     lib.gmmiv_plan_norm_windows.restype = ct.c_int64
+    lib.gmmiv_plan_turn_positions.restype = ct.c_int64
     return lib
 
 
@@ -358,6 +362,73 @@ class Context:
         _chk(lib.gmmiv_feat_norm_window(self._h, _vptr(x), dt, ct.c_int64(ldx), D, _ptr(r), ct.c_int64(nrun), ct.c_int64(nfiles), _ptr(so), _ptr(st), _ptr(al),
                                         ct.c_int64(nsteps), flags, _ptr(gstat), _ptr(step_stat)))
         return gstat, step_stat
+
+    # ---- TurnDetection (include/gmmiv_turn.h): the criterion curve, the decisions and the output segments of a list of files
+    def turn_curve(self, x, runs, nfiles, pos_off, win_size=50, win_step=5, crit="DGLR", min_llk=-200.0, max_llk=200.0, value=None, status=None, npos=None):
+        """gmmiv_turn_curve on x (a torch device frame matrix, column slices allowed): runs [nrun, 3] int64 (first frame, length, file) and
+        pos_off [nrun + 1] as plan_turn_positions returns it, host or device (npos is then needed) -> (value [npos], status [npos] int32):
+        numpy unless torch device arrays are passed (with device tables the call then only enqueues)."""
+        x, dt, T, ldx = _feat_view(x)
+        D = x.shape[1]
+        r, po = self._tab(runs), self._tab(pos_off)
+        nrun = 0 if r is None else r.shape[0]
+        if npos is None:
+            npos = int(po[-1])
+        if value is None:
+            value = np.zeros(npos)
+        if status is None:
+            status = np.zeros(npos, np.int32)
+        _chk(lib.gmmiv_turn_curve(self._h, _vptr(x), dt, ct.c_int64(ldx), D, _ptr(r), ct.c_int64(nrun), ct.c_int64(nfiles), _ptr(po), ct.c_int64(npos),
+                                  ct.c_int64(win_size), ct.c_int64(win_step), turn_crit(crit), ct.c_double(min_llk), ct.c_double(max_llk), _ptr(value), _ptr(status)))
+        return value, status
+
+    def turn_pick(self, value, pos_off, alpha=0.7, smoothed=None, dec=None, run_stats=None, n_turns=None, npos=None):
+        """gmmiv_turn_pick on a curve (numpy or torch device) -> (smoothed [npos], dec [npos] uint8, run_stats [nrun, 2] = mean | std,
+        n_turns [nrun]); outputs numpy unless torch device arrays are passed."""
+        po = self._tab(pos_off)
+        nrun = po.shape[0] - 1
+        v = value if _is_torch(value) else np.ascontiguousarray(value, np.float64)
+        if npos is None:
+            npos = int(v.shape[0])
+        if smoothed is None:
+            smoothed = np.zeros(npos)
+        if dec is None:
+            dec = np.zeros(npos, np.uint8)
+        if run_stats is None:
+            run_stats = np.zeros((nrun, 2))
+        if n_turns is None:
+            n_turns = np.zeros(nrun, np.int64)
+        _chk(lib.gmmiv_turn_pick(self._h, _ptr(v), _ptr(po), ct.c_int64(nrun), ct.c_int64(npos), ct.c_double(alpha), _ptr(smoothed), _ptr(dec), _ptr(run_stats),
+                                 _ptr(n_turns)))
+        return smoothed, dec, run_stats, n_turns
+
+    def turn_segments(self, runs, nfiles, pos_off, dec, win_size=50, win_step=5, seg_off=None, seg_begin=None, seg_len=None, seg_count=None, npos=None):
+        """gmmiv_turn_segments.  seg_begin is None: the counting call -> seg_count [nfiles]; with seg_off [nfiles + 1], seg_begin, seg_len:
+        the fill call -> (seg_count, seg_begin, seg_len).  Arrays numpy or torch device."""
+        r, po, so = self._tab(runs), self._tab(pos_off), self._tab(seg_off)
+        nrun = 0 if r is None else r.shape[0]
+        d = dec if _is_torch(dec) else np.ascontiguousarray(dec, np.uint8)
+        if npos is None:
+            npos = int(d.shape[0])
+        if seg_count is None:
+            seg_count = np.zeros(nfiles, np.int64)
+        _chk(lib.gmmiv_turn_segments(self._h, _ptr(r), ct.c_int64(nrun), ct.c_int64(nfiles), _ptr(po), ct.c_int64(npos), _ptr(d), ct.c_int64(win_size),
+                                     ct.c_int64(win_step), _ptr(seg_count), _ptr(so), _ptr(seg_begin), _ptr(seg_len)))
+        return seg_count if seg_begin is None else (seg_count, seg_begin, seg_len)
+
+    def turn_detect(self, x, runs, nfiles, win_size=50, win_step=5, alpha=0.7, crit="DGLR", min_llk=-200.0, max_llk=200.0):
+        """plan + curve + pick + count + fill with host tables and outputs -> dict(pos_off, value, status, smoothed, dec, run_stats, n_turns,
+        seg_off [nfiles + 1], seg_begin, seg_len)"""
+        r = np.ascontiguousarray(runs, np.int64).reshape(-1, 3)
+        po = plan_turn_positions(r, nfiles, win_size, win_step)
+        value, status = self.turn_curve(x, r, nfiles, po, win_size, win_step, crit, min_llk, max_llk)
+        sm, dec, rs, nt = self.turn_pick(value, po, alpha)
+        cnt = self.turn_segments(r, nfiles, po, dec, win_size, win_step)
+        off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        sb, sl = np.zeros(int(off[-1]), np.int64), np.zeros(int(off[-1]), np.int64)
+        if off[-1] > 0:
+            self.turn_segments(r, nfiles, po, dec, win_size, win_step, seg_off=off, seg_begin=sb, seg_len=sl)
+        return dict(pos_off=po, value=value, status=status, smoothed=sm, dec=dec, run_stats=rs, n_turns=nt, seg_off=off, seg_begin=sb, seg_len=sl)
 
     # ---- EnergyDetector on resident frames: x is the ENERGY COLUMN, a torch device view [T, 1] (x[:, 16:17] of a wider matrix keeps its stride)
     def energy_train(self, x, runs, nfiles, C=3, nb_train_it=10, variance_flooring=0.5, variance_ceiling=10.0, alpha=0.0, model=None, threshold=None,
@@ -873,6 +944,33 @@ def plan_norm_windows(runs, nfiles, file_first, window_duration=5.0, window_comp
     if n < 0:
         raise GmmivError("gmmiv error: %s" % lib.gmmiv_last_error().decode())
     return off, np.ascontiguousarray(steps[:n]), np.ascontiguousarray(alpha[:n])
+
+
+def turn_crit(name):
+    """the GMMIV_TURN_* constant of a clusteringCrit name (or the constant itself); DELTABIC is refused: it is not a closed form of the
+    windows' moments (a split of the merged Gaussian and two EM iterations per position)"""
+    if isinstance(name, str):
+        if name == "DELTABIC":
+            raise GmmivError("clusteringCrit DELTABIC is not supported: it needs two EM iterations per window position (GLR, DGLR and BIC are)")
+        if name not in TURN_CRIT:
+            raise GmmivError("unknown clusteringCrit %r (GLR, DGLR or BIC)" % (name,))
+        return TURN_CRIT[name]
+    return int(name)
+
+
+def turn_tile_positions(D, win_size=50, win_step=5):
+    """gmmiv_turn_tile_positions: positions per tile of k_turn_curve (0: the windows do not fit the LDS)"""
+    return int(lib.gmmiv_turn_tile_positions(int(D), ct.c_int64(win_size), ct.c_int64(win_step)))
+
+
+def plan_turn_positions(runs, nfiles, win_size=50, win_step=5):
+    """gmmiv_plan_turn_positions (pure host) on the run table [nrun, 3] (first frame, length, file) -> pos_off [nrun + 1]"""
+    r = np.ascontiguousarray(runs, np.int64).reshape(-1, 3)
+    off = np.zeros(r.shape[0] + 1, np.int64)
+    n = lib.gmmiv_plan_turn_positions(_ptr(r), ct.c_int64(r.shape[0]), ct.c_int64(nfiles), ct.c_int64(win_size), ct.c_int64(win_step), _ptr(off))
+    if n < 0:
+        raise GmmivError("gmmiv error: %s" % lib.gmmiv_last_error().decode())
+    return off
 
 
 def score_list_class(n, streaming):

@@ -1803,6 +1803,93 @@ int liagpu_energy_detector_files(int device, int n, const char **names, const ch
     })
 }
 
+namespace {
+TurnDetectionCfg turn_cfg(const char *crit, long winSize, long winStep, double alpha, double minLLK, double maxLLK)
+{
+    TurnDetectionCfg cfg;
+    cfg.clusteringCrit = crit ? crit : "";
+    if (winSize < 1 || winStep < 1) throw Exception("winSize and winStep must be >= 1");
+    cfg.winSize = (unsigned long)winSize; cfg.winStep = (unsigned long)winStep; cfg.alpha = alpha; cfg.minLLK = minLLK; cfg.maxLLK = maxLLK;
+    return cfg;
+}
+// out_off [nfiles + 1], out_begin / out_len [max_out] <- the clusters in CSR form; curve_off [nseg + 1] (nullable), value / smoothed / dec
+// [max_pos], stats [nseg x 2] <- the curves of the input segments in table order
+void turn_put(const std::vector<SegCluster> &out, const std::vector<std::vector<TurnCurve> > &curves, long *out_off, long *out_begin, long *out_len, long max_out,
+              long *curve_off, double *value, double *smoothed, unsigned char *dec, double *stats, long max_pos)
+{
+    long k = 0, p = 0, q = 0;
+    for (size_t f = 0; f < out.size(); ++f) {
+        out_off[f] = k;
+        for (const Seg &g : out[f]) {
+            if (k >= max_out) throw Exception("out_begin too small");
+            out_begin[k] = (long)g.begin; out_len[k] = (long)g.length; ++k;
+        }
+        if (curve_off)
+            for (const TurnCurve &c : curves[f]) {
+                curve_off[q] = p;
+                if (p + (long)c.value.size() > max_pos) throw Exception("value too small");
+                for (size_t i = 0; i < c.value.size(); ++i, ++p) { value[p] = c.value[i]; smoothed[p] = c.smoothed[i]; dec[p] = c.dec[i]; }
+                stats[2 * q] = c.mean; stats[2 * q + 1] = c.std;
+                ++q;
+            }
+    }
+    out_off[out.size()] = k;
+    if (curve_off) curve_off[q] = p;
+}
+} // namespace
+
+// liagpu::turnDetectionBatch (twin == 0) or the host-only loop twin liagpu::turnDetection per file (twin != 0; no GPU is touched) on nfiles
+// frame matrices laid end to end: x [T x D] float32, file f = frames [file_begin[f], file_begin[f + 1]), its input segments seg_begin /
+// seg_len [seg_off[f], seg_off[f + 1]) (frames of the FILE).  Outputs: see turn_put; the output segments count frames of the file.
+int liagpu_turn_detection_batch(int device, int twin, const float *x, long T, int D, const long *file_begin, long nfiles, const long *seg_off, const long *seg_begin,
+                                const long *seg_len, const char *crit, long winSize, long winStep, double alpha, double minLLK, double maxLLK, long *out_off,
+                                long *out_begin, long *out_len, long max_out, long *curve_off, double *value, double *smoothed, unsigned char *dec, double *stats,
+                                long max_pos)
+{
+    GUARD({
+        const TurnDetectionCfg cfg = turn_cfg(crit, winSize, winStep, alpha, minLLK, maxLLK);
+        if (nfiles < 0 || D < 1 || (nfiles > 0 && (file_begin[0] != 0 || file_begin[nfiles] != T))) throw Exception("file_begin must run from 0 to T");
+        std::vector<SegCluster> sel((size_t)nfiles), out;
+        for (long f = 0; f < nfiles; ++f) sel[(size_t)f] = make_cluster(seg_begin + seg_off[f], seg_len + seg_off[f], seg_off[f + 1] - seg_off[f]);
+        std::vector<std::vector<TurnCurve> > curves;
+        if (twin) {
+            out.resize((size_t)nfiles); curves.resize((size_t)nfiles);
+            for (long f = 0; f < nfiles; ++f) {
+                out[(size_t)f] = turnDetection(x + (size_t)file_begin[f] * D, (unsigned long)(file_begin[f + 1] - file_begin[f]), (unsigned long)D, sel[(size_t)f], cfg, &curves[(size_t)f]);
+                for (Seg &g : out[(size_t)f]) g.source = (unsigned long)f;
+            }
+        } else if (nfiles > 0) {
+            GpuServer srv(device);
+            std::vector<unsigned long> first((size_t)nfiles, 0);
+            for (long f = 0; f < nfiles; ++f) first[(size_t)f] = (unsigned long)file_begin[f];
+            FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D, first);
+            out = turnDetectionBatch(fs, sel, cfg, &curves);
+        }
+        turn_put(out, curves, out_off, out_begin, out_len, max_out, curve_off, value, smoothed, dec, stats, max_pos);
+    })
+}
+
+// liagpu::turnDetectionFiles: names [n] are joined with the paths / extensions; out_off [n + 1], out_begin / out_len [max_out] <- the output
+// segments (what the label files were written from)
+int liagpu_turn_detection_files(int device, int n, const char **names, const char *feature_path, const char *load_ext, const char *label_path,
+                                const char *label_ext, const char *label, const char *save_path, const char *save_ext, const char *mask, double frameLength,
+                                const char *crit, long winSize, long winStep, double alpha, double minLLK, double maxLLK, long *out_off, long *out_begin,
+                                long *out_len, long max_out)
+{
+    GUARD({
+        TurnDetectionFilesCfg cfg;
+        cfg.turn = turn_cfg(crit, winSize, winStep, alpha, minLLK, maxLLK);
+        (void)turnCriterion(cfg.turn.clusteringCrit);
+        GpuServer srv(device);
+        cfg.featureFilesPath = feature_path ? feature_path : ""; cfg.loadFeatureFileExtension = load_ext ? load_ext : "";
+        cfg.labelFilesPath = label_path ? label_path : ""; cfg.labelFilesExtension = label_ext ? label_ext : "";
+        cfg.labelSelectedFrames = label ? label : ""; cfg.saveLabelFilePath = save_path ? save_path : "";
+        cfg.saveLabelFileExtension = save_ext ? save_ext : ""; cfg.featureServerMask = mask ? mask : ""; cfg.frameLength = frameLength;
+        const std::vector<SegCluster> out = turnDetectionFiles(srv, std::vector<std::string>(names, names + n), cfg);
+        turn_put(out, std::vector<std::vector<TurnCurve> >(), out_off, out_begin, out_len, max_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    })
+}
+
 // selectFrames alone (EnergyDetector.cpp:118-157; host only, no GPU): energy [T], threshold, selected segments -> output segments
 int liagpu_select_frames(const float *energy, long T, double threshold, const long *seg_begin, const long *seg_len, long nseg, long *out_begin,
                          long *out_len, long max_out, long *n_out, long *count_out)

@@ -724,6 +724,46 @@ void energyDetectorFiles(GpuServer &srv, const std::vector<std::string> &names, 
     }
 }
 
+std::vector<SegCluster> turnDetectionFiles(GpuServer &srv, const std::vector<std::string> &names, const TurnDetectionFilesCfg &cfg)
+{
+    std::vector<SegCluster> out;
+    if (names.empty()) return out;
+    (void)turnCriterion(cfg.turn.clusteringCrit);                        // a refused criterion before any file is read
+    std::vector<unsigned long> first;
+    std::vector<SegCluster> clusters;
+    std::vector<float> all;
+    unsigned long total = 0, dim = 0;
+    for (size_t k = 0; k < names.size(); ++k) {
+        const FeatureFile f = readFeatureFile(cfg.featureFilesPath + names[k] + cfg.loadFeatureFileExtension, cfg.featureServerMask);
+        if (f.nFrames) {
+            if (dim && f.vectSize != dim) throw Exception("turnDetectionFiles: [" + names[k] + "] has another dimension than the files before it");
+            dim = f.vectSize;
+        }
+        first.push_back(total);
+        total += f.nFrames;
+        all.insert(all.end(), f.data.begin(), f.data.end());
+        SegCluster c;
+        if (cfg.labelFilesExtension.empty()) { Seg s; s.begin = 0; s.length = f.nFrames; s.source = k; if (f.nFrames) c.push_back(s); }
+        else c = selectSegments(readLabelFile(cfg.labelFilesPath + names[k] + cfg.labelFilesExtension), cfg.labelSelectedFrames, cfg.frameLength, k);
+        for (const Seg &g : c)
+            if (g.begin + g.length > f.nFrames) throw Exception("turnDetectionFiles: a segment of [" + names[k] + "] ends after the last frame of the file");
+        clusters.push_back(c);
+    }
+    if (!dim) throw Exception("turnDetectionFiles: no frames");
+    {
+        FeatureBuffer fs(srv, all.data(), total, dim, first);
+        out = turnDetectionBatch(fs, clusters, cfg.turn);
+    }
+    for (size_t k = 0; k < names.size(); ++k) {
+        const std::string path = (cfg.saveLabelFilePath.empty() ? cfg.labelFilesPath : cfg.saveLabelFilePath) + names[k] + cfg.saveLabelFileExtension;
+        std::ofstream o(path.c_str(), std::ios::out | std::ios::trunc);
+        if (!o.good()) throw Exception("Can't create label file [" + path + "]");
+        for (const Seg &g : out[k])
+            o << frameIdxToTime(g.begin, cfg.frameLength) << " " << frameIdxToTime(g.begin + g.length - 1, cfg.frameLength) << " " << cfg.labelSelectedFrames << std::endl;
+    }
+    return out;
+}
+
 // ---- IvTest on an ndx ----------------------------------------------------------------------------------------------------------
 namespace {
 // the lines of an XList: blank-separated elements, empty lines skipped

@@ -188,4 +188,16 @@ struct EnergyDetectorFilesCfg {
 void energyDetectorFiles(GpuServer &srv, const std::vector<std::string> &names, const EnergyDetectorFilesCfg &cfg, std::vector<double> *thresholds = nullptr,
                          std::vector<int> *status = nullptr);
 
+// TurnDetection driven by files (TurnDetection.cpp:292-349): every feature file of the list goes into ONE resident buffer, the input clusters
+// come from <labelFilesPath><name><labelFilesExtension> (labelFilesExtension "": every frame of the file), liagpu::turnDetectionBatch runs
+// once on the whole list, and <saveLabelFilePath><name><saveLabelFileExtension> receives one line "begin_s end_s label" per output segment,
+// the label string of the input segment kept on its pieces (labelSelectedFrames: the cluster holds the segments of that label).
+struct TurnDetectionFilesCfg {
+    TurnDetectionCfg turn;
+    std::string featureFilesPath, loadFeatureFileExtension = ".prm", labelFilesPath, labelFilesExtension = ".lbl", labelSelectedFrames = "speech";
+    std::string saveLabelFilePath, saveLabelFileExtension = ".turn.lbl", featureServerMask;
+    double frameLength = 0.01;
+};
+std::vector<SegCluster> turnDetectionFiles(GpuServer &srv, const std::vector<std::string> &names, const TurnDetectionFilesCfg &cfg);
+
 } // namespace liagpu

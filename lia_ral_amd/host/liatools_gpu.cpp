@@ -1252,6 +1252,201 @@ std::vector<SegCluster> energyDetectorBatch(FeatureBuffer &fs, const std::vector
     return out;
 }
 
+// ---- TurnDetection -----------------------------------------------------------------------------------------
+int turnCriterion(const std::string &crit)
+{
+    if (crit == "GLR") return GMMIV_TURN_GLR;
+    if (crit == "DGLR") return GMMIV_TURN_DGLR;
+    if (crit == "BIC") return GMMIV_TURN_BIC;
+    if (crit == "DELTABIC")
+        throw Exception("turnDetection: clusteringCrit DELTABIC is not supported: it splits the merged Gaussian and runs two EM iterations per window position (GLR, DGLR and BIC are closed forms of the windows' moments)");
+    throw Exception("turnDetection: unknown clusteringCrit [" + crit + "] (GLR, DGLR or BIC)");
+}
+
+namespace {
+// accumulateStatLLK of InitOneGausMixture's model over the same frames (ClusteringCriterion.cpp:807-825, AccumulateStat.cpp:69-95); NaN when
+// a covariance is <= 0 or not finite (the reference's arithmetic gives 0 x inf there)
+double turnWindowLLK(const float *x, unsigned long n, unsigned long D, double minLLK, double maxLLK, std::vector<double> &mean, std::vector<double> &covInv)
+{
+    mean.assign(D, 0.0); covInv.assign(D, 0.0);
+    std::vector<double> &s = mean, &ss = covInv;                         // FrameAccGD: frame by frame
+    for (unsigned long t = 0; t < n; ++t)
+        for (unsigned long d = 0; d < D; ++d) { const double v = (double)x[t * D + d]; s[d] += v; ss[d] += v * v; }
+    double det = 1.0;
+    for (unsigned long d = 0; d < D; ++d) {
+        const double m = s[d] / (double)n, cov = ss[d] / (double)n - m * m;
+        if (!(cov > 0.0) || !std::isfinite(cov)) return NAN;
+        mean[d] = m; covInv[d] = 1.0 / cov; det *= cov;
+    }
+    const double cst = pow(2.0 * M_PI, -0.5 * (double)D) / sqrt(det);
+    double acc = 0.0;
+    for (unsigned long t = 0; t < n; ++t) {
+        double q = 0.0;
+        for (unsigned long d = 0; d < D; ++d) { const double e = (double)x[t * D + d] - mean[d]; q += e * e * covInv[d]; }
+        const double lk = cst * exp(-0.5 * q);
+        double l = minLLK;                                               // the zero-likelihood rule
+        if (lk > 0.0 && std::isfinite(lk)) { l = log(lk); if (l < minLLK) l = minLLK; if (l > maxLLK) l = maxLLK; }
+        acc += l;
+    }
+    return acc;
+}
+
+// :184-263 as written on one segment's curve
+void turnPick(TurnCurve &c, double alpha)
+{
+    std::vector<double> &res = c.smoothed;
+    res = c.value;
+    const unsigned long n = res.size();
+    double buf[2] = {res[0], 0.0};
+    for (unsigned long i = 1; i < n - 1; i++) {
+        buf[i % 2] = res[i];
+        res[i] = 0.25 * buf[(i - 1) % 2] + 0.25 * res[i + 1] + 0.5 * res[i];
+    }
+    double sum = 0.0, sum2 = 0.0;
+    for (unsigned long i = 0; i < n; i++) { sum += res[i]; sum2 += res[i] * res[i]; }
+    c.mean = sum / (double)n;
+    c.std = sqrt(sum2 / (double)n - c.mean * c.mean);
+    c.dec.assign(n, 0);
+    for (unsigned long i = 1, j = 0; i < n - 1; i++) {
+        j = i - 1;
+        double minL = res[i];
+        bool ok = true;
+        while (ok && j > 0) {
+            if (res[j] < minL) { minL = res[j]; j--; } else ok = false;
+        }
+        if (fabs(res[i] - minL) > alpha * c.std) {
+            j = i + 1;
+            double minR = res[i];
+            ok = true;
+            while (ok && j < n) {
+                if (res[j] < minR) { minR = res[j]; j++; } else ok = false;
+            }
+            c.dec[i] = fabs(res[i] - minR) > alpha * c.std ? 1 : 0;
+        }
+    }
+}
+} // namespace
+
+SegCluster turnDetection(const float *frames, unsigned long nFrames, unsigned long D, const SegCluster &cluster, const TurnDetectionCfg &cfg,
+                         std::vector<TurnCurve> *curves)
+{
+    const int crit = turnCriterion(cfg.clusteringCrit);
+    if (cfg.winSize < 1 || cfg.winStep < 1 || D < 1) throw Exception("turnDetection: winSize, winStep and vectSize must be >= 1");
+    const unsigned long W = cfg.winSize, S = cfg.winStep;
+    SegCluster out;
+    if (curves) curves->assign(cluster.size(), TurnCurve());
+    std::vector<double> m, iv;
+    for (size_t k = 0; k < cluster.size(); ++k) {
+        const Seg &seg = cluster[k];
+        if (seg.begin + seg.length > nFrames) throw Exception("turnDetection: a segment ends after the last frame");
+        if (seg.length <= 2 * W) { if (seg.length) out.push_back(seg); continue; }   // :142-145
+        const unsigned long endSeg = seg.begin + seg.length - 1;
+        TurnCurve c;
+        for (unsigned long start1 = seg.begin; start1 + 2 * W - 1 < endSeg; start1 += S) {      // end2 < endSeg
+            const float *x = frames + (size_t)start1 * D;
+            const double l1 = turnWindowLLK(x, W, D, cfg.minLLK, cfg.maxLLK, m, iv), l2 = turnWindowLLK(x + (size_t)W * D, W, D, cfg.minLLK, cfg.maxLLK, m, iv);
+            const double l12 = turnWindowLLK(x, 2 * W, D, cfg.minLLK, cfg.maxLLK, m, iv);
+            const double g = l12 - (l1 + l2);
+            double v = g;
+            if (crit == GMMIV_TURN_DGLR) v = -1.0 * g;
+            if (crit == GMMIV_TURN_BIC) v = (-1 * g) - 0.5 * (double)(2 * D + 1) * log((double)(2 * W));
+            c.value.push_back(v);
+        }
+        turnPick(c, cfg.alpha);
+        unsigned long start = seg.begin;
+        for (unsigned long i = 0; i < c.dec.size(); i++)
+            if (c.dec[i]) {
+                const unsigned long frame = seg.begin + W - 1 + i * S;   // end1 of position i
+                Seg g = seg; g.begin = start; g.length = frame - start + 1;
+                out.push_back(g);
+                start = frame + 1;
+            }
+        if (start < endSeg) { Seg g = seg; g.begin = start; g.length = endSeg - start + 1; out.push_back(g); }
+        if (curves) (*curves)[k] = c;
+    }
+    return out;
+}
+
+std::vector<SegCluster> turnDetectionBatch(FeatureBuffer &fs, const std::vector<SegCluster> &perFile, const TurnDetectionCfg &cfg,
+                                           std::vector<std::vector<TurnCurve> > *curves)
+{
+    const int crit = turnCriterion(cfg.clusteringCrit);
+    const size_t nf = perFile.size();
+    if (nf != fs.getSourceCount()) throw Exception("turnDetectionBatch: one SegCluster per source of the feature buffer expected");
+    const int D = (int)fs.getVectSize();
+    const int64_t W = (int64_t)cfg.winSize, S = (int64_t)cfg.winStep;
+    std::vector<int64_t> runs;
+    std::vector<size_t> runSeg;                                          // the input segment of a run (segments of length 0 have none)
+    for (size_t s = 0; s < nf; ++s)
+        for (size_t k = 0; k < perFile[s].size(); ++k) {
+            const Seg &g = perFile[s][k];
+            if (g.begin + g.length > fs.getFeatureCountOfASource(s)) throw Exception("turnDetectionBatch: a segment ends after the last frame of its source");
+            if (g.length == 0) continue;
+            runs.push_back((int64_t)(fs.getFirstFeatureIndexOfASource(s) + g.begin)); runs.push_back((int64_t)g.length); runs.push_back((int64_t)s);
+            runSeg.push_back(k);
+        }
+    const int64_t nrun = (int64_t)(runs.size() / 3);
+    std::vector<SegCluster> out(nf);
+    if (curves) { curves->assign(nf, std::vector<TurnCurve>()); for (size_t s = 0; s < nf; ++s) (*curves)[s].assign(perFile[s].size(), TurnCurve()); }
+    if (nf == 0) return out;
+    GpuServer &srv = fs.server();
+    std::vector<int64_t> posOff((size_t)nrun + 1, 0);
+    const int64_t npos = gmmiv_plan_turn_positions(runs.data(), nrun, (int64_t)nf, W, S, posOff.data());
+    if (npos < 0) throw Exception(gmmiv_last_error());
+    // one device block: value | smoothed [npos], run_stats [nrun x 2] (doubles), n_turns [nrun] | seg_count [nf] (int64), dec [npos] (bytes)
+    const size_t nd = 2 * (size_t)npos + 2 * (size_t)nrun, ni = (size_t)nrun + nf, bytes = nd * sizeof(double) + ni * sizeof(int64_t) + (size_t)npos + 8;
+    struct Block { void *p = nullptr; ~Block() { if (p) (void)hipFree(p); } } blk;
+    hipcheck(hipMalloc(&blk.p, bytes), "turnDetectionBatch: hipMalloc");
+    double *dVal = (double *)blk.p, *dSm = dVal + npos, *dRs = dSm + npos;
+    int64_t *dNt = (int64_t *)(dRs + 2 * nrun), *dCnt = dNt + nrun;
+    uint8_t *dDec = (uint8_t *)(dCnt + nf);
+    srv.check(gmmiv_turn_curve(srv.ctx(), fs.device(), GMMIV_F32, D, D, runs.data(), nrun, (int64_t)nf, posOff.data(), npos, W, S, crit, cfg.minLLK, cfg.maxLLK,
+                               dVal, nullptr));
+    srv.check(gmmiv_turn_pick(srv.ctx(), dVal, posOff.data(), nrun, npos, cfg.alpha, dSm, dDec, dRs, dNt));
+    srv.check(gmmiv_turn_segments(srv.ctx(), runs.data(), nrun, (int64_t)nf, posOff.data(), npos, dDec, W, S, dCnt, nullptr, nullptr, nullptr));
+    std::vector<unsigned char> host(bytes);
+    hipcheck(hipMemcpyAsync(host.data(), blk.p, bytes, hipMemcpyDeviceToHost, (hipStream_t)srv.stream()), "turnDetectionBatch: download");
+    srv.sync();
+    const double *hVal = (const double *)host.data(), *hSm = hVal + npos, *hRs = hSm + npos;
+    const int64_t *hCnt = (const int64_t *)(hRs + 2 * nrun) + nrun;
+    const uint8_t *hDec = (const uint8_t *)(hCnt + nf);
+    std::vector<int64_t> off(nf + 1, 0);
+    for (size_t s = 0; s < nf; ++s) off[s + 1] = off[s] + hCnt[s];
+    std::vector<int64_t> sb((size_t)off[nf]), sl((size_t)off[nf]);
+    if (off[nf] > 0)
+        srv.check(gmmiv_turn_segments(srv.ctx(), runs.data(), nrun, (int64_t)nf, posOff.data(), npos, dDec, W, S, nullptr, off.data(), sb.data(), sl.data()));
+    // segments never cross an input run and come in run order: a run without positions gives one, another one per decision and its tail
+    int64_t k = 0;
+    for (int64_t q = 0; q < nrun; ++q) {
+        const size_t s = (size_t)runs[3 * q + 2];
+        const int64_t p0 = posOff[(size_t)q], n = posOff[(size_t)q + 1] - p0, b = runs[3 * q], end = b + runs[3 * q + 1] - 1;
+        int64_t cnt = 1;
+        if (n > 0) {
+            int64_t start = b;
+            cnt = 0;
+            for (int64_t i = 0; i < n; ++i) if (hDec[p0 + i]) { ++cnt; start = b + W + i * S; }
+            if (start < end) ++cnt;
+        }
+        const unsigned long first = fs.getFirstFeatureIndexOfASource(s);
+        for (int64_t j = 0; j < cnt; ++j, ++k) {
+            if (k >= off[s + 1]) throw Exception("turnDetectionBatch: the device's segment count of a source differs from its decisions");
+            Seg g = perFile[s][runSeg[(size_t)q]];
+            g.begin = (unsigned long)sb[(size_t)k] - first; g.length = (unsigned long)sl[(size_t)k]; g.source = s;
+            out[s].push_back(g);
+        }
+    }
+    if (k != off[nf]) throw Exception("turnDetectionBatch: the device's segment counts differ from its decisions");
+    if (curves)
+        for (int64_t q = 0; q < nrun; ++q) {
+            const int64_t p0 = posOff[(size_t)q], n = posOff[(size_t)q + 1] - p0;
+            if (n == 0) continue;
+            TurnCurve &c = (*curves)[(size_t)runs[3 * q + 2]][runSeg[(size_t)q]];
+            c.value.assign(hVal + p0, hVal + p0 + n); c.smoothed.assign(hSm + p0, hSm + p0 + n); c.dec.assign(hDec + p0, hDec + p0 + n);
+            c.mean = hRs[2 * q]; c.std = hRs[2 * q + 1];
+        }
+    return out;
+}
+
 // ---- GmmTokenizer -------------------------------------------------------------------------------------
 // the sorted top list of every selected frame, [n x ctop] (DETERMINE_TOP_DISTRIBS + getTopDistribIndexVector, GmmTokenizer.cpp:71-72, :100-101)
 static std::vector<int32_t> topListOfSelection(const SegCluster &selectedSegments, FeatureBuffer &fs, DeviceMixture &world, int ctop,

@@ -9,6 +9,7 @@
 // driver catches and prints exactly like `catch (Exception& e) { cout << e.toString(); }`
 // (LIA_SpkDet/TrainWorld/src/TrainWorld.cpp:187-190).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include <stdexcept>
@@ -18,6 +19,7 @@
 #include "../../include/gmmiv.h"
 #include "../../include/gmmiv_iv_trials.h"
 #include "../../include/gmmiv_feat_window.h"
+#include "../../include/gmmiv_turn.h"
 
 namespace liagpu {
 
@@ -547,6 +549,34 @@ void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSourc
 // running mean / std with the forgetting factor (windowDuration - 1) / windowDuration, started from windowDuration - initWithDelay zero
 // vectors and the source's first initWithDelay frames (0: the tool without the parameter).  One enqueue (gmmiv_feat_norm_online).
 void normFeatOnlineMode(FeatureBuffer &fs, long windowDuration = 300, long initWithDelay = 0);
+
+// ---- TurnDetection (LIA_SpkSeg/TurnDetection/src/TurnDetection.cpp:101-287; the criterion of ClusteringCriterion.cpp:104-139, :807-927): every
+// input segment longer than 2 winSize frames is walked by two adjacent windows of winSize frames in steps of winStep; a one-Gaussian model
+// per window and of both, the criterion GLR / DGLR / BIC from their accumulated log-likelihoods; the curve is smoothed, and a position whose
+// value stands out by alpha standard deviations from the minima to its left and right cuts the segment (include/gmmiv_turn.h has the rule).
+// clusteringCrit "DELTABIC" (a split of the merged Gaussian and two EM iterations per position) is refused with a message.
+struct TurnDetectionCfg {
+    std::string clusteringCrit = "DGLR";
+    unsigned long winSize = 50, winStep = 5;
+    double alpha = 0.7, minLLK = -200.0, maxLLK = 200.0;
+};
+struct TurnCurve {                        // of one input segment; empty for a segment that is copied through
+    std::vector<double> value, smoothed;
+    std::vector<unsigned char> dec;
+    double mean = NAN, std = NAN;
+};
+int turnCriterion(const std::string &clusteringCrit);   // GMMIV_TURN_*; throws on DELTABIC and on an unknown name
+// The loop twin, HOST ONLY, one cluster: frames [nFrames x vectSize] float32, Seg::begin counts frames of that matrix.  The arithmetic is
+// the reference's, in its order: FrameAccGD sums frame by frame, det = prod cov, cst = (2 pi)^(-D/2) / sqrt(det), lk = cst exp(-m / 2),
+// log, the clamp (a likelihood that is 0 or not finite gives minLLK), accumulated frame by frame; then :184-279 as written.
+SegCluster turnDetection(const float *frames, unsigned long nFrames, unsigned long vectSize, const SegCluster &cluster, const TurnDetectionCfg &cfg,
+                         std::vector<TurnCurve> *curves = nullptr);
+// ALL sources of the buffer in one device pass (gmmiv_turn_curve, gmmiv_turn_pick, a counting and a filling gmmiv_turn_segments):
+// perFile[s] is the cluster of input segments of source s (Seg::begin counts from the source's first frame; Seg::source is ignored), the
+// result [s] its output segments (begin from the source's first frame, Seg::source = s, Seg::labelCode = the input segment's).
+// curves (optional) [s][segment] receives the curves and decisions.
+std::vector<SegCluster> turnDetectionBatch(FeatureBuffer &fs, const std::vector<SegCluster> &perFile, const TurnDetectionCfg &cfg,
+                                           std::vector<std::vector<TurnCurve> > *curves = nullptr);
 
 // ---- AccumulateTVStat.h ----------------------------------------------------------------------------
 class TVAcc {

@@ -941,6 +941,57 @@ def energy_detector_files(names, feature_path="", load_ext=".prm", label_path=""
     return th[:len(names)].copy(), st[:len(names)].copy()
 
 
+def turn_detection_batch(frames, segments, crit="DGLR", win_size=50, win_step=5, alpha=0.7, min_llk=-200.0, max_llk=200.0, twin=False, device=0):
+    """TurnDetection on a LIST of files in one device pass (liagpu::turnDetectionBatch), or -- twin=True -- the host-only loop twin
+    liagpu::turnDetection file by file (no GPU): frames[f] a float32 matrix [T_f, D], segments[f] = (seg_begin, seg_len) of its input
+    segments (frames of the file) -> one dict per file: begin, length (the output segments, frames of the file) and curves, one dict(value,
+    smoothed, dec, mean, std) per input segment (empty arrays for a segment that is copied through).  crit DELTABIC is refused."""
+    xs = [np.ascontiguousarray(x, np.float32) for x in frames]
+    nf = len(xs)
+    D = xs[0].shape[1] if nf else 1
+    assert all(x.ndim == 2 and x.shape[1] == D for x in xs)
+    fb = np.zeros(nf + 1, np.int64)
+    fb[1:] = np.cumsum([len(x) for x in xs])
+    x = np.concatenate(xs) if nf and fb[-1] else np.zeros((0, D), np.float32)
+    sb = [np.ascontiguousarray(s[0], np.int64).reshape(-1) for s in segments]
+    sl = [np.ascontiguousarray(s[1], np.int64).reshape(-1) for s in segments]
+    assert len(sb) == nf
+    so = np.zeros(nf + 1, np.int64)
+    so[1:] = np.cumsum([len(b) for b in sb])
+    sbc = np.concatenate(sb + [np.zeros(1, np.int64)]); slc = np.concatenate(sl + [np.zeros(1, np.int64)])
+    npos = int(sum(int(np.maximum(0, -(-(l - 2 * win_size) // win_step)).sum()) for l in sl))
+    room = npos + int(so[-1]) + 1
+    oo = np.zeros(nf + 1, np.int64); ob = np.zeros(room, np.int64); ol = np.zeros(room, np.int64)
+    co = np.zeros(int(so[-1]) + 1, np.int64); val = np.zeros(npos + 1); sm = np.zeros(npos + 1); dec = np.zeros(npos + 1, np.uint8)
+    stats = np.zeros((int(so[-1]) + 1, 2))
+    _chk(lib.liagpu_turn_detection_batch(device, int(bool(twin)), x.ctypes.data_as(_fp), ct.c_long(len(x)), int(D), fb.ctypes.data_as(_lp), ct.c_long(nf),
+                                         so.ctypes.data_as(_lp), sbc.ctypes.data_as(_lp), slc.ctypes.data_as(_lp), crit.encode(), ct.c_long(win_size),
+                                         ct.c_long(win_step), ct.c_double(alpha), ct.c_double(min_llk), ct.c_double(max_llk), oo.ctypes.data_as(_lp),
+                                         ob.ctypes.data_as(_lp), ol.ctypes.data_as(_lp), ct.c_long(room), co.ctypes.data_as(_lp), _d(val), _d(sm),
+                                         dec.ctypes.data_as(ct.c_void_p), _d(stats), ct.c_long(npos + 1)))
+    out = []
+    for f in range(nf):
+        curves = [dict(value=val[co[q]:co[q + 1]].copy(), smoothed=sm[co[q]:co[q + 1]].copy(), dec=dec[co[q]:co[q + 1]].copy(), mean=float(stats[q, 0]),
+                       std=float(stats[q, 1])) for q in range(int(so[f]), int(so[f + 1]))]
+        out.append(dict(begin=ob[oo[f]:oo[f + 1]].copy(), length=ol[oo[f]:oo[f + 1]].copy(), curves=curves))
+    return out
+
+
+def turn_detection_files(names, feature_path="", load_ext=".prm", label_path="", label_ext=".lbl", label="speech", save_path="", save_ext=".turn.lbl",
+                         mask="", frame_length=0.01, crit="DGLR", win_size=50, win_step=5, alpha=0.7, min_llk=-200.0, max_llk=200.0, max_segments=1 << 20,
+                         device=0):
+    """liagpu::turnDetectionFiles: the list's feature files and label files in one batch; one output label file <save_path><name><save_ext>
+    per name, the input label kept on every piece -> per name (begin [], length []) of the segments written (frames of the file)."""
+    names = list(names)
+    arr = (ct.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    oo = np.zeros(len(names) + 1, np.int64); ob = np.zeros(max_segments, np.int64); ol = np.zeros(max_segments, np.int64)
+    _chk(lib.liagpu_turn_detection_files(device, len(names), arr, feature_path.encode(), load_ext.encode(), label_path.encode(), label_ext.encode(),
+                                         label.encode(), save_path.encode(), save_ext.encode(), mask.encode(), ct.c_double(frame_length), crit.encode(),
+                                         ct.c_long(win_size), ct.c_long(win_step), ct.c_double(alpha), ct.c_double(min_llk), ct.c_double(max_llk),
+                                         oo.ctypes.data_as(_lp), ob.ctypes.data_as(_lp), ol.ctypes.data_as(_lp), ct.c_long(max_segments)))
+    return [(ob[oo[k]:oo[k + 1]].copy(), ol[oo[k]:oo[k + 1]].copy()) for k in range(len(names))]
+
+
 def select_frames(energy, threshold, seg_begin, seg_len):
     """selectFrames (EnergyDetector.cpp:118-157) on the host: -> (begin[], length[], frames above the threshold)."""
     e = np.ascontiguousarray(energy, np.float32)
