@@ -382,15 +382,16 @@ class Context:
                                   ct.c_int64(win_size), ct.c_int64(win_step), turn_crit(crit), ct.c_double(min_llk), ct.c_double(max_llk), _ptr(value), _ptr(status)))
         return value, status
 
-    def turn_pick(self, value, pos_off, alpha=0.7, smoothed=None, dec=None, run_stats=None, n_turns=None, npos=None):
+    def turn_pick(self, value, pos_off, alpha=0.7, smoothed=None, dec=None, run_stats=None, n_turns=None, npos=None, smooth=True):
         """gmmiv_turn_pick on a curve (numpy or torch device) -> (smoothed [npos], dec [npos] uint8, run_stats [nrun, 2] = mean | std,
-        n_turns [nrun]); outputs numpy unless torch device arrays are passed."""
+        n_turns [nrun]); outputs numpy unless torch device arrays are passed.  smooth=False passes NULL for smoothed (the library keeps the
+        smoothed curve in its workspace) and returns None in its place."""
         po = self._tab(pos_off)
         nrun = po.shape[0] - 1
         v = value if _is_torch(value) else np.ascontiguousarray(value, np.float64)
         if npos is None:
             npos = int(v.shape[0])
-        if smoothed is None:
+        if smoothed is None and smooth:
             smoothed = np.zeros(npos)
         if dec is None:
             dec = np.zeros(npos, np.uint8)

@@ -28,19 +28,20 @@ SPIN_CYCLES = 20_000_000         # torch.cuda._sleep in front of the restoring c
 # ---------------------------------------------------------------------------------------------------------------- the ABI
 _HANDLE = re.compile(r"\b(gmmiv_ctx|gmmiv_gmm|gmmiv_gmm_batch|gmmiv_comm|gmmiv_hook_fn)\b|(?<!unsigned )\bchar\b")
 _PLANNERS = ("gmmiv_em_acc_len", "gmmiv_tv_packed_len", "gmmiv_shard_range", "gmmiv_energy_stage_frames", "gmmiv_trial_piece",
-             "gmmiv_score_list_class", "gmmiv_iv_trial_piece", "gmmiv_iv_trial_anchor")
+             "gmmiv_score_list_class", "gmmiv_iv_trial_piece", "gmmiv_iv_trial_anchor", "gmmiv_turn_tile_positions")
 _COLLECTIVE = re.compile(r"gmmiv_(allreduce|reduce_scatter|allgather|broadcast)_f64(_begin)?$")
 
 
 def plain(name):
     """whether the proxy forwards `name` as it is: the context, planner and communicator functions (the rows of
-    test_cpu_judged_inventory.EXEMPT with those reasons; the handle functions are NOT among them -- they take device arrays)"""
+    test_cpu_judged_inventory.EXEMPT with those reasons, and gmmiv_plan_norm_windows, a planner that is judged because it hands back
+    doubles; the handle functions are NOT among them -- they take device arrays)"""
     return (name.startswith(("gmmiv_ctx_", "gmmiv_comm_", "gmmiv_plan_")) or name in ("gmmiv_last_error", "gmmiv_version") or name in _PLANNERS
             or bool(_COLLECTIVE.match(name)))
 
 
 def prototypes():
-    """{function: [(parameter name, 'scalar' | 'handle' | 'read' | 'written')]} from the two headers: a pointer to const is read, any
+    """{function: [(parameter name, 'scalar' | 'handle' | 'read' | 'written')]} from the headers of include/: a pointer to const is read, any
     other array pointer is written (and perhaps read)"""
     out = {}
     for name, text in abi_functions().items():
@@ -91,6 +92,12 @@ def poison(a):
 NOT_LATE = (
     ("gather + scatter runs", "runs", "include/gmmiv.h, gmmiv_gather_runs / gmmiv_scatter_runs: rows of (source frame, output row, length) that 'must not "
      "overlap' in the written matrix, and no sentence makes a run of length 0 valid: all-zero rows would all name row 0"),
+    ("normfeat window", "step_off", "include/gmmiv_feat_window.h: the CSR of the steps per file; a host table that does not end at nsteps is refused, and no "
+     "sentence makes a CSR of zeros valid when there are steps"),
+    ("normfeat window", "steps", "include/gmmiv_feat_window.h: rows of (window lo, window hi, apply lo, apply hi) with 'lo <= apply lo < apply hi <= hi': "
+     "an all-zero row breaks apply lo < apply hi"),
+    ("turn detection", "pos_off", "include/gmmiv_turn.h: 'the CSR of gmmiv_plan_turn_positions for the same (W, S)'; a host table that does not end at npos "
+     "is refused, and no sentence makes a CSR of zeros valid when there are positions"),
 )
 # the integer tables that ARE late, with the sentence of the header that makes an all-zero table valid
 ZERO_IS_VALID = {
@@ -101,6 +108,8 @@ ZERO_IS_VALID = {
     "col_id": "gmmiv_score_normalize_list: an id in [0, ncol)",
     "trials": "gmmiv_score_apply_trials: a flag byte, 0 = fill the cell",
     "owner": "gmmiv_jfa_subtract: o = owner[r] is one of the nfact factor rows, and 0 is one",
+    "dec": "gmmiv_turn_segments: a run 'is cut after frame b + W - 1 + i S of every i with dec[i] != 0': a table of zeros cuts nowhere",
+    "seg_off": "gmmiv_turn_segments: 'Segments beyond a file's CSR room are not written': offsets that are all 0 are files without room",
 }
 
 
@@ -360,10 +369,12 @@ _GENERAL = "DEGENERATE INPUTS: 'a call whose arrays are all device pointers only
            "the exceptions are named there)"
 _EXCEPT = "DEGENERATE INPUTS: named among the calls that wait (fallback flags / top-1 selection / a table upload)"
 _NORM = "NormFeat: 'with device pointers throughout every call only enqueues on the context's stream'"
+_NORMWIN = "gmmiv_feat_window.h: 'with device pointers throughout, gstat / step_stat included, the call only enqueues on the context's stream'"
+_TURN = "gmmiv_turn.h: 'with device pointers throughout a call only enqueues on the context's stream'"
 _MODELS = "'the call waits once for its table upload, like the other *_models calls'"
 _SILENT = "no sentence on synchronisation"
 _IVT = "gmmiv_iv_trials.h: 'NOT enqueue-only: it waits for the context's stream once after uploading its tables'"
-# ABI function -> (what include/gmmiv.h says of a call with device pointers throughout, the sentence).  Rule (c) of
+# ABI function -> (what its header says of a call with device pointers throughout, the sentence).  Rule (c) of
 # tests/test_gpu_stream_order.py holds the E rows: every late call with device arrays throughout returns with the stream busy.
 ENQUEUE_ONLY = {
     "gmmiv_llk": (E, _GENERAL), "gmmiv_occ": (E, _GENERAL), "gmmiv_em_accumulate": (E, _GENERAL), "gmmiv_llk_use_top": (E, _GENERAL),
@@ -373,6 +384,8 @@ ENQUEUE_ONLY = {
     "gmmiv_gather_frames": (S, _SILENT),
     "gmmiv_gather_runs": (E, "'with a device table the call only enqueues on the context's stream (no synchronisation)'"),
     "gmmiv_scatter_runs": (E, "'a device table only enqueues'"),
+    "gmmiv_plan_norm_windows": (S, "pure host, no frame data and no context: the proxy forwards it untouched (plain())"),
+    "gmmiv_feat_norm_window": (E, _NORMWIN), "gmmiv_turn_curve": (E, _TURN), "gmmiv_turn_pick": (E, _TURN), "gmmiv_turn_segments": (E, _TURN),
     "gmmiv_frame_moments_groups": (E, _NORM), "gmmiv_frame_moments_stats": (E, _NORM), "gmmiv_feat_norm_apply": (E, _NORM), "gmmiv_feat_norm_online": (E, _NORM),
     "gmmiv_energy_train": (E, "'with device pointers throughout both calls only enqueue on the context's stream'"),
     "gmmiv_energy_select": (E, "'with device pointers throughout both calls only enqueue on the context's stream'"),

@@ -1,5 +1,5 @@
-"""The inventory of the per-element programme: every function of include/gmmiv.h and include/gmmiv_iv_trials.h that produces numbers
-is named in JUDGED with the GPU test module that judges it per element (per frame, trial, system ..) against a derived bar, or
+"""The inventory of the per-element programme: every function of every header under include/ (gmmiv.h, gmmiv_feat_window.h,
+gmmiv_iv_trials.h, gmmiv_turn.h; test_cpu_ws_history.HEADERS lists the directory) that produces numbers is named in JUDGED with the GPU test module that judges it per element (per frame, trial, system ..) against a derived bar, or
 exactly -- or it sits in EXEMPT with one of four reasons.  A function in neither table fails the test, and so does a module that
 does not mention the binding's method: a new entry point cannot arrive judged per array alone without this file saying so."""
 import os
@@ -47,6 +47,12 @@ JUDGED = {
     "gmmiv_feat_compensate_models": ("test_gpu_feat_comp_models", "feat_compensate"),
     "gmmiv_energy_train": ("test_gpu_energy", "energy_train"),
     "gmmiv_energy_select": ("test_gpu_energy", "energy_select"),
+    # windowed NormFeat (the planner hands back doubles -- alpha -- so it is judged, exactly, not exempt) and TurnDetection
+    "gmmiv_plan_norm_windows": ("test_gpu_normwin", "plan_norm_windows"),
+    "gmmiv_feat_norm_window": ("test_gpu_normwin", "feat_norm_window"),
+    "gmmiv_turn_curve": ("test_gpu_turn", "turn_curve"),
+    "gmmiv_turn_pick": ("test_gpu_turn", "turn_pick"),
+    "gmmiv_turn_segments": ("test_gpu_turn", "turn_segments"),
     # total variability: E- and M-step
     "gmmiv_tv_subtract_m": ("test_gpu_tv_elementwise", "tv_subtract_m"),
     "gmmiv_tv_subtract_m_to": ("test_gpu_tv_elementwise", "tv_subtract_m_to"),
@@ -113,7 +119,7 @@ EXEMPT = {
     "gmmiv_em_acc_len": _PLAN, "gmmiv_tv_packed_len": _PLAN, "gmmiv_shard_range": _PLAN, "gmmiv_energy_stage_frames": _PLAN,
     "gmmiv_plan_model_tiles": _PLAN, "gmmiv_plan_feat_tiles": _PLAN, "gmmiv_plan_trial_tiles": _PLAN, "gmmiv_trial_piece": _PLAN,
     "gmmiv_score_list_class": _PLAN, "gmmiv_plan_score_lists": _PLAN, "gmmiv_iv_trial_piece": _PLAN, "gmmiv_iv_trial_anchor": _PLAN,
-    "gmmiv_plan_iv_trial_tiles": _PLAN,
+    "gmmiv_plan_iv_trial_tiles": _PLAN, "gmmiv_turn_tile_positions": _PLAN, "gmmiv_plan_turn_positions": _PLAN,
     "gmmiv_comm_get_unique_id": _COMM, "gmmiv_comm_get_unique_id_for": _COMM, "gmmiv_comm_exchange_id_file": _COMM,
     "gmmiv_comm_create": _COMM, "gmmiv_comm_destroy": _COMM, "gmmiv_comm_world": _COMM, "gmmiv_comm_rank": _COMM,
     "gmmiv_comm_backend": _COMM, "gmmiv_comm_info": _COMM, "gmmiv_comm_take_bytes": _COMM, "gmmiv_allreduce_f64": _COMM,
@@ -126,7 +132,7 @@ def test_every_abi_function_is_judged_or_exempt():
     f = set(abi_functions())
     assert len(f) > 100
     unknown = (set(JUDGED) | set(EXEMPT)) - f
-    assert not unknown, "named here but in neither header: %s" % sorted(unknown)
+    assert not unknown, "named here but in no header: %s" % sorted(unknown)
     both = set(JUDGED) & set(EXEMPT)
     assert not both, "judged AND exempt: %s" % sorted(both)
     missing = f - set(JUDGED) - set(EXEMPT)

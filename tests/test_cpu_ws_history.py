@@ -1,8 +1,10 @@
 """What tests/test_gpu_ws_history.py relies on, checked without a GPU: the large cases dominate the judged ones in every quantity
 that sizes a workspace -- those of the i-vector back end included -- and do not align with them; every judged back-end shape is a row
-of its reference module's own table; the degenerate frames are where the table says; and the programme reaches every function of
-include/gmmiv.h and include/gmmiv_iv_trials.h that takes a context, model or batch handle -- or names it in EXEMPT with a reason --
-so a new ABI function with neither fails here."""
+of its reference module's own table; the degenerate frames are where the table says; the run tables of windowed NormFeat and
+TurnDetection are valid and hold the runs they are there for; and the programme reaches every function of every header under
+include/ (gmmiv.h, gmmiv_feat_window.h, gmmiv_iv_trials.h, gmmiv_turn.h today; HEADERS lists the directory, so a new header is read
+too) that takes a context, model or batch handle -- or names it in EXEMPT with a reason -- so a new ABI function with neither
+fails here."""
 import ast
 import inspect
 import os
@@ -35,6 +37,17 @@ def test_every_judged_case_is_dominated_by_a_large_case_that_does_not_align_with
             assert len(wh.seg_table(large)[1]) >= len(wh.seg_table(small)[1]) and len(wh.trial_table(large)[0]) >= len(wh.trial_table(small)[0])
             assert max(np.diff(wh.file_table(large))) >= max(np.diff(wh.file_table(small)))
             assert sum(large["energy"]) >= sum(small["energy"]) and sum(large["lists"]) >= sum(small["lists"])
+            # windowed NormFeat and TurnDetection: every quantity of run_sizes, and no chain of a judged case can fill more segments
+            # than the dirtying tables have runs (a run yields at least one)
+            ls, ss = wh.run_sizes(large), wh.run_sizes(small)
+            assert set(ls) == set(ss) == {"nrun", "npos", "nsteps", "nrun_D", "seg_room"} <= set(wh.sizes(small))
+            assert all(ls[k] >= ss[k] for k in ss), (large["name"], small["name"], ls, ss)
+            assert large["nfiles"] >= small["nfiles"] and ls["nrun"] >= ss["nrun"] + ss["npos"]
+            assert ls["nrun"] % ss["nrun"] and ls["npos"] % ss["npos"]                      # the run and position counts are no multiples
+    files = lambda c: np.bincount(wh.run_table(c)[0][:, 2], minlength=c["nfiles"])
+    assert max(wh.run_sizes(c)["nrun"] for c in wh.LARGE) > 2 * 1024                        # k_turn_tiles: three chunks of 1024 runs
+    assert max(files(c).max() for c in wh.LARGE) > 2 * 256                                  # k_turn_segments: a file of more than two strides of 256
+    assert all(c["plant"] for c in wh.LARGE)                                                # non-finite frames: neither family screens them
     assert max(c["gcase"][2] for c in wh.LARGE) > 4096 and wh.Z_MB_530 >= 1              # more than one chunk of the smallest scratch
     assert max(np.diff(wh.file_table(wh.LARGE[0]))) >= 2500 > 2 * 1024                     # the online scan: more than two chunks
     assert all(c["cohort"] == 100003 for c in wh.LARGE)
@@ -151,8 +164,49 @@ def test_tables_are_valid_and_have_an_empty_segment():
         fb = wh.file_table(case)
         assert fb[-1] <= T and np.all(np.diff(fb) >= 0)
         assert all(c <= 64 for c in case["trial_ctops"])                                   # gmmiv_llr_trials: ctop <= 64
+        check_run_tables(case)
+    kinds = [run_kinds(c) for c in wh.SMALL]
+    assert all({0, 1} <= set(k["positions"]) and k["short"] and k["empty_files"] for k in kinds), kinds
+    assert any(k["P + 1"] for k in kinds), "no judged case holds a run of P + 1 positions"
     assert wh.SMALL[0]["nseg"] == 5 and wh.SMALL[0]["G"] == 3 and wh.SMALL[0]["ntrial"] == 6
     assert wh.LARGE[0]["nseg"] == 40 and wh.LARGE[0]["G"] == 7 and wh.LARGE[0]["ntrial"] == 60
+
+
+def check_run_tables(case):
+    """the run table of the two new steps: accepted by both planners, inside the files of file_table, and turn_table's CSR, decisions
+    and room are what turn_ref says"""
+    from lia_ral_amd import capi
+    import turn_ref as tn
+    T, nf, W, S = case["gcase"][2], case["nfiles"], wh.TURN_W, wh.TURN_S
+    runs, first = wh.run_table(case)
+    fb = wh.file_table(case)
+    assert runs.dtype == np.int64 and runs.shape[1] == 3 and np.array_equal(first, fb[:-1])
+    assert np.all(np.diff(runs[:, 2]) >= 0) and runs[:, 2].min() >= 0 and runs[:, 2].max() < nf
+    assert np.all(runs[:, 1] >= 1) and np.all(runs[:, 0] >= fb[runs[:, 2]]) and np.all(runs[:, 0] + runs[:, 1] <= fb[runs[:, 2] + 1]) and fb[-1] <= T
+    assert np.all(runs[1:, 0] >= runs[:-1, 0] + runs[:-1, 1])                               # no overlap, begins strictly increasing
+    assert (np.bincount(runs[:, 2], minlength=nf) == 0).sum() == 1                          # a file without runs
+    off, st, al = capi.plan_norm_windows(runs, nf, first, *wh.NORMWIN)                      # the planner accepts the table ...
+    ref = wh._window_plan(case["name"])                                                     # ... and sizes() counts its steps
+    assert np.array_equal(off, ref[0]) and np.array_equal(st, ref[1]) and len(al) == len(ref[2]) == wh.run_sizes(case)["nsteps"] > 0
+    t = wh.turn_table(case)
+    po = capi.plan_turn_positions(runs, nf, W, S)
+    want = [tn.positions_as_written(int(L), W, S) for L in runs[:, 1]]
+    assert np.array_equal(po, t["pos_off"]) and list(np.diff(po)) == want and po[-1] == wh.run_sizes(case)["npos"]
+    assert capi.turn_tile_positions(wh.turn_cols(case), W, S) == case["runs"]["P"] >= 2
+    npos = int(po[-1])
+    assert t["curve"].shape == (npos,) and np.isnan(t["curve"]).sum() == 1 and not (t["curve"] == -0.5).any()
+    assert np.array_equal(t["curve"][np.isfinite(t["curve"])], np.round(t["curve"][np.isfinite(t["curve"])]))
+    assert t["dec"].shape == (npos,) and t["dec"].dtype == np.uint8 and 0 < t["dec"].sum() < npos
+    room = np.diff(t["seg_off"])
+    assert t["seg_off"][0] == 0 and list(room - t["seg_count"]) == [-2] + [0] * (nf - 2) + [3] and t["seg_count"].sum() >= len(runs)
+
+
+def run_kinds(case):
+    runs, _ = wh.run_table(case)
+    t = wh.turn_table(case)
+    n = np.diff(t["pos_off"])
+    return {"positions": sorted(set(n.tolist())), "short": bool((runs[:, 1] <= 2 * wh.TURN_W).any()), "P + 1": bool((n == case["runs"]["P"] + 1).any()),
+            "empty_files": int((np.bincount(runs[:, 2], minlength=case["nfiles"]) == 0).sum())}
 
 
 def test_the_planted_frames_are_where_the_table_says_and_the_large_host_frames_are_float64():
@@ -185,11 +239,12 @@ def test_the_planted_frames_are_where_the_table_says_and_the_large_host_frames_a
 HANDLE = re.compile(r"\bgmmiv_(ctx|gmm|gmm_batch)\s*\*")
 
 
-HEADERS = ("gmmiv.h", "gmmiv_iv_trials.h")
+HEADERS = tuple(sorted(h for h in os.listdir(os.path.join(ROOT, "include")) if h.endswith(".h")))      # every header: a new one cannot stay outside
+assert {"gmmiv.h", "gmmiv_feat_window.h", "gmmiv_iv_trials.h", "gmmiv_turn.h"} <= set(HEADERS), HEADERS
 
 
 def abi_functions():
-    """{name: argument text} of every function prototype of include/gmmiv.h and include/gmmiv_iv_trials.h"""
+    """{name: argument text} of every function prototype of every header under include/"""
     src = "\n".join(open(os.path.join(ROOT, "include", h)).read() for h in HEADERS)
     src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
     src = re.sub(r"//[^\n]*", " ", src)
@@ -239,6 +294,10 @@ def test_the_abi_is_parsed():
     assert {"gmmiv_score_cosine_trials", "gmmiv_score_mahalanobis_trials", "gmmiv_score_twocov_trials", "gmmiv_score_plda_trials"} <= set(f)
     assert HANDLE.search(f["gmmiv_score_plda_trials"]) and HANDLE.search(f["gmmiv_iv_trial_piece"]) and not HANDLE.search(f["gmmiv_plan_iv_trial_tiles"])
     assert HANDLE.search(f["gmmiv_llk"]) and not HANDLE.search(f["gmmiv_em_acc_len"]) and not HANDLE.search(f["gmmiv_allreduce_f64"])
+    new = {"gmmiv_plan_norm_windows", "gmmiv_feat_norm_window", "gmmiv_turn_tile_positions", "gmmiv_plan_turn_positions", "gmmiv_turn_curve",
+           "gmmiv_turn_pick", "gmmiv_turn_segments"}
+    assert new <= set(f) and {n for n in new if HANDLE.search(f[n])} == {"gmmiv_feat_norm_window", "gmmiv_turn_curve", "gmmiv_turn_pick", "gmmiv_turn_segments"}
+    assert len(HEADERS) >= 4 and list(HEADERS) == sorted(HEADERS)
 
 
 def test_every_abi_function_with_a_handle_is_reached_or_exempt():

@@ -26,6 +26,13 @@ about ninety times.  The probe held on every one of the 578 late calls and rule 
 parametrised test takes longer than 0.1 s after its context exists, the 159 of them 10 s together.  On the parent's library the three
 "score rules" tests fail with "score_plda: FTJF + I is not positive definite" (gmmiv_score_plda copied FTJF on the NULL stream and read
 the poison); "score trials" passes there too: gmmiv_score_plda_trials made the same copy, but behind the wait for its table upload.
+
+Measured again on 2026-10-21 with the steps "normfeat window" and "turn detection" in the programme (parent 32904a4;
+profiles/r29/stream_order.json): 602 late calls, 24 of them new -- gmmiv_feat_norm_window 6, gmmiv_turn_curve 3, gmmiv_turn_pick 6,
+gmmiv_turn_segments 9, all with device arrays throughout and all back with the stream busy.  The longest host-side part of a busy
+return among the new calls was 0.018 ms (gmmiv_turn_curve; 0.010 ms gmmiv_feat_norm_window, 0.008 ms gmmiv_turn_pick, 0.007 ms
+gmmiv_turn_segments) next to the 0.089 ms above (0.100 ms in this run, gmmiv_score_twocov again): the 8.3 ms spin outlasts them four
+hundred times.  The probe held on every call; 165 tests, the module 10.3 s, the six new cases 0.1 s each at most.
 """
 import time
 
@@ -121,5 +128,7 @@ def test_every_step_ran_late_and_reached_its_entry_points():
     from test_cpu_judged_inventory import JUDGED
     if FAILED:
         raise RuntimeError("not run: an earlier GPU call of this module failed: %r" % (FAILED[0],))
-    missing = sorted(set(JUDGED) - set(OBSERVED))
+    forwarded = {n for n in JUDGED if so.plain(n)}        # pure host: the proxy hands it on untouched and keeps no record of it
+    assert forwarded == {"gmmiv_plan_norm_windows"}
+    missing = sorted(set(JUDGED) - forwarded - set(OBSERVED))
     assert not missing, "judged functions that no late step called: %s" % missing

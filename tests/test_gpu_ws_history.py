@@ -2,8 +2,9 @@
 
 The workspaces of a context are grow-only and never cleared; a fresh hipMalloc comes back zeroed, so on a context that has done
 nothing else a read of memory the call has not written sees 0 -- and every other GPU file of this suite runs on such contexts.
-Here the programme of tests/ws_history.py (every frame-consuming entry point, the batched models, the front end, the score
-normalisation and the i-vector back end: the T-matrix chain, the development set, PLDA, the scoring rules on matrices and on trial
+Here the programme of tests/ws_history.py (54 steps: every frame-consuming entry point, the batched models, the front end -- windowed
+NormFeat and TurnDetection included, whose tile offsets, run bases, staged decisions, run partials and smoothed curve live in slots
+the back end shares --, the score normalisation and the i-vector back end: the T-matrix chain, the development set, PLDA, the scoring rules on matrices and on trial
 lists, JFA) runs on contexts with different histories and the outputs are compared BIT FOR BIT, no reference and no tolerance:
 
     fresh_small, fresh_small_again        the judged shapes on two fresh contexts: the precondition (they must agree)
@@ -18,7 +19,9 @@ per programme step and form then compares every output of the step in every sequ
 them from passing emptily (no slot grew in the small pass, the large pass touched every slot the small one uses, the NaN calls
 returned NaN or "not positive definite" as each must, the planted frames were counted, the chunked steps launched twice, the E-step
 under tv_batch 16 ran its short batches).  With WS_HISTORY_JSON set to a path the outcome per step, the seconds, the workspace tables
-and the launch counts are written there (profiles/r23/ws_history.json).
+and the launch counts are written there (profiles/r23/ws_history.json; profiles/r29/ws_history.json with the two steps of windowed
+NormFeat and TurnDetection: on an MI355X on 2026-10-21, parent 32904a4, the module takes 11.1 s for 123 tests, 10.5 s for 119 before; a
+large pass spends 0.015 s in either form of "normfeat window" and 0.007 s in "turn detection", and 30 NaN-as-data calls finish it).
 """
 import json
 import os
@@ -176,10 +179,10 @@ def test_the_comparisons_are_not_vacuous():
     # the NaN-as-data calls answered as they must wherever a large pass ran: NaN everywhere, or "not positive definite" and nothing else
     for name in ("fresh_large", "large_then_small", "large_then_small_reversed", "small_then_large", "large_moved_then_small"):
         r = sequence(name)
-        assert r["nan_ok"] is True and len(r["nan"]) == 27, (name, sorted(k for k, v in r["nan"].items() if not v))
+        assert r["nan_ok"] is True and len(r["nan"]) == 30, (name, sorted(k for k, v in r["nan"].items() if not v))
     families = ("tv_estimate_a_and_c", "tv_update_t", "tv_min_divergence", "dev_cov_mat", "dev_mahalanobis", "iv_normalize", "jfa_subtract",
                 "jfa_estimate_z_and_d", "score_cosine_trials", "score_mahalanobis_trials", "score_twocov_trials", "score_plda_trials", "plda_em_iteration",
-                "a finite call after them")
+                "feat_norm_window", "turn_curve", "turn_pick", "a finite call after them")
     assert set(families) <= set(large["nan"])
     # the short-batch E-step ran its batches: k_dgemm(L) is launched once per batch, and the timer holds the launches of the last call --
     # 64 and 65 utterances under tv_batch 16 are 4 and 4 + a batch of one; the default E-step is one batch per call

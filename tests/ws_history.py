@@ -1,6 +1,7 @@
 """The programme behind tests/test_gpu_ws_history.py: every frame-consuming entry point, the batched models, the front-end / score
-calls and the i-vector back end (T-matrix chain, development set, PLDA, scoring rules, JFA) of one context as an ordered list of
-named steps, run on small (judged) and large (dirtying) cases in several orders.
+calls -- windowed NormFeat (include/gmmiv_feat_window.h) and TurnDetection (include/gmmiv_turn.h) among them -- and the i-vector back
+end (T-matrix chain, development set, PLDA, scoring rules, JFA) of one context as an ordered list of 54 named steps, run on small
+(judged) and large (dirtying) cases in several orders.
 Plain numpy at import: the GPU is touched only inside a step.  No reference is involved -- a step returns EVERYTHING its call
 produces and the test compares bits between contexts with different histories ("Results do not depend on a context's
 history").
@@ -11,8 +12,8 @@ step        (ctx, handles, case, form) -> {name: array}.  form "host": numpy in 
 case        a row of SMALL or LARGE.  Data comes from the generators of the reference modules (gmm_ref.model / frames,
             mllr_ref.generate, energy_ref.energy_like, tv_ref.statistics, backend_ref.score_case / ivn_inputs / dev_inputs / jfa_inputs,
             estimation_ref.em_inputs / precompute_inputs / eigen_matrix / lda_inputs / twocov_inputs / ortho_inputs); only the integer
-            tables (segments, trials, runs) and the inputs of the dirtying back-end shapes -- the same recipes at sizes the reference
-            tables do not hold -- are laid out here.
+            tables (segments, trials, runs; run_table / turn_table for the label segments of windowed NormFeat and TurnDetection) and
+            the inputs of the dirtying back-end shapes -- the same recipes at sizes the reference tables do not hold -- are laid out here.
 sequence    an ordered list of (case, step, form) run on ONE context: see SEQUENCES.
 """
 import functools
@@ -26,6 +27,8 @@ import estimation_ref as es
 import gmm_ref as gr
 import iv_trials_ref as ivr
 import mllr_ref
+import normwin_ref as nw
+import turn_ref as tn
 import tv_ref as tr
 from elementwise_judge import SENTINEL, options
 from test_gpu_gmm_elementwise import chunk_plan, layouts
@@ -72,21 +75,32 @@ EIG_COND = 1e3                   # the condition number (estimation_ref.CONDS) o
 
 # name, (C, D, T, spread), segments, models, trials, ctop of determine_top / of llr_trials, utterance layouts of tv_stats, online
 # files, energy files (frames), cohort length, list lengths, matrix (M, S), options of the whole case, planted frames
+# runs: the label segments of windowed NormFeat and TurnDetection (run_table): P = gmmiv_turn_tile_positions at the case's columns for
+# (TURN_W, TURN_S); heads = per file of file_table the lengths of its first runs, a guard frame after each; cycle = the lengths that
+# fill the rest of a file that has heads, no frame between them.  Judged: runs of 0 positions (L = 5 and L = 2 W = 8), 1 (9, 10, 11),
+# 2 (12, 14) and more, P + 1 = 15 positions (L = 51) where the file holds them -- at T = 65 and 66 no file does -- and a file without runs.
+TURN_W, TURN_S, TURN_COLS = 4, 3, 60       # the windows of the "turn detection" step; the columns it reads of a wider matrix
+RUN_CYCLE = (1, 2, 1, 1, 3, 1, 2)          # dirtying: runs without positions, seven of them in eleven frames
 SMALL = (
     dict(name="s37x13x65", gcase=(37, 13, 65, 2.0), nseg=5, G=3, ntrial=6, ctops=(10, 17), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[0]),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[0],
+         runs=dict(P=32, heads=((5, 8, 9, 11), (), (12, 12)), cycle=())),
     dict(name="s129x60x257", gcase=(129, 60, 257, 2.0), nseg=5, G=3, ntrial=6, ctops=(10, 17, 70), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[1]),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[1],
+         runs=dict(P=14, heads=((5, 8, 51, 9), (), (12, 40, 20)), cycle=())),
     dict(name="s40x97x66", gcase=(40, 97, 66, 0.5), nseg=5, G=3, ntrial=6, ctops=(10, 17), trial_ctops=(10, 17), tv="abc", nfiles=3,
-         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[2]),
+         energy=(65, 0, 257), cohort=33, lists=(5, 65, 17), ms=(5, 7), opts={}, plant=False, online_rows=0, iv=IV_SMALL[2],
+         runs=dict(P=14, heads=((5, 8, 9, 12), (), (10, 14)), cycle=())),
 )
 LARGE = (
     dict(name="L530x60x4300", gcase=(530, 60, 4300, 2.0), nseg=40, G=7, ntrial=60, ctops=(10, 17, 70, 100), trial_ctops=(17, 64), tv="bc",
          nfiles=3, energy=(5000, 2500, 0, 6001, 700, 9000, 1300), cohort=100003, lists=(100003, 7, 2049, 64), ms=(7, 11),
-         opts={"z_scratch_mb": Z_MB_530, "timing": 1}, plant=True, online_rows=48000, iv=IV_LARGE[0]),
+         opts={"z_scratch_mb": Z_MB_530, "timing": 1}, plant=True, online_rows=48000, iv=IV_LARGE[0],
+         runs=dict(P=14, heads=((51, 300, 9, 12), (), (8, 5, 200, 14)), cycle=RUN_CYCLE)),
     dict(name="L96x101x700", gcase=(96, 101, 700, 0.5), nseg=40, G=7, ntrial=60, ctops=(10, 17, 64), trial_ctops=(17, 64), tv="abc", nfiles=3,
          energy=(5000, 2500, 0, 6001, 700, 9000, 1300), cohort=100003, lists=(100003, 7, 2049, 64), ms=(7, 11), opts={}, plant=True, online_rows=48000,
-         iv=IV_LARGE[1]),
+         iv=IV_LARGE[1],
+         runs=dict(P=14, heads=((51, 150, 9, 12), (), (8, 5, 40)), cycle=RUN_CYCLE)),
 )
 CASES = {c["name"]: c for c in SMALL + LARGE}
 PLANT_HEAD = {1: np.nan, 5: np.inf, 11: -np.inf, 13: 1e30}     # row -> the value put into one of its dimensions (kind 1: screened)
@@ -152,6 +166,67 @@ def file_table(case):
 
 
 @functools.lru_cache(maxsize=None)
+def _run_table(name):
+    case = CASES[name]
+    fb, spec, rows = file_table(case), case["runs"], []
+    assert len(spec["heads"]) == case["nfiles"]
+    for f, heads in enumerate(spec["heads"]):
+        pos, end = int(fb[f]), int(fb[f + 1])
+        for n in heads:
+            assert pos + n <= end, (name, f, n)
+            rows.append((pos, n, f))
+            pos += n + 1
+        k = 0
+        while heads and spec["cycle"] and pos + spec["cycle"][k % len(spec["cycle"])] <= end:
+            n = spec["cycle"][k % len(spec["cycle"])]
+            rows.append((pos, n, f))
+            pos, k = pos + n, k + 1
+    return _frozen((np.array(rows, np.int64).reshape(-1, 3), fb[:-1].copy()))
+
+
+def run_table(case):
+    """-> (runs [nrun, 3] = (first frame, length, file), file_first [nfiles]) of the "normfeat window" and "turn detection" steps.
+    The existing tables do not serve as they are: seg_table / _norm_runs cut [3, T - 1) into ADJACENT segments of G groups (G = 7 > nfiles
+    on the dirtying cases) and drop the empty one, so no run is shorter than 2 W, none lies behind a guard frame and there cannot be 2049 of
+    them; file_table is sound as the files' extents -- [file_begin[f], file_begin[f + 1]), the middle file empty -- and the runs are laid
+    inside them: begins strictly increasing, no overlap (gmmiv_plan_norm_windows), file ids non-decreasing, a file without runs"""
+    return _run_table(case["name"])
+
+
+def turn_cols(case):
+    return min(case["gcase"][1], TURN_COLS)
+
+
+@functools.lru_cache(maxsize=None)
+def _turn_table(name):
+    case = CASES[name]
+    runs, _ = _run_table(name)
+    nf = case["nfiles"]
+    n = [tn.positions_as_written(int(L), TURN_W, TURN_S) for L in runs[:, 1]]
+    po = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    npos = int(po[-1])
+    rng = np.random.default_rng(len(runs) + npos)
+    curve = rng.integers(-50, 50, npos).astype(np.float64)                 # exact under the smoothing; no -0.5 (stream_order.poison)
+    curve[npos // 2] = np.nan
+    dec = (rng.random(npos) < 0.3).astype(np.uint8)
+    cnt = np.zeros(nf, np.int64)
+    for r, (b, L, f) in enumerate(runs):
+        cnt[f] += len(tn.segments_as_written(int(b), int(L), TURN_W, TURN_S, dec[int(po[r]):int(po[r + 1])]))
+    room = cnt.copy()
+    room[0] -= 2                                                           # two entries short for the first file, three long for the last
+    room[nf - 1] += 3
+    assert room.min() >= 0 and cnt[0] > 2
+    return _frozen(dict(runs=runs, pos_off=po, curve=curve, dec=dec, seg_count=cnt, seg_off=np.concatenate([[0], np.cumsum(room)]).astype(np.int64)))
+
+
+def turn_table(case):
+    """-> dict(runs, pos_off: the CSR of turn_ref.positions_as_written for (TURN_W, TURN_S); curve: an integer curve with one NaN over
+    pos_off, for turn_pick alone; dec: a decision table of its own, for turn_segments alone; seg_count: the segments per file that dec
+    makes (turn_ref.segments_as_written); seg_off: the CSR of a room two entries short for file 0 and three long for the last file)"""
+    return _turn_table(case["name"])
+
+
+@functools.lru_cache(maxsize=None)
 def _batch_models(name):
     case = CASES[name]
     ms = []
@@ -169,8 +244,28 @@ def sizes(case):
     out = dict(C=C, D_tiles=(D + 3) // 4, T=T, nseg=case["nseg"], G=case["G"], ntrial=case["ntrial"], ctop=max(case["ctops"]),
                trial_ctop=max(case["trial_ctops"]), nfiles=case["nfiles"], energy_files=len(case["energy"]), energy_frames=max(case["energy"]),
                cohort=case["cohort"], list_len=max(case["lists"]), nlists=len(case["lists"]), M=case["ms"][0], S=case["ms"][1])
+    out.update(run_sizes(case))
     out.update(iv_sizes(case))
     return out
+
+
+NORMWIN = (0.5, 0.8, 0.01)       # window duration (s), windowComp, frame length (s) of the "normfeat window" step
+
+
+@functools.lru_cache(maxsize=None)
+def _window_plan(name):
+    runs, first = _run_table(name)
+    return _frozen(nw.plan(runs, CASES[name]["nfiles"], first, *NORMWIN))
+
+
+def run_sizes(case):
+    """what sizes a slot of gmmiv_feat_norm_window and the gmmiv_turn_* calls: the run partials are 2 D doubles per run (WS_PART), the
+    staged tables and outputs go by runs, positions, steps and files, the segment room by the CSR the caller brings -- seg_room is the
+    larger of the room of turn_table's own dec and of nrun + npos, which no chain of the judged cases can exceed (a run yields at most
+    one segment per position and one more)"""
+    t = turn_table(case)
+    nrun, npos = len(t["runs"]), int(t["pos_off"][-1])
+    return dict(nrun=nrun, npos=npos, nsteps=len(_window_plan(case["name"])[2]), nrun_D=nrun * case["gcase"][1], seg_room=max(int(t["seg_off"][-1]), nrun + npos))
 
 
 def iv_sizes(case):
@@ -716,6 +811,59 @@ def s_norm_online(ctx, h, case, form):
     return {"out": out}
 
 
+def s_normwin(ctx, h, case, form):
+    """the plan of NORMWIN on run_table, then two calls, each on a copy of the frames: flags 0 with both statistics, cmsOnly with
+    neither.  The rewritten buffers come back whole: the guard frames between the runs and the unowned rows keep their values"""
+    from lia_ral_amd import capi
+    D, nf = case["gcase"][1], case["nfiles"]
+    runs, first = run_table(case)
+    off, st, al = capi.plan_norm_windows(runs, nf, first, *NORMWIN)
+    r, o, s, a = to(form, runs), to(form, off), to(form, st), to(form, al)
+    x = frames(case, form)
+    both = mut("device", x)
+    gstat, sstat = buf(form, (nf, 2 * D)), buf(form, (len(al), 2 * D))
+    ctx.feat_norm_window(both, r, nf, o, s, a, gstat=gstat, step_stat=sstat)
+    cms = mut("device", x)
+    ctx.feat_norm_window(cms, r, nf, o, s, a, cms_only=True, stats=False)
+    return {"frames": both, "gstat": gstat, "step_stat": sstat, "frames cmsOnly": cms}
+
+
+def s_turn(ctx, h, case, form):
+    """(a) the chain of a caller: curve -> pick -> segments, counted, then filled into the room the counts give and three entries more;
+    (b) turn_pick alone on turn_table's integer curve with smoothed = NULL: the smoothed curve lives in WS_PART; (c) turn_segments alone
+    on turn_table's dec, in a room two entries short for file 0 and three long for the last file.  For D > TURN_COLS the frames are the
+    first TURN_COLS columns of the matrix, with its stride"""
+    nf, W, S = case["nfiles"], TURN_W, TURN_S
+    t = turn_table(case)
+    nrun, npos = len(t["runs"]), int(t["pos_off"][-1])
+    x = dev(frames(case, form))[:, :turn_cols(case)]
+    r, p = to(form, t["runs"]), to(form, t["pos_off"])
+    ints = lambda n: buf(form, (n,), np.int64)
+    # (a)
+    value, status = buf(form, (npos,)), buf(form, (npos,), np.int32)
+    ctx.turn_curve(x, r, nf, p, W, S, "DGLR", value=value, status=status, npos=npos)
+    sm, dec, rs, nt = buf(form, (npos,)), buf(form, (npos,), np.uint8, fill=9), buf(form, (nrun, 2)), ints(nrun)
+    ctx.turn_pick(value, p, 0.5, sm, dec, rs, nt, npos=npos)
+    cnt = ints(nf)
+    ctx.turn_segments(r, nf, p, dec, W, S, seg_count=cnt, npos=npos)
+    off = np.concatenate([[0], np.cumsum(host(cnt))]).astype(np.int64)
+    assert 0 < off[-1] <= nrun + npos
+    cnt_fill, sb, sl = ints(nf), ints(int(off[-1]) + 3), ints(int(off[-1]) + 3)
+    ctx.turn_segments(r, nf, p, dec, W, S, seg_off=to(form, off), seg_begin=sb, seg_len=sl, seg_count=cnt_fill, npos=npos)
+    out = {"value": value, "status": status, "smoothed": sm, "dec": dec, "run_stats": rs, "n_turns": nt, "seg_count": cnt, "seg_count of the fill": cnt_fill,
+           "seg_begin": sb, "seg_len": sl}
+    # (b)
+    dec_b, rs_b, nt_b = buf(form, (npos,), np.uint8, fill=9), buf(form, (nrun, 2)), ints(nrun)
+    ctx.turn_pick(to(form, t["curve"]), p, 0.5, dec=dec_b, run_stats=rs_b, n_turns=nt_b, npos=npos, smooth=False)
+    out.update({"pick alone dec": dec_b, "pick alone run_stats": rs_b, "pick alone n_turns": nt_b})
+    # (c)
+    room = int(t["seg_off"][-1])
+    cnt_c, sb_c, sl_c = ints(nf), ints(room + 3), ints(room + 3)
+    ctx.turn_segments(r, nf, p, to(form, t["dec"]), W, S, seg_off=to(form, t["seg_off"]), seg_begin=sb_c, seg_len=sl_c, seg_count=cnt_c, npos=npos)
+    out.update({"segments alone seg_count": cnt_c, "segments alone seg_begin": sb_c, "segments alone seg_len": sl_c})
+    return out
+
+
 def s_runs(ctx, h, case, form):
     C, D, T, _ = case["gcase"]
     x = dev(_frames(case["name"], "float32"))
@@ -1051,6 +1199,8 @@ PROGRAMME = (
     Step("mllr_adapt", s_mllr, ("gmmiv_mllr_adapt_models",), only=_mllr_ok),
     Step("normfeat", s_normfeat, ("gmmiv_frame_moments_groups", "gmmiv_frame_moments_stats", "gmmiv_feat_norm_apply")),
     Step("feat_norm_online", s_norm_online, ("gmmiv_feat_norm_online",)),
+    Step("normfeat window", s_normwin, ("gmmiv_plan_norm_windows", "gmmiv_feat_norm_window")),
+    Step("turn detection", s_turn, ("gmmiv_turn_curve", "gmmiv_turn_pick", "gmmiv_turn_segments")),
     Step("gather + scatter runs", s_runs, ("gmmiv_gather_runs", "gmmiv_scatter_runs", "gmmiv_gather_frames")),
     Step("energy_detect", s_energy, ("gmmiv_energy_train", "gmmiv_energy_select")),
     Step("score matrix", s_score_matrix, ("gmmiv_score_cohort_stats", "gmmiv_score_normalize")),
@@ -1121,6 +1271,7 @@ NAN_IVN = (67, 41, 259)
 NAN_JFA = (9, 14, 8, 15, 41)     # C, D, R, speakers, sessions
 NAN_SCORE = (131, 259, 261)
 NAN_EM = (37, 8, 6)
+NAN_RUNS = (40, 10, TURN_W, TURN_S)     # files, runs of 290 frames per file, the windows of the turn calls: 400 runs, 37 600 positions
 
 
 def nan(*shape):
@@ -1145,7 +1296,8 @@ def not_positive_definite(call):
 
 
 def nan_calls(ctx):
-    """the NaN-as-data calls that finish a large pass, one per family of the back end at a large odd shape, host arrays in (they are
+    """the NaN-as-data calls that finish a large pass, one per family of the back end at a large odd shape -- and one each of windowed
+    NormFeat and TurnDetection above the judged sizes -- host arrays in (they are
     staged through the shared WS_T* / WS_X / WS_LSE / WS_PART / WS_TIV / WS_IVT_* slots, which hold NaN afterwards) -> {call: whether it
     answered as it must}: NaN everywhere from a call without an SPD system, "not positive definite" from one with; the last entry is a
     finite call the context must still serve"""
@@ -1200,6 +1352,18 @@ def nan_calls(ctx):
     ok["score_twocov_trials"] = all_nan(ctx.score_twocov_trials(nan(dim, M), nan(dim, S), p["G"], p["H"], tm, ts))
     ok["score_plda_trials"] = all_nan(ctx.score_plda_trials(nan(dim, M), p["nsess"], nan(dim, S), p["FTJF"], tm, ts))
     ok["score_plda_trials NaN FTJF"] = not_positive_definite(lambda: ctx.score_plda_trials(nan(dim, M), p["nsess"], nan(dim, S), nan(dim, dim), tm, ts))
+    # windowed NormFeat and TurnDetection, host tables: more files, runs, steps and positions than any judged case, NaN frames
+    from lia_ral_amd import capi
+    nf, per, W, S = NAN_RUNS
+    big = np.array([[i * 3000 + k * 300, 290, i] for i in range(nf) for k in range(per)], np.int64)
+    xb = t.full((nf * 3000, 70), float("nan"), dtype=t.float64, device="cuda")
+    ob, sb, ab = capi.plan_norm_windows(big, nf, big[::per, 0].copy(), 5.0, 1.0, 0.01)
+    ok["feat_norm_window"] = len(ab) > max(run_sizes(c)["nsteps"] for c in SMALL) and all_nan(*ctx.feat_norm_window(xb, big, nf, ob, sb, nan(len(ab))))
+    po = capi.plan_turn_positions(big, nf, W, S)
+    value, status = ctx.turn_curve(xb[:, :TURN_COLS], big, nf, po, W, S, "DGLR")
+    ok["turn_curve"] = all_nan(value) and bool((status == tn.BAD_COV).all()) and len(value) == per * nf * tn.positions_as_written(290, W, S)
+    sm, dec, rs, nt = ctx.turn_pick(value, po, 0.5)
+    ok["turn_pick"] = all_nan(sm, rs) and not dec.any() and not nt.any()
     # PLDA EM
     dim, rf, rg = NAN_EM
     n = int(sps.sum())
