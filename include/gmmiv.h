@@ -62,6 +62,26 @@ void *gmmiv_ctx_stream(gmmiv_ctx *ctx);
  * to look at device data on the host (the PLDA rules read FTJF for their K_n cache, the host factorisations of the T-matrix M-step
  * their small matrices) copies it on the context's stream and waits for that stream.  Outputs in device memory are valid in stream order; which calls return with the
  * stream still busy ("only enqueue") is said per entry point, and DESIGN.md section 4 has the observed table. */
+/* ADDRESSING.  Every offset from a pointer handed to a call is computed in 64 bits: a frame t of (x, T, ldx) is read at x + t * ldx, a
+ * row of (out, ldo), of a matrix with ld / lda / ldb / ldc, a matrix of a batch with sA / sB / sC and a model of a table with *_stride
+ * likewise, wherever the product lies -- beyond 2^32 bytes, 2^31 elements or 2^32 elements from the pointer.  Frame numbers and row
+ * numbers in tables (runs, frame_idx, file_begin, utt_begin, seg_begin and the segment / trial tables) are int64_t and are used as such:
+ * a resident corpus of 60 float32 per frame passes 2^32 bytes at 18 M frames and 2^31 elements at 36 M frames, and nothing changes
+ * there.  Results depend on the frames addressed, not on how far from the pointer they lie.
+ * COUNTS are narrower than offsets.  Model and matrix dimensions (C, D, M, N, K, batch, nrows, G, ctop) are int.  The int64_t counts --
+ * frames per call (T), entries per table (n, nrun, nseg, nfiles, ntrial, U, nlines, npos, ngroups) -- go up to 2^31 - 1 at the most, and
+ * some stop earlier.  The limits that are CHECKED and refused with a message:
+ *   nseg of gmmiv_llk_models, gmmiv_tv_stats_models, gmmiv_em_stats_models, gmmiv_feat_compensate_models; nseg and ntrial of
+ *   gmmiv_llr_trials; U of gmmiv_tv_stats          more than (2^31 - 1) / 64 = 33 554 431: GMMIV_ERR_UNSUPPORTED ("too many ..")
+ *   T of gmmiv_occ; the distributions (rows for axis 0, columns for axis 1) of gmmiv_score_cohort_stats and of gmmiv_score_list_stats;
+ *   M of gmmiv_score_normalize; n of gmmiv_iv_normalize; M and S of the scoring rules, M, S and ntrial of the *_trials scoring rules
+ *                                                  more than 2^31 - 1: GMMIV_ERR_UNSUPPORTED
+ *   n of gmmiv_score_normalize_list                more than 256 (2^31 - 1): GMMIV_ERR_UNSUPPORTED
+ *   gmmiv_turn_curve                               npos / gmmiv_turn_tile_positions + min(nrun, npos) tiles beyond 2^31 - 1: GMMIV_ERR_ARG
+ * Every other count (T of the other frame-consuming calls, n, nrun, nfiles, nlines, ngroups) is NOT checked against 2^31 - 1: several
+ * launch grids and work lists are sized by them in 32 bits, and beyond it the behaviour is undefined.  A caller with more frames or
+ * table entries than that cuts the call -- the frames stay where they are: the pointer or the frame numbers move, which is what the
+ * paragraph above is for. */
 const char *gmmiv_last_error(void);
 const char *gmmiv_version(void);
 /* Runtime knobs; returns the previous value (-1: unknown key).  EVERY option is state of the context it is set on -- two

@@ -1423,10 +1423,15 @@ class GmmBatch:
         assert n in (row, self.G * row), "a table is shared ([%d]) or per model ([%d x %d])" % (row, self.G, row)
         return 0 if n == row and self.G > 1 else row
 
-    def load(self, w, mean, covinv):
-        """w [C] or [G, C]; mean, covinv [C, D] or [G, C, D] (numpy or torch device): a table with one model's size is shared by all G."""
-        w, mean, covinv = _f64(w), _f64(mean), _f64(covinv)
+    def load(self, w, mean, covinv, strides=None):
+        """w [C] or [G, C]; mean, covinv [C, D] or [G, C, D] (numpy or torch device): a table with one model's size is shared by all G.
+        strides = (w, mean, covinv) in doubles: the tables are then pointers to model 0 (model g at p + g * stride), not sized arrays."""
         CD = self.C * self.D
+        if strides is not None:
+            _chk(lib.gmmiv_gmm_batch_load(self._h, _vptr(w), ct.c_int64(strides[0]), _vptr(mean), ct.c_int64(strides[1]), _vptr(covinv),
+                                          ct.c_int64(strides[2])))
+            return self
+        w, mean, covinv = _f64(w), _f64(mean), _f64(covinv)
         _chk(lib.gmmiv_gmm_batch_load(self._h, _ptr(w), ct.c_int64(self._stride(w, self.C)), _ptr(mean), ct.c_int64(self._stride(mean, CD)),
                                       _ptr(covinv), ct.c_int64(self._stride(covinv, CD))))
         return self
@@ -1537,9 +1542,10 @@ class GmmBatch:
         return llr, client_mean, world_mean
 
     def map_adapt(self, N, F, count, w0, mean0, cur_mean, method="MAPOccDep", mean=True, weight=False, reg=(16.0, 16.0, 16.0), alpha_mean=0.75,
-                  mean_out=None, w_out=None, count_stride=1):
+                  mean_out=None, w_out=None, count_stride=1, cur_stride=None):
         """computeMAP for the G statistics rows (gmmiv_map_adapt_models): -> (means [G, C*D], weights [G, C]).  reg = (mean, var, weight)
-        like host_capi.compute_map; cur_mean [C*D] (shared) or [G, C*D]; count [G] (count_stride 1) or e.g. seg_llk[:, 1] as stride 2."""
+        like host_capi.compute_map; cur_mean [C*D] (shared) or [G, C*D]; count [G] (count_stride 1) or e.g. seg_llk[:, 1] as stride 2.
+        cur_stride (doubles): cur_mean is then a pointer to model 0's means, model g at cur_mean + g * cur_stride."""
         G, C, D = self.G, self.C, self.D
         tor = _is_torch(N)
         if mean_out is None:
@@ -1551,7 +1557,8 @@ class GmmBatch:
                 mean_out = np.empty((G, C * D)); w_out = np.empty((G, C))
         cur = _f64(cur_mean)
         _chk(lib.gmmiv_map_adapt_models(self.ctx._h, G, C, D, _ptr(_f64(N)), _ptr(_f64(F)), _ptr(_f64(count)), ct.c_int64(count_stride), _ptr(_f64(w0)),
-                                        _ptr(_f64(mean0)), _ptr(cur), ct.c_int64(self._stride(cur, C * D)), MAP_METHODS.get(method, 0), int(bool(mean)),
+                                        _ptr(_f64(mean0)), _vptr(cur) if cur_stride is not None else _ptr(cur),
+                                        ct.c_int64(self._stride(cur, C * D) if cur_stride is None else cur_stride), MAP_METHODS.get(method, 0), int(bool(mean)),
                                         int(bool(weight)), ct.c_double(reg[0]), ct.c_double(reg[2]), ct.c_double(alpha_mean), _ptr(mean_out),
                                         _ptr(w_out)))
         return mean_out, w_out
