@@ -1377,6 +1377,89 @@ int liagpu_norm_feat_files_window(int device, int n, const char **names, const c
     })
 }
 
+// liagpu::normFeat with warp on the frames x [T x D] (rewritten in place), sources and clusters as liagpu_norm_feat takes them; the
+// target table (nbin_t, tbounds [nbin_t + 1], tcount [nbin_t]) or, with nbin_t == 0, the file histo_path (NULL: the refusal of the
+// rand()-made default target).  windowMode != 0 is passed on to be refused by name.
+int liagpu_norm_feat_warp(int device, float *x, long T, int D, long nsrc, const long *src_first, const long *clu_off, const long *seg_begin,
+                          const long *seg_len, int segmentalMode, int fileMode, int windowMode, int cmsOnly, int varOnly, long warpBinCount,
+                          int warpAdd01Norm, int nbin_t, const double *tbounds, const double *tcount, const char *histo_path, int first_col, int ncols)
+{
+    GUARD({
+        GpuServer srv(device);
+        std::vector<unsigned long> first(src_first, src_first + nsrc);
+        if (nsrc < 1 || src_first[nsrc] != T) throw Exception("norm_feat_warp: src_first must end at the frame count");
+        FeatureBuffer fs(srv, x, (unsigned long)T, (unsigned long)D, first);
+        NormFeatCfg cfg;
+        cfg.warp = true; cfg.warpBinCount = (unsigned long)warpBinCount; cfg.warpAdd01Norm = warpAdd01Norm != 0;
+        cfg.segmentalMode = segmentalMode != 0; cfg.fileMode = fileMode != 0; cfg.windowMode = windowMode != 0;
+        cfg.cmsOnly = cmsOnly != 0; cfg.varOnly = varOnly != 0;
+        if (nbin_t > 0) { cfg.warpTarget.bounds.assign(tbounds, tbounds + nbin_t + 1); cfg.warpTarget.count.assign(tcount, tcount + nbin_t); }
+        if (histo_path) cfg.warpGaussHistoFilename = histo_path;
+        normFeat(fs, clusters_from(clu_off, nsrc, seg_begin, seg_len), cfg, (unsigned long)first_col, (unsigned long)ncols);
+        fs.download(x);
+    })
+}
+
+// liagpu::featWarpHost (no device): runs [nrun x 3] = (first frame, length, unit); status (nullable) [nunits x D]
+int liagpu_feat_warp_host(float *x, long ld, int D, const long *runs, long nrun, long nunits, long nbBin, int nbin_t, const double *tbounds,
+                          const double *tcount, int *status)
+{
+    GUARD({
+        Histo t;
+        t.bounds.assign(tbounds, tbounds + nbin_t + 1); t.count.assign(tcount, tcount + nbin_t);
+        std::vector<int64_t> r(runs, runs + 3 * nrun);
+        std::vector<int> st;
+        featWarpHost(x, (unsigned long)ld, D, r, nunits, (unsigned long)nbBin, t, status ? &st : nullptr);
+        if (status) std::copy(st.begin(), st.end(), status);
+    })
+}
+
+// .histo files: nbin = liagpu_histo_bins(path) (< 0: error), then liagpu_histo_read fills bounds [nbin + 1] and count [nbin]
+long liagpu_histo_bins(const char *path)
+{
+    long n = -1;
+    const int rc = [&]() -> int { GUARD({ n = (long)readHistoFile(path).count.size(); }) }();
+    return rc ? -1 : n;
+}
+int liagpu_histo_read(const char *path, double *bounds, double *count)
+{
+    GUARD({
+        const Histo h = readHistoFile(path);
+        std::copy(h.bounds.begin(), h.bounds.end(), bounds);
+        std::copy(h.count.begin(), h.count.end(), count);
+    })
+}
+int liagpu_histo_write(const char *path, int nbin, const double *bounds, const double *count)
+{
+    GUARD({
+        Histo h;
+        h.bounds.assign(bounds, bounds + nbin + 1); h.count.assign(count, count + nbin);
+        writeHistoFile(path, h);
+    })
+}
+
+// liagpu::normFeatFiles with warp (the other arguments as liagpu_norm_feat_files); histo_path NULL or "": the refusal of the default target
+int liagpu_norm_feat_files_warp(int device, int n, const char **names, const char *feature_path, const char *load_ext, const char *save_path,
+                                const char *save_ext, const char *label_path, const char *label_ext, const char *label, double frameLength,
+                                const char *mask, int writeAllFeatures, int segmentalMode, int fileMode, int windowMode, int cmsOnly, int varOnly,
+                                long warpBinCount, int warpAdd01Norm, const char *histo_path)
+{
+    GUARD({
+        GpuServer srv(device);
+        NormFeatFilesCfg cfg;
+        cfg.norm.warp = true; cfg.norm.warpBinCount = (unsigned long)warpBinCount; cfg.norm.warpAdd01Norm = warpAdd01Norm != 0;
+        cfg.norm.warpGaussHistoFilename = histo_path ? histo_path : "";
+        cfg.norm.segmentalMode = segmentalMode != 0; cfg.norm.fileMode = fileMode != 0; cfg.norm.windowMode = windowMode != 0;
+        cfg.norm.cmsOnly = cmsOnly != 0; cfg.norm.varOnly = varOnly != 0;
+        cfg.featureFilesPath = feature_path ? feature_path : ""; cfg.loadFeatureFileExtension = load_ext ? load_ext : "";
+        cfg.saveFeatureFilePath = save_path ? save_path : ""; cfg.saveFeatureFileExtension = save_ext ? save_ext : "";
+        cfg.labelFilesPath = label_path ? label_path : ""; cfg.labelFilesExtension = label_ext ? label_ext : "";
+        cfg.labelSelectedFrames = label ? label : ""; cfg.frameLength = frameLength; cfg.featureServerMask = mask ? mask : "";
+        cfg.writeAllFeatures = writeAllFeatures != 0;
+        normFeatFiles(srv, std::vector<std::string>(names, names + n), cfg);
+    })
+}
+
 // ComputeTest from FILES for one ndx line (test file + client list): RAW models, .prm features with
 // featureServerMask, .lbl selection.  Writes the NIST-style result lines (segmental mode) into out_text
 // and the LLRs into llr_out[nseg x nClients].  ComputeTest.cpp:129-215 + the format readers of io.h.

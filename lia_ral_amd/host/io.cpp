@@ -69,6 +69,31 @@ void writeFeatureFile(const std::string &path, const FeatureFile &f)
     o.write((const char *)f.data.data(), f.data.size() * sizeof(float));
 }
 
+Histo readHistoFile(const std::string &path)
+{
+    std::ifstream in(path.c_str());
+    if (!in) throw Exception("cannot read [" + path + "]");
+    long nb = 0;
+    in >> nb;
+    if (!in || nb < 1) throw Exception("[" + path + "] is not a histo file (bin count)");
+    Histo h;
+    h.bounds.resize((size_t)nb + 1); h.count.resize((size_t)nb);
+    for (long i = 0; i < nb; ++i) in >> h.bounds[(size_t)i] >> h.count[(size_t)i];
+    in >> h.bounds[(size_t)nb];
+    if (!in) throw Exception("[" + path + "] is not a histo file (" + std::to_string(nb) + " bins announced)");
+    return h;
+}
+
+void writeHistoFile(const std::string &path, const Histo &h)
+{
+    if (h.empty() || h.bounds.size() != h.count.size() + 1) throw Exception("writeHistoFile: bounds must be one longer than count");
+    std::ofstream o(path.c_str(), std::ios::out | std::ios::trunc);
+    if (!o) throw Exception("cannot write [" + path + "]");
+    o << h.count.size() << "\n";
+    for (size_t i = 0; i < h.count.size(); ++i) o << h.bounds[i] << "\t" << h.count[i] << "\n";
+    o << h.bounds.back() << "\n";
+}
+
 std::vector<LabelSeg> readLabelFile(const std::string &path)
 {
     std::ifstream f(path.c_str());
@@ -636,16 +661,18 @@ void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const 
         else c = selectSegments(readLabelFile(cfg.labelFilesPath + names[k] + cfg.labelFilesExtension), cfg.labelSelectedFrames, cfg.frameLength, k);
         for (const Seg &g : c)
             if (g.begin + g.length > f.nFrames) throw Exception("normFeatFiles: a segment of [" + names[k] + "] ends after the last frame of the file");
-        if (cfg.norm.windowMode)
+        if (cfg.norm.windowMode || cfg.norm.warp)
             for (size_t i = 1; i < c.size(); ++i)
                 if (c[i].begin < c[i - 1].begin + c[i - 1].length)
-                    throw Exception("normFeatFiles: windowMode: the selected segments of [" + names[k] + "] overlap or are not in increasing order");
+                    throw Exception(std::string("normFeatFiles: ") + (cfg.norm.warp ? "warp" : "windowMode") + ": the selected segments of [" + names[k] + "] overlap or are not in increasing order");
         clusters.push_back(c);
     }
     if (!dim) throw Exception("normFeatFiles: no frames");
     std::vector<int> cols = parseFeatureMask(cfg.featureServerMask);
     if (cols.empty()) for (unsigned long c = 0; c < dim; ++c) cols.push_back((int)c);
     for (int c : cols) if ((unsigned long)c >= dim) throw Exception("featureServerMask selects a column beyond vectSize");
+    NormFeatCfg norm = cfg.norm;
+    if (norm.warp && norm.warpTarget.empty() && !norm.warpGaussHistoFilename.empty()) norm.warpTarget = readHistoFile(norm.warpGaussHistoFilename);
     std::vector<float> all((size_t)total * dim);
     for (size_t k = 0; k < files.size(); ++k)
         if (files[k].nFrames) memcpy(all.data() + (size_t)first[k] * dim, files[k].data.data(), files[k].data.size() * sizeof(float));
@@ -655,7 +682,7 @@ void normFeatFiles(GpuServer &srv, const std::vector<std::string> &names, const 
         for (size_t a = 0; a < cols.size();) {                 // one call per contiguous piece of the mask
             size_t b = a + 1;
             while (b < cols.size() && cols[b] == cols[b - 1] + 1) ++b;
-            NormFeatCfg nc = cfg.norm;
+            NormFeatCfg nc = norm;
             nc.frameLength = cfg.frameLength;                  // windowMode counts its windows in the label files' time base
             if (!nc.extMean.empty()) {
                 if (nc.extMean.size() != cols.size() || nc.extStd.size() != cols.size()) throw Exception("normFeatFiles: external mean / std must have one value per masked column");

@@ -33,6 +33,11 @@ std::vector<LabelSeg> readLabelFile(const std::string &path);
 SegCluster selectSegments(const std::vector<LabelSeg> &lab, const std::string &labelSelectedFrames, double frameLength,
                           unsigned long source = 0);
 
+// Histo::save files (NormFeat/test/*.histo): a line nbBin, nbBin lines "lowerBound count", the last upper bound; written with the
+// default ostream precision (%g), which is the precision of the reference's files.
+Histo readHistoFile(const std::string &path);
+void writeHistoFile(const std::string &path, const Histo &h);
+
 MixtureGD readMixtureRAW(const std::string &path);
 void writeMixtureRAW(const std::string &path, const MixtureGD &m);
 // XML mixture files (saveMixtureFileFormat XML; fixture LIA_SpkDet/TrainWorld/test/wld.validate):

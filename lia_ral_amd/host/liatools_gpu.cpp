@@ -2,6 +2,7 @@
 // all frame x Gaussian arithmetic happens in libgmmiv (HIP kernels).
 #include "liatools_gpu.h"
 #include "io.h"
+#include "../../include/ext/gmmiv_feat_warp.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1040,12 +1041,135 @@ void normFeatWindowPass(FeatureBuffer &fs, const std::vector<SegCluster> &select
     srv.check(gmmiv_feat_norm_window(srv.ctx(), fs.mutableDevice() + firstCol, GMMIV_F32, (int64_t)fs.getVectSize(), D, runs.data(), nrun, nfiles, stepOff.data(),
                                      steps.data(), alpha.data(), nsteps, flags, nullptr, nullptr));
 }
+// warp: the histograms of all units, then the warp of all units, two launches.  A run is one label segment, never cut: the entry
+// points want the runs of a unit in frame order.
+void normFeatWarpPass(FeatureBuffer &fs, const std::vector<int64_t> &runs, int64_t nunits, const NormFeatCfg &cfg, const Histo &target, unsigned long firstCol, int D)
+{
+    const int64_t nrun = (int64_t)(runs.size() / 3);
+    if (nrun == 0 || nunits == 0) return;
+    GpuServer &srv = fs.server();
+    const int64_t ld = (int64_t)fs.getVectSize();
+    float *x = fs.mutableDevice() + firstCol;
+    const size_t UD = (size_t)nunits * (size_t)D, nb = (size_t)cfg.warpBinCount;
+    double *bounds = (double *)srv.workspace(4, UD * (2 * nb + 1) * sizeof(double) + UD * sizeof(int32_t));
+    double *count = bounds + UD * (nb + 1);
+    int32_t *status = (int32_t *)(count + UD * nb);
+    // host tables: each call uploads them and returns when the stream has used them
+    srv.check(gmmiv_feat_warp_hist(srv.ctx(), x, GMMIV_F32, ld, D, runs.data(), nrun, nunits, (int)nb, 0, bounds, count, status));
+    srv.check(gmmiv_feat_warp_apply(srv.ctx(), x, GMMIV_F32, ld, x, GMMIV_F32, ld, D, runs.data(), nrun, nunits, (int)nb, bounds, count, status,
+                                    (int)target.count.size(), target.bounds.data(), target.count.data()));
+}
+void pushWholeRun(std::vector<int64_t> &runs, unsigned long first, unsigned long len, int64_t group)
+{
+    if (len == 0) return;
+    runs.push_back((int64_t)first); runs.push_back((int64_t)len); runs.push_back(group);
+}
+
+// the order of the sort of include/ext/gmmiv_feat_warp.h: the float's bits as a sign-magnitude integer
+inline uint32_t warpKey(float v)
+{
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+inline double warpArea(const double *b, const double *c, size_t i) { return c[i] * (b[i + 1] - b[i]); }   // areaHisto, AccumulateStat.cpp:424-427
+inline double warpLin(double val, double lower, double higher)                                            // linearInterpolation, :432-437
+{
+    const double EPS = 0.000000000000000000001;
+    const double interval = higher - lower;
+    if (interval < EPS) return 1;
+    return (val - lower) / interval;
+}
+// warping(), ScoreWarp.cpp:168-206, loop for loop (idxW is kept inside the table: a unit's own values never leave it)
+double warpValue(double score, const double *sb, const double *sc, size_t nb, const double *tb, const double *tc, size_t nt)
+{
+    double totalWarp = 0.0;
+    size_t idxW = 0;
+    for (; (idxW < nb) && (sb[idxW + 1] < score); idxW++);
+    if (idxW == nb) idxW = nb - 1;
+    for (size_t idx = 0; idx < idxW; idx++) totalWarp += warpArea(sb, sc, idx);
+    const double percentW = warpLin(score, sb[idxW], sb[idxW + 1]);
+    totalWarp += warpArea(sb, sc, idxW) * percentW;
+    double totalDest;
+    size_t idxD;
+    for (idxD = 0, totalDest = 0; (idxD < nt) && (totalDest < totalWarp); idxD++) totalDest += warpArea(tb, tc, idxD);
+    if (idxD == nt) {
+        idxD--;
+        totalDest -= warpArea(tb, tc, idxD);
+    } else if (idxD > 0) {
+        totalDest -= warpArea(tb, tc, idxD);
+        idxD--;
+    }
+    double ret = tb[idxD];
+    const double percentH = warpLin(totalWarp, totalDest, warpArea(tb, tc, idxD) + totalDest);
+    ret += (tb[idxD + 1] - tb[idxD]) * percentH;
+    return ret;
+}
 } // namespace
+
+void featWarpHost(float *x, unsigned long ld, int D, const std::vector<int64_t> &runs, int64_t nunits, unsigned long nbBin, const Histo &target,
+                  std::vector<int> *status)
+{
+    if (target.empty() || target.bounds.size() != target.count.size() + 1) throw Exception("featWarpHost: the target needs bounds one longer than count");
+    if (nbBin < 1) throw Exception("featWarpHost: nbBin >= 1 expected");
+    if (status) status->assign((size_t)nunits * (size_t)D, 0);
+    const size_t nrun = runs.size() / 3, nb = (size_t)nbBin, nt = target.count.size();
+    std::vector<float> v;
+    std::vector<double> b(nb + 1), c(nb);
+    size_t r0 = 0;
+    for (int64_t u = 0; u < nunits; ++u) {
+        size_t r1 = r0;
+        while (r1 < nrun && runs[3 * r1 + 2] == u) ++r1;
+        for (int col = 0; col < D; ++col) {
+            v.clear();
+            for (size_t r = r0; r < r1; ++r)
+                for (int64_t t = 0; t < runs[3 * r + 1]; ++t) v.push_back(x[(size_t)(runs[3 * r] + t) * ld + col]);
+            const size_t n = v.size();
+            bool degenerate = n == 0;
+            if (n) {
+                std::sort(v.begin(), v.end(), [](float p, float q) { return warpKey(p) < warpKey(q); });
+                const size_t k = n / nb;
+                for (size_t i = 0; i < nb; ++i) b[i] = (double)v[i * k];
+                b[nb] = (double)v[n - 1];
+                for (size_t i = 0; i < nb; ++i) {
+                    const double w = b[i + 1] - b[i];
+                    const size_t m = i + 1 < nb ? k : n - (nb - 1) * k;
+                    c[i] = ((double)m / (double)n) / w;
+                    if (!(w > 0 && w < HUGE_VAL)) degenerate = true;
+                }
+            }
+            if (status) (*status)[(size_t)u * D + col] = degenerate ? GMMIV_WARP_DEGENERATE : 0;
+            if (degenerate) continue;
+            for (size_t r = r0; r < r1; ++r)
+                for (int64_t t = 0; t < runs[3 * r + 1]; ++t) {
+                    float &f = x[(size_t)(runs[3 * r] + t) * ld + col];
+                    f = (float)warpValue((double)f, b.data(), c.data(), nb, target.bounds.data(), target.count.data(), nt);
+                }
+        }
+        r0 = r1;
+    }
+}
 
 void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSource, const NormFeatCfg &cfg, unsigned long firstCol, unsigned long nCols)
 {
     if (cfg.segmentalMode && cfg.windowMode) throw Exception(" Incompatible modes (segmental/windowMode)");
     if (cfg.cmsOnly && cfg.varOnly) throw Exception(" cmsOnly and varOnly are not compatible)");
+    if (cfg.cmsOnly && cfg.warp) throw Exception(" cmsOnly and warp are not compatible)");               // NormFeat.cpp:262-264
+    if (cfg.varOnly && cfg.warp) throw Exception(" varOnly and warp are not compatible)");
+    if (!cfg.extMean.empty() && cfg.warp) throw Exception(" externalStats and warp are not compatible)");
+    Histo target;
+    if (cfg.warp) {
+        if (cfg.windowMode) throw Exception("normFeat: warp with windowMode is not built (its histograms read frames an earlier window has rewritten)");
+        if (cfg.warpTarget.empty() && cfg.warpGaussHistoFilename.empty())
+            throw Exception("normFeat: warp needs warpGaussHistoFilename: the rand()-made default target (makeGausHisto) is not built");
+        target = cfg.warpTarget.empty() ? readHistoFile(cfg.warpGaussHistoFilename) : cfg.warpTarget;
+        if (target.bounds.size() != target.count.size() + 1 || target.empty()) throw Exception("normFeat: the warp target needs bounds one longer than count");
+        if (cfg.warpBinCount < 1 || cfg.warpBinCount > GMMIV_WARP_MAX_BINS) throw Exception("normFeat: warpBinCount must lie in [1, " + std::to_string(GMMIV_WARP_MAX_BINS) + "]");
+        for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
+            for (size_t i = 1; i < selectedPerSource[s].size(); ++i)
+                if (selectedPerSource[s][i].begin < selectedPerSource[s][i - 1].begin + selectedPerSource[s][i - 1].length)
+                    throw Exception("normFeat: warp: the segments of source " + std::to_string(s) + " overlap or are not in increasing order (segment " + std::to_string(i) + ")");
+    }
     if (selectedPerSource.size() != fs.getSourceCount()) throw Exception("normFeat: one SegCluster per source of the feature buffer expected");
     if (firstCol >= fs.getVectSize() || firstCol + nCols > fs.getVectSize()) throw Exception("normFeat: the column slice lies outside vectSize");
     const int D = (int)(nCols ? nCols : fs.getVectSize() - firstCol);
@@ -1059,11 +1183,25 @@ void normFeat(FeatureBuffer &fs, const std::vector<SegCluster> &selectedPerSourc
     if (cfg.segmentalMode) {
         int64_t group = 0;
         for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
-            for (const Seg &g : selectedPerSource[s]) pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, group++);
-        normFeatPass(fs, runs, group, cfg, firstCol, D);
+            for (const Seg &g : selectedPerSource[s]) {
+                if (cfg.warp) pushWholeRun(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, group++);
+                else pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, group++);
+            }
+        if (cfg.warp) normFeatWarpPass(fs, runs, group, cfg, target, firstCol, D);
+        else normFeatPass(fs, runs, group, cfg, firstCol, D);
     }
     if (cfg.windowMode) normFeatWindowPass(fs, selectedPerSource, cfg, firstCol, D);
     if (fileMode) {
+        runs.clear();
+        for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
+            for (const Seg &g : selectedPerSource[s]) {
+                if (cfg.warp) pushWholeRun(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, (int64_t)s);
+                else pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, (int64_t)s);
+            }
+        if (cfg.warp) normFeatWarpPass(fs, runs, (int64_t)selectedPerSource.size(), cfg, target, firstCol, D);
+        else normFeatPass(fs, runs, (int64_t)selectedPerSource.size(), cfg, firstCol, D);
+    }
+    if (cfg.warp && cfg.warpAdd01Norm) {                             // :475-483: mean / std of every source's cluster, after the warp
         runs.clear();
         for (unsigned long s = 0; s < selectedPerSource.size(); ++s)
             for (const Seg &g : selectedPerSource[s]) pushRuns(runs, fs.getFirstFeatureIndexOfASource(s) + g.begin, g.length, (int64_t)s);

@@ -531,12 +531,33 @@ std::vector<SegCluster> energyDetectorBatch(FeatureBuffer &fs, const std::vector
 // ignored by it like the reference does, fileMode with it applies the file pass afterwards (:272, :448); alone it is NOT followed by
 // the file pass (:243).  One plan on the host (gmmiv_plan_norm_windows) and one launch for all sources; a source is one workgroup, so
 // a single long source runs on one compute unit.  A cluster whose segments overlap or are out of order is refused.
+// warp (:362-368, :465-483, include/ext/gmmiv_feat_warp.h): every column of a unit -- a segment in segmentalMode, a source's selected
+// cluster in fileMode -- through its own warpBinCount-bin histogram onto the target table of warpGaussHistoFilename (a Histo::save
+// file; warpTarget, when not empty, is used instead of reading the file).  cmsOnly, varOnly and ext vectors with it are refused
+// (:262-264).  warpAdd01Norm (:475-483): the mean / std pass over every source's cluster afterwards.  A column whose histogram has a bin
+// without width is copied through (GMMIV_WARP_DEGENERATE).  Not built, refused with a message: warp with windowMode (its histograms
+// read frames an earlier window has rewritten), and the rand()-made default target (a target must be named).  The segments of a
+// cluster must be in increasing order and must not overlap.  Two launches for all sources.
+struct Histo {                                 // alize-core's Histo as Histo::save writes it: bounds [nbBin + 1], count [nbBin]
+    std::vector<double> bounds, count;
+    bool empty() const { return count.empty(); }
+};
 struct NormFeatCfg {
     bool segmentalMode = false, fileMode = false, cmsOnly = false, varOnly = false;
     std::vector<double> extMean, extStd;
     bool windowMode = false;
     double windowDuration = 5, windowComp = 1, frameLength = 0.01;
+    bool warp = false, warpAdd01Norm = false;
+    unsigned long warpBinCount = 40;
+    std::string warpGaussHistoFilename;
+    Histo warpTarget;
 };
+// The host-only twin of warp's per-unit loop (tests and tools/bench_feat_warp.py; one core, no device): x [. x ld] float32, in place on
+// the first D columns of the frames of runs [nrun x 3] = (first frame, length, unit), unit ids non-decreasing.  Per unit and column:
+// the values sorted (the order of include/ext/gmmiv_feat_warp.h), the histogram, then warping() (ScoreWarp.cpp:168-206) loop for loop.
+// status (optional) [nunits x D] receives 0 or GMMIV_WARP_DEGENERATE; such a column is left as it is.
+void featWarpHost(float *x, unsigned long ld, int D, const std::vector<int64_t> &runs, int64_t nunits, unsigned long nbBin, const Histo &target,
+                  std::vector<int> *status = nullptr);
 // ALL sources of the buffer in one batch: selectedPerSource[s] is the cluster of selected segments of source s (Seg::begin counts
 // from the source's first frame; Seg::source is ignored).  A pass is three enqueues on the whole batch -- gmmiv_frame_moments_groups,
 // gmmiv_frame_moments_stats, gmmiv_feat_norm_apply, one group per segment or per source, runs cut at 4096 frames, all with device

@@ -739,12 +739,77 @@ def norm_feat_window(x, clusters, src_first=None, window_duration=5.0, window_co
     return x
 
 
+def read_histo(path):
+    """liagpu::readHistoFile (a Histo::save file) -> (bounds [nbin + 1], count [nbin])"""
+    lib.liagpu_histo_bins.restype = ct.c_long
+    nb = lib.liagpu_histo_bins(path.encode())
+    if nb < 0:
+        raise HostError(lib.liagpu_last_error().decode())
+    b, c = np.zeros(nb + 1), np.zeros(nb)
+    _chk(lib.liagpu_histo_read(path.encode(), _d(b), _d(c)))
+    return b, c
+
+
+def write_histo(path, bounds, count):
+    """liagpu::writeHistoFile: the layout and the precision (%g) of Histo::save"""
+    b, c = np.ascontiguousarray(bounds, np.float64), np.ascontiguousarray(count, np.float64)
+    _chk(lib.liagpu_histo_write(path.encode(), len(c), _d(b), _d(c)))
+
+
+def _target(target):
+    if target is None:
+        return 0, None, None, None
+    if isinstance(target, str):
+        return 0, None, None, target.encode()
+    b, c = np.ascontiguousarray(target[0], np.float64), np.ascontiguousarray(target[1], np.float64)
+    return len(c), b, c, None
+
+
+def norm_feat_warp(x, clusters, target, src_first=None, segmental_mode=False, file_mode=False, warp_bin_count=40, warp_add01_norm=False,
+                   window_mode=False, cms_only=False, var_only=False, first_col=0, ncols=0, device=0):
+    """liagpu::normFeat with warp (NormFeat.cpp:362-368, 465-483) on float32 frames [T, D]: clusters and src_first as norm_feat takes
+    them, the segments of a cluster in increasing order; target = (bounds, count) or the path of a .histo file (warpGaussHistoFilename;
+    None: refused, the rand()-made default target is not built).  window_mode, cms_only, var_only are refused with it -> the frames."""
+    x = np.array(x, np.float32)
+    T, D = x.shape
+    sf = _sources(src_first, T)
+    off, b, l = _clusters(clusters)
+    nt, tb, tc, path = _target(target)
+    _chk(lib.liagpu_norm_feat_warp(device, x.ctypes.data_as(_fp), ct.c_long(T), D, ct.c_long(len(sf) - 1), sf.ctypes.data_as(_lp), off.ctypes.data_as(_lp),
+                                   b.ctypes.data_as(_lp), l.ctypes.data_as(_lp), int(segmental_mode), int(file_mode), int(window_mode), int(cms_only),
+                                   int(var_only), ct.c_long(warp_bin_count), int(warp_add01_norm), nt, None if tb is None else _d(tb),
+                                   None if tc is None else _d(tc), path, int(first_col), int(ncols)))
+    return x
+
+
+def feat_warp_host(x, runs, nunits, target, warp_bin_count=40):
+    """liagpu::featWarpHost, the host-only twin of warp's per-unit loop (no device): float32 frames [T, D], runs [nrun, 3] = (first frame,
+    length, unit), target = (bounds, count) -> (the warped frames, status [nunits, D])"""
+    x = np.array(x, np.float32)
+    T, D = x.shape
+    r = np.ascontiguousarray(runs, np.int64).reshape(-1, 3)
+    tb, tc = np.ascontiguousarray(target[0], np.float64), np.ascontiguousarray(target[1], np.float64)
+    st = np.zeros((nunits, D), np.int32)
+    _chk(lib.liagpu_feat_warp_host(x.ctypes.data_as(_fp), ct.c_long(D), D, r.ctypes.data_as(_lp), ct.c_long(len(r)), ct.c_long(nunits),
+                                   ct.c_long(warp_bin_count), len(tc), _d(tb), _d(tc), st.ctypes.data_as(ct.POINTER(ct.c_int))))
+    return x, st
+
+
 def norm_feat_files(names, feature_path="", load_ext=".prm", save_ext=".norm.prm", label_path="", label_ext=".lbl", label="speech",
                     frame_length=0.01, mask="", write_all_features=True, save_path="", segmental_mode=False, file_mode=False, cms_only=False,
-                    var_only=False, device=0, window_mode=False, window_duration=5.0, window_comp=1.0):
+                    var_only=False, device=0, window_mode=False, window_duration=5.0, window_comp=1.0, warp=False, warp_bin_count=40,
+                    warp_gauss_histo_filename="", warp_add01_norm=False):
     """liagpu::normFeatFiles: <feature_path><name><load_ext> -> <save_path or feature_path><name><save_ext> for every name, one batch.
-    window_mode: NormFeat's windowMode with window_duration / window_comp (segmental_mode with it is refused, file_mode follows it)."""
+    window_mode: NormFeat's windowMode with window_duration / window_comp (segmental_mode with it is refused, file_mode follows it).
+    warp: feature warping onto the table of warp_gauss_histo_filename (needed), warp_bin_count bins per histogram, warp_add01_norm the
+    mean / std pass afterwards; window_mode, cms_only and var_only with it are refused."""
     arr = (ct.c_char_p * len(names))(*[n.encode() for n in names])
+    if warp:
+        _chk(lib.liagpu_norm_feat_files_warp(device, len(names), arr, feature_path.encode(), load_ext.encode(), save_path.encode(), save_ext.encode(),
+                                             label_path.encode(), label_ext.encode(), label.encode(), ct.c_double(frame_length), mask.encode(),
+                                             int(write_all_features), int(segmental_mode), int(file_mode), int(window_mode), int(cms_only),
+                                             int(var_only), ct.c_long(warp_bin_count), int(warp_add01_norm), warp_gauss_histo_filename.encode()))
+        return
     if window_mode:
         if segmental_mode:
             raise HostError(" Incompatible modes (segmental/windowMode)")
